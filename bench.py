@@ -1,7 +1,13 @@
 """Headline benchmark (driver contract: one process per GPU, rank 0 prints ONE JSON line).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full      # + every leg beside the headline (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps of the headline PairHMM path and prints the line; --full adds the
+queue, ragged, CPU-baseline, sortmardup, Smith-Waterman, BGZF, CLI, mixed and regions legs (the --no-* options and
+the sizes select among them).  --dump-outputs DIR writes the headline path's results of its last timed step
+(pairhmm_log10.npy, pairhmm_used_f64.npy, pairhmm_index.npy; a seeded sample above 2M test cases) for comparing builds.
 
 PairHMM (`value`, GCUPS):
   N = 1  BASELINE.json configs[1]: 1M synthetic test cases, read 128 x haplotype 256 (sub-run 2a), resident in HBM.
@@ -422,6 +428,26 @@ def timed_resident(eng, batch, steps, warmup, barrier):
     return dt, batch.stats()
 
 
+DUMP_MAX_PAIRS = 2 << 20       # 20 bytes per dumped test case (log10, used_f64, index): 40 MB at most over all ranks
+
+
+def dump_outputs(out_dir, batch, lo, rank, world):
+    """What a caller of the timed path receives after its last step: the log10 likelihood of every test case and
+    whether it was computed in fp64.  Above DUMP_MAX_PAIRS (over all ranks) a fixed, seeded sample of test cases is
+    written, with their indices in the stream."""
+    out, used = batch.results(with_flags=True)
+    idx = np.arange(lo, lo + len(out), dtype=np.int64)
+    cap = DUMP_MAX_PAIRS // world
+    if len(out) > cap:
+        keep = np.sort(np.random.default_rng(0x5EED0D00 + rank).choice(len(out), cap, replace=False))
+        out, used, idx = out[keep], used[keep], idx[keep]
+    tag = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"pairhmm_log10{tag}.npy"), out.astype(np.float64))
+    np.save(os.path.join(out_dir, f"pairhmm_used_f64{tag}.npy"), used.astype(np.float32))
+    np.save(os.path.join(out_dir, f"pairhmm_index{tag}.npy"), idx.astype(np.float64))
+
+
 def pairhmm_rooflines(st, traffic):
     """the binding roof of the PairHMM recurrence is fp32 VECTOR issue (12 flop per cell against the
     157.3 TFLOP/s vector peak), so that is what `roofline` reports; the HBM fraction BASELINE.json's
@@ -556,6 +582,11 @@ def main():
                                                              "pipeline co-resident on every GPU)")
     ap.add_argument("--mixed", action="store_true", help="(default since round 3; kept so that older command lines still parse)")
     ap.add_argument("--mixed-seconds", type=float, default=1.0, help="window of each solo phase of the configs[4] leg; the co-resident phase runs twice that")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (queue, ragged, CPU baselines, sortmardup, "
+                                                        "Smith-Waterman, BGZF, the CLI, mixed, regions; the --no-* options and sizes above "
+                                                        "select among them); without it only the headline PairHMM steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline path's results of its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -611,6 +642,8 @@ def main():
     dt, st = timed_resident(eng, batch, args.steps, args.warmup, barrier)
     tmax = max_over_ranks(dt)
     value = total * 128 * 256 * args.steps / tmax / 1e9    # every test case of the stream is 128 x 256 cells
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch, lo, rank, world)
     batch.close()
 
     line = None
@@ -628,7 +661,7 @@ def main():
 
     # ---- the same shard through the host work queue: host buffers in, results in host memory out (PCIe-inclusive;
     # never `value`).  Lanes pack / upload batch k+1 while the kernels of batch k run.
-    if not args.no_queue:
+    if args.full and not args.no_queue:
         lanes = args.queue_lanes or max(2, min(8, host_cores() // world))      # the ranks of a node share its cores
         if world == 1:
             # at one GPU the resident batch is configs[1] (1M test cases); the queue is measured on a longer stream of the
@@ -662,7 +695,7 @@ def main():
         del qout
 
     # ---- sub-run 2b: ragged lengths R in [32,128], H in [64,256]
-    if not args.no_ragged:
+    if args.full and not args.no_ragged:
         n2 = hi - lo if world == 1 else min(hi - lo, 1 << 20)
         d2 = synth.gen_pairhmm_pairs_fast(n2, 0x5EED0002 + 0x100 * rank, r_range=(32, 128), h_range=(64, 256), threads=host_threads(world))
         b2 = eng.batch(d2)
@@ -679,21 +712,22 @@ def main():
                               "valu_all_kernels": {"frac": 12.0 * d2["cells"] / (st2["ms_f32"] * 1e-3) / 1e12 / VALU_FP32_PEAK_TFLOPS,
                                                    "note": "all fp32 launches of a step (one per read-length class), 12 flop per cell"}}
         del d2
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(synth, 1 << 18, seed)
     d = prepared = None
     eng.close()
 
     # ---- second half of BASELINE.json's metric: sortmardup Mrecords/s (configs[3]) ------------
-    sort_line = None
-    if args.sort_records > 0:
-        sort_line = sortmardup_leg(pkg, synth, args, rank, local_rank, world, dist, torch, backend)
-    sw_line = smithwaterman_leg(pkg, synth, args, rank, local_rank) if args.sw_pairs > 0 else None
-    bgzf_line = bgzf_leg(pkg, synth, args, rank, local_rank) if args.bgzf_mb > 0 else None
-    cli_line = cli_leg(pkg, synth, args, rank) if args.cli_records > 0 else None
-    mixed_line = mixed_leg(pkg, synth, args, rank, local_rank, world, shard, barrier, max_over_ranks) if not args.no_mixed else None
+    sort_line = sw_line = bgzf_line = cli_line = mixed_line = None
+    if args.full:
+        if args.sort_records > 0:
+            sort_line = sortmardup_leg(pkg, synth, args, rank, local_rank, world, dist, torch, backend)
+        sw_line = smithwaterman_leg(pkg, synth, args, rank, local_rank) if args.sw_pairs > 0 else None
+        bgzf_line = bgzf_leg(pkg, synth, args, rank, local_rank) if args.bgzf_mb > 0 else None
+        cli_line = cli_leg(pkg, synth, args, rank) if args.cli_records > 0 else None
+        mixed_line = mixed_leg(pkg, synth, args, rank, local_rank, world, shard, barrier, max_over_ranks) if not args.no_mixed else None
     if rank == 0:
-        if not args.no_regions:
+        if args.full and not args.no_regions:
             line["regions"] = regions_leg(pkg, synth, local_rank, 3)      # three lanes, 131072 test cases per batch: the best of the sweep in profiles/r03_regions_queue_sweep.txt
         if mixed_line is not None:
             line["mixed"] = mixed_line
