@@ -31,6 +31,9 @@
 //     sumM and sumX apart, and read from lane nl-1 at the end (as the reference does).
 //   * fp32 results < 1e-28f are appended to a re-run list; the same template instantiated for
 //     double processes that list (IntelPairHmm.cc:338-350).
+//   * The cell is not computed in the reference's 8-operation order but in an algebraically equal
+//     one: 6 operations in fp32 (X scaled by pGAPM of the row below, Y carried divided by its own
+//     row's pMY), 7 in fp64; see the comment above `use_plain`.
 
 #include <type_traits>
 
@@ -173,6 +176,7 @@ template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false>
 __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem, const uint32_t block, const uint32_t n_blocks) {
     constexpr int GPW = 64 / G;                   // groups per wavefront
     constexpr bool kETab = (sizeof(T) == 4);      // fp32: emission table in LDS; fp64: compare+select
+    constexpr bool kSix = (sizeof(T) == 4) && !EXACT;   // fp32: the 6-operation cell; fp64: the scaled 7-operation cell (see sweep)
     constexpr int RP2 = (RPL + 1) / 2;
     constexpr int S = lane_stride<G>();           // lane stride of a group inside its DPP row
     const int gpb = (int)blockDim.x / G;          // groups per block
@@ -354,23 +358,36 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
             }
         };
 
-        // The sweep in two algebraic forms (selected per wavefront):
+        // The sweep in three algebraic forms (plain, or the precision's fast form; selected per wavefront):
         //  plain  (the reference's operation order, avx-pairhmm-template.h:177-192), 8 ops per cell:
         //      M = ((M2*pMM + X2*pGAPM) + Y2*pGAPM) * e ;  X = M1*pMX + X1*pXX ;  Y = Ml*pMY + Yl*pYY
-        //  scaled, 7 ops per cell: rows carry X^ = g'*X and Y^ = g'*Y, g' = pGAPM of the row BELOW
+        //  scaled (fp64), 7 ops per cell: rows carry X^ = g'*X and Y^ = g'*Y, g' = pGAPM of the row BELOW
         //  (the only consumer of X and Y across rows), so the consumer needs no multiply:
         //      M  = (fma(pMM, M2, X^2) + Y^2) * e
         //      X^ = A*M1 + B*X^1     A = g'*pMX,  B = g'*pXX/g   (g = this row's pGAPM)
         //      Y^ = C*Ml + D*Y^l     C = g'*pMY,  D = pYY
         //  Read row R has no row below: g' = 1 there, so its X^ is X and the final sums are unchanged.
+        //  six (fp32), 6 ops per cell: X^ as in the scaled form, Y carried as y = Y / pMY of its own row.  Y's
+        //  recurrence runs along the row, so that scale never changes along it and y needs no multiply:
+        //      M  = fma(q, y2, fma(pMM, M2, X^2)) * e     q = g * pMY' (pMY' = pMY of the row above, 1 for row 0)
+        //      X^ = A*M1 + B*X^1
+        //      y  = pYY*yl + Ml
+        //  The match-to-match path (pMM, e) carries table values only, as in the reference: a rounded per-row
+        //  product on it (e*g or pMM/g) adds a bias of up to an ulp per row, which over a 1000-row read
+        //  reaches 1.5e-5 in log10 (tools/dev_cell_emulate.py).  y <= max M / (1 - pYY) <= 4.9 max M for
+        //  gap-continuation bytes >= 1, and pMY' is a table value, so q has the same bits wherever the row
+        //  above lives (this lane, the lane above, the previous strip).
         //  B divides by g, so a wavefront that sees a row with pGAPM == 0 (gap-continuation byte 0)
         //  takes the plain form.
         const bool use_plain = EXACT || __any((int)zero_gap) != 0;
+        constexpr int kPlain = 0, kScaled = 1, kSixOp = 2;
 
-        auto sweep = [&](auto scaled_tag) {
-            constexpr bool SC = decltype(scaled_tag)::value;
+        auto sweep = [&](auto form_tag) {
+            constexpr int FORM = decltype(form_tag)::value;
+            constexpr bool SC = FORM == kScaled;
+            constexpr bool SIX = FORM == kSixOp;
             T y_above = init_y;                     // what the group's lane 0 sees above its top row
-            if constexpr (SC) {
+            if constexpr (SC || SIX) {
                 // g of the row below each row: next row in this lane, or the next lane's top row
                 T g_own[RPL], g_below[RPL];
 #pragma unroll
@@ -382,21 +399,38 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     g_below[RPL - 1] = (T)1.0;
                     if constexpr (STRIP) { if (!last_strip) g_below[RPL - 1] = (T)1.0 - ph2pr[a.gcp[job.read_off + (uint64_t)(row_base + rows_here)] & 127]; }
                 }
+                // six: pMY of the row above each row -- this lane's row s - 1, or lane j - 1's bottom row; above the group's
+                // lane 0 lies the boundary row (pMY_0 := 1, so y_0 = INITIAL/H) or the previous strip's last read row.
+                // A row-0 clone passes pMY' = 1 on.
+                T my_above[RPL];
+                if constexpr (SIX) {
+                    T my_own[RPL];
+#pragma unroll
+                    for (int s = 0; s < RPL; ++s) my_own[s] = clone[s] ? (T)1.0 : k4[s];
+                    T my_top = (T)1.0;
+                    if constexpr (STRIP) {
+                        if (strip > 0) my_top = ph2pr[a.del[job.read_off + (uint64_t)(row_base - 1)] & 127];
+                    }
+                    my_above[0] = shr1<G>(my_top, my_own[RPL - 1]);
+#pragma unroll
+                    for (int s = 1; s < RPL; ++s) my_above[s] = my_own[s - 1];
+                }
 #pragma unroll
                 for (int s = 0; s < RPL; ++s) {
                     if (clone[s]) {
-                        py[s] = g_below[s] * init_y;             // Y^ of a row-0 clone, constant (D = 1)
+                        py[s] = SIX ? init_y : g_below[s] * init_y;   // Y^ / y of a row-0 clone, constant (D = 1)
                     } else {
                         const T gb = g_below[s];
                         const T pMX = k2[s], pXX = k3[s], pMY = k4[s];
                         k1[s] = gb * pMX;                        // A
                         k2[s] = gb * ratio[s];                   // B = g' * (pXX / g), ratio from the table
-                        k3[s] = gb * pMY;                        // C
+                        if constexpr (SIX) k3[s] = g_own[s] * my_above[s];   // q = g * pMY'
+                        else k3[s] = gb * pMY;                               // C
                         k4[s] = pXX;                             // D = pYY
                     }
                     if (clone[s]) { k1[s] = 0; k2[s] = 0; k3[s] = 0; k4[s] = 1; }
                 }
-                y_above = g_own[0] * init_y;
+                y_above = SIX ? init_y : g_own[0] * init_y;
             }
             const T old_y = (j == 0) ? y_above : (T)0;
             T uaM = 0, uaX = 0, uaY = old_y, ubM = 0, ubX = 0, ubY = old_y;   // two shifted-in sets
@@ -418,7 +452,17 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 // copy in the tail loop must round identically, or a pair's result would depend on
                 // how many of its columns ran in which loop, i.e. on its wavefront neighbours.
                 T Mn[RPL], Xn[RPL], Yn[RPL];
-                if constexpr (SC) {
+                if constexpr (SIX) {
+                    Mn[0] = fma_(k3[0], o2Y, fma_(o2M, k0[0], o2X)) * ec[0];
+                    Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
+                    Yn[0] = fma_(py[0], k4[0], pm[0]);
+#pragma unroll
+                    for (int s = 1; s < RPL; ++s) {
+                        Mn[s] = fma_(k3[s], py[s - 1], fma_(pm[s - 1], k0[s], px[s - 1])) * ec[s];
+                        Xn[s] = fma_(Xn[s - 1], k2[s], Mn[s - 1] * k1[s]);
+                        Yn[s] = fma_(py[s], k4[s], pm[s]);
+                    }
+                } else if constexpr (SC) {
                     Mn[0] = (fma_(o2M, k0[0], o2X) + o2Y) * ec[0];
                     Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
                     Yn[0] = fma_(py[0], k4[0], pm[0] * k3[0]);
@@ -497,9 +541,10 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 load_e(hn, e);
             }
         };
-        if constexpr (EXACT) sweep(std::integral_constant<bool, false>{});
-        else if (use_plain) sweep(std::integral_constant<bool, false>{});
-        else sweep(std::integral_constant<bool, true>{});
+        if constexpr (EXACT) sweep(std::integral_constant<int, kPlain>{});
+        else if (use_plain) sweep(std::integral_constant<int, kPlain>{});
+        else if constexpr (kSix) sweep(std::integral_constant<int, kSixOp>{});
+        else sweep(std::integral_constant<int, kScaled>{});
       }   // strips
 
         // ---- result (IntelPairHmm.cc:338-350)
@@ -633,21 +678,27 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
         // ---- per-row constants in two passes, so that few values are live at a time (the 128 registers of 4 wavefronts
         //      per SIMD are all spoken for by the sweep).  Slot t = half * P + k of the lane holds read row
         //      j * RPL + t - top_clones; register pair k = (slot k, slot P + k).
-        //      Pass 1: pGAPM of every row (0 for clones and unused slots) -> g' = pGAPM of the row below.
-        T g_own[RPL];
+        //      Pass 1: pGAPM of every row (0 for clones and unused slots) -> g' = pGAPM of the row below, and pMY of every
+        //      row (1 for clones: pMY_0 := 1) -> pMY' = pMY of the row above.
+        T g_own[RPL], my_own[RPL];
 #pragma unroll
         for (int t = 0; t < RPL; ++t) {
             const int rho = j * RPL + t - top_clones;
             const int q = 2 * j + (t >= P ? 1 : 0);
             g_own[t] = 0;
+            my_own[t] = 0;
             if (live && q < nh && rho >= 0) {
                 const int qc = a.gcp[job.read_off + (uint64_t)rho] & 127;
                 g_own[t] = (T)1.0 - ph2pr[qc];
-                to_f64 |= (qc == 0);                      // pGAPM == 0: the scaled form divides by it (see below)
+                my_own[t] = ph2pr[a.del[job.read_off + (uint64_t)rho] & 127];
+                to_f64 |= (qc == 0);                      // pGAPM == 0: the cell divides by it (see below)
+            } else if (live && q < nh) {
+                my_own[t] = 1;
             }
         }
         const T g_next_lane = shr1_down<G>(g_own[0]);
-        //      Pass 2: the scaled coefficients (pairhmm_body's "scaled" form) and the emission table, row by row.
+        const T my_prev_lane = shr1<G>((T)1.0, my_own[RPL - 1]);     // lane j - 1's bottom row; the boundary row for lane 0
+        //      Pass 2: the coefficients of pairhmm_body's 6-operation cell and the emission table, row by row.
         f2 K0[P], K1[P], K2[P], K3[P], K4[P], pm[P], px[P], py[P];
         {
             float* et = reinterpret_cast<float*>(etab) + lane;
@@ -660,8 +711,8 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
                 T c0 = 0, cA = 0, cB = 0, cC = 0, cD = 0, y0 = 0, eM = 0, eX = 0;
                 int rb = 0;
                 if (live && q < nh) {
-                    if (rho < 0) {                        // a clone of row 0: Y^ = g' * INITIAL / H for ever (D = 1)
-                        cD = 1; y0 = gb * init_y;
+                    if (rho < 0) {                        // a clone of row 0: y = INITIAL / H for ever (D = 1)
+                        cD = 1; y0 = init_y;
                     } else {
                         const uint64_t o = job.read_off + (uint64_t)rho;
                         const int qi = a.ins[o] & 127, qd = a.del[o] & 127, qc = a.gcp[o] & 127;
@@ -670,7 +721,7 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
                         c0 = mm[((mx * (mx + 1)) >> 1) + mn];
                         cA = gb * ph2pr[qi];              // A = g' * pMX
                         cB = gb * gap_ratio[qc];          // B = g' * pXX / g
-                        cC = gb * ph2pr[qd];              // C = g' * pMY
+                        cC = g_own[t] * (t > 0 ? my_own[t - 1] : my_prev_lane);     // q = g * pMY'
                         cD = ph2pr[qc];                   // D = pYY
                         eM = (T)1.0 - ph2pr[qq];
                         rb = base_code(a.bases[o]);
@@ -687,7 +738,7 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
         }
 #pragma unroll
         for (int k = 0; k < P; ++k) { pm[k] = f2{0, 0}; px[k] = f2{0, 0}; }
-        const T y_above = g_own[0] * init_y;
+        const T y_above = init_y;
         const T py_mid = py[P - 1].x;
         __syncthreads();
 
@@ -708,7 +759,7 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
 
         const uint8_t* hp_lane = hapbuf + (PAD - 2 * j);       // hp_lane[d] = code of the LOW half's column at step d
         const uint8_t* et_lane = etab + lane * 4;
-        // A test case with a gap-continuation byte of 0 (pGAPM == 0) cannot take the scaled form (B divides by pGAPM) and
+        // A test case with a gap-continuation byte of 0 (pGAPM == 0) cannot take the 6-operation form (B divides by pGAPM) and
         // this kernel carries no plain form (its second copy of the sweep costs 22 registers: 3 instead of 4 wavefronts
         // per SIMD): such a test case goes to the double-precision list, whose kernel has both forms.  The decision is
         // per test case (its group's lanes), never per wavefront, so a value does not depend on the batch it is in.
@@ -727,16 +778,16 @@ __device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* sm
             f2 uaM = {0, 0}, uaX = {0, 0}, uaY = {old_y, py_mid}, ubM = {0, 0}, ubX = {0, 0}, ubY = {old_y, py_mid};
 
             auto column = [&](const f2 (&ec)[P], f2& o2M, f2& o2X, f2& o2Y, const f2 o1M, const f2 o1X, bool count) {
-                // the scaled 7-operation cell of pairhmm_body, two rows per instruction
+                // the 6-operation cell of pairhmm_body, two rows per instruction
                 f2 Mn[P], Xn[P], Yn[P];
-                Mn[0] = (pk_fma(o2M, K0[0], o2X) + o2Y) * ec[0];
+                Mn[0] = pk_fma(K3[0], o2Y, pk_fma(o2M, K0[0], o2X)) * ec[0];
                 Xn[0] = pk_fma(o1X, K2[0], o1M * K1[0]);
-                Yn[0] = pk_fma(py[0], K4[0], pm[0] * K3[0]);
+                Yn[0] = pk_fma(py[0], K4[0], pm[0]);
 #pragma unroll
                 for (int k = 1; k < P; ++k) {
-                    Mn[k] = (pk_fma(pm[k - 1], K0[k], px[k - 1]) + py[k - 1]) * ec[k];
+                    Mn[k] = pk_fma(K3[k], py[k - 1], pk_fma(pm[k - 1], K0[k], px[k - 1])) * ec[k];
                     Xn[k] = pk_fma(Xn[k - 1], K2[k], Mn[k - 1] * K1[k]);
-                    Yn[k] = pk_fma(py[k], K4[k], pm[k] * K3[k]);
+                    Yn[k] = pk_fma(py[k], K4[k], pm[k]);
                 }
 #pragma unroll
                 for (int k = 0; k < P; ++k) { pm[k] = Mn[k]; px[k] = Xn[k]; py[k] = Yn[k]; }
@@ -813,12 +864,13 @@ __global__ __launch_bounds__(256, P == 4 ? MGX_HMM_PK_MINWAVES : 1) void pairhmm
 // per lane at exactly 128 -- except 7 rows per lane (129 registers), which the bound brings to 128 at the cost of one or
 // two values parked in scratch outside the sweep.  The bound is applied to that class ONLY: on the 8-row classes it
 // changes the allocator's choices and parks 16-18 values (236 MB of scratch writes per 1 M test cases; same duration).
-// (Holding 11 rows per lane -- 171 registers -- to the 168 of 3 wavefronts spills 19: not done.)
+// (Holding 11 rows per lane -- 171 registers -- to the 168 of 3 wavefronts spills 19: not done.)  10 rows per lane (the
+// 151-base reads) need 169 with the 6-operation cell: held to the 168 of 3 wavefronts.
 template <typename T, int G, int RPL>
 #ifndef MGX_HMM_MINWAVES_8
 #define MGX_HMM_MINWAVES_8 4
 #endif
-__global__ __launch_bounds__(256, (sizeof(T) == 4 && RPL == 7) ? MGX_HMM_MINWAVES_8 : 1) void pairhmm_fwd(KernelArgs a) {
+__global__ __launch_bounds__(256, (sizeof(T) == 4 && RPL == 7) ? MGX_HMM_MINWAVES_8 : (sizeof(T) == 4 && RPL == 10) ? 3 : 1) void pairhmm_fwd(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     pairhmm_body<T, G, RPL>(a, smem, blockIdx.x, gridDim.x);
 }
