@@ -13,16 +13,15 @@
 //   * CIGAR text and its capacity rule (host, next to the caller's buffer): PairWiseSW.h:410-444
 //
 // Back-trace bytes are laid out by (step, lane, row-in-lane) so that one step of a wavefront stores
-// 64 * RPL consecutive bytes; the trace kernels convert (i, j) back to that index (BtView).
+// 64 * RPL consecutive bytes; the trace kernel converts (i, j) back to that index (BtView).
 //
 // Two fill kernels (round 3):
 //   k_sw_fill16   packed 16-bit scores, two pairs per lane group, the four decisions of a cell taken from the sign bits of four
 //                 packed differences, back-trace nibbles, all row classes in one launch -- for every pair whose scores provably fit
 //                 16 bits (I16Rule; the realignment workload of Mutect2 always does): 12.6 instructions per cell
 //   k_sw_fill     32-bit scores, one pair per lane group, compare + select per decision, back-trace bytes, one launch per row class
-//                 -- everything else (long references with long alternates, large scoring parameters); optionally with the lanes
-//                 over the alternate sequence (TR; measured slower, opt-in)
-// Both write what the trace kernels read through BtView / LastRow / LastCol; a batch may mix them pair by pair.
+//                 -- everything else (long references with long alternates, large scoring parameters)
+// Both write what the trace kernel reads through BtView / LastRow / LastCol; a batch may mix them pair by pair.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,13 +66,12 @@ struct SwJob {
     u64 sc_off;          // score arena (int32): last_row[ncol + 1] then last_col[nrow + 1]
     u64 el_off;          // element arena (int16): 2 * (len1 + len2 + 2)
     u32 len1, len2, rpl, strategy, out_index;
-    u32 g;               // bits 0-7: lanes per pair (32 or 64) | kJobTr | kJobI16 | kJobHalf
+    u32 g;               // bits 0-7: lanes per pair (32 or 64) | kJobI16 | kJobHalf
     u64 lr_off;          // 16-bit fill: the last lane's H values per swept position (back-trace arena, bytes)
     u64 lc_off;          // 16-bit fill: every lane's packed H values at the pair's last swept position
     int32_t low16;       // 16-bit fill: this pair's stand-in for LOW_INIT_VALUE
     u32 pad_;
 };
-constexpr u32 kJobTr = 0x100u;      // k_sw_fill<.., TR>: the lanes own the alternate sequence
 constexpr u32 kJobI16 = 0x200u;     // k_sw_fill16: packed 16-bit scores, two pairs per lane group, back-trace nibbles
 constexpr u32 kJobHalf = 0x400u;    // k_sw_fill16: this pair is the high half of its lane group
 constexpr u32 kNoOutput = 0xFFFFFFFFu;   // out_index of a filler job (a 16-bit class is padded to whole wavefronts)
@@ -88,14 +86,7 @@ struct SwParams { int match, mismatch, open, extend; };
 // bits 0-1 op, bit 2 INSERT_EXT, bit 3 DELETE_EXT (PairWiseSW.h:31-66).  (Storing the length of the
 // diagonal match run in the spare bits, so that the trace crosses a run in one step, was measured:
 // trace 0.58 -> 0.38 ms, fill 1.14 -> 1.42 ms per 20 000 pairs -- not kept.)
-// TR (round 3): the lanes own the ALTERNATE sequence's positions (columns j) and sweep the reference (rows i) -- the
-// transposed recurrence.  The reads realigned after PairHMM are 100-151 bases against haplotype windows of 250-400: with the
-// lanes over the reference, 64 lanes x 8 rows hold 250-400 rows (49-78 % of the row slots) and a pair takes ncol + 63 steps of
-// which ncol do work (66 %); with the lanes over the read, 32 lanes x 4-5 positions hold 100-151 (78-100 %) and a pair takes
-// nrow + 31 steps of which nrow do work (91 %), two pairs per wavefront.  Every cell computes the same values with the same tie
-// rules: E (horizontal gap) is the state carried along the sweep when the lanes own rows and the chain handed from position to
-// position when they own columns, F (vertical gap) the other way round; H still prefers the diagonal, then E, then F.
-template <int G, int RPL, bool TR>
+template <int G, int RPL>
 __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, u32 n_jobs, const u8* __restrict__ s1, const u8* __restrict__ s2,
                                                 u8* __restrict__ bt, int32_t* __restrict__ sc, u32 lds_stride, SwParams P) {
     extern __shared__ u8 sh_all[];                    // the swept sequences: one global load per step would
@@ -106,14 +97,14 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
     SwJob J{};
     if (live) J = jobs[job_idx];
     const int nrow = (int)J.len1, ncol = (int)J.len2;
-    const int n_own = TR ? ncol : nrow, n_swp = TR ? nrow : ncol;      // positions spread over the lanes | positions swept
+    const int n_own = nrow, n_swp = ncol;             // positions spread over the lanes | positions swept
     const bool indel = J.strategy == MGX_SW_INDEL || J.strategy == MGX_SW_LEADING_INDEL;
-    const u8* own = TR ? s2 + J.off2 : s1 + J.off1;
-    const u8* swp = TR ? s1 + J.off1 : s2 + J.off2;
+    const u8* own = s1 + J.off1;
+    const u8* swp = s2 + J.off2;
     int32_t* last_row = sc + J.sc_off;               // H(nrow, j), j = 1 .. ncol
     int32_t* last_col = last_row + ncol + 1;         // H(i, ncol), i = 1 .. nrow
-    int32_t* const edge_own = TR ? last_col : last_row;      // written step by step by the lane that owns the last position
-    int32_t* const edge_swp = TR ? last_row : last_col;      // the registers after the last step
+    int32_t* const edge_own = last_row;              // written step by step by the lane that owns the last position
+    int32_t* const edge_swp = last_col;              // the registers after the last step
     u8* btp = bt + J.bt_off;
     u8* sh_b = sh_all + (size_t)grp * lds_stride;
     for (int x = lane; x < n_swp; x += G) sh_b[x] = swp[x];
@@ -161,9 +152,9 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
                 const int gc_new = max(ext_c, open_c);
                 // E is the horizontal gap (INSERT), F the vertical one (DELETE); ties prefer the extension
                 int ext = 0;
-                if (!(open_s > ext_s)) ext |= TR ? kDeleteExt : kInsertExt;
-                if (!(open_c > ext_c)) ext |= TR ? kInsertExt : kDeleteExt;
-                const int ee = TR ? gc_new : gs_new, ff = TR ? gs_new : gc_new;
+                if (!(open_s > ext_s)) ext |= kInsertExt;
+                if (!(open_c > ext_c)) ext |= kDeleteExt;
+                const int ee = gs_new, ff = gc_new;
                 int h = max(diag + (sa[k] == c2 ? P.match : P.mismatch), kMinCutoff);
                 int op = kOpMatch;
                 if (ee > h) { op = kOpInsert; h = ee; }
@@ -208,7 +199,7 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
 //   * back-trace: one 32-bit word per lane, step and four rows: low half = the first pair's four nibbles (row 4q in bits 0-3),
 //     high half = the second pair's; nibble = {8: E opened, 4: F opened, 2: E > diagonal, 1: F > max(diagonal, E)}
 //   * H(nrow, j): the lane that owns a pair's last row stores its RPL packed H values per step (three or four store instructions;
-//     picking the one row out of the registers would cost RPL selects per step); the trace kernels read row (nrow - 1) % RPL of it
+//     picking the one row out of the registers would cost RPL selects per step); the trace kernel reads row (nrow - 1) % RPL of it
 //   * H(i, ncol): every lane stores its RPL packed H values when it passes the pair's last column (the other pair may sweep on)
 //   * every class of a batch runs in ONE launch (a wave-uniform switch over RPL; classes are padded to whole wavefronts with filler
 //     jobs): 20 000 pairs are 5 000 wavefronts -- per-class launches of a few hundred wavefronts each would leave the device idle.
@@ -359,17 +350,16 @@ __global__ __launch_bounds__(64) void k_sw_fill16(const SwJob* __restrict__ jobs
 #undef MGX_SW16_CASE
 }
 
-// what the trace kernels read of a pair's back-trace, whichever kernel filled it: the byte of the 32-bit form (op | INSERT_EXT | DELETE_EXT)
+// what the trace kernel reads of a pair's back-trace, whichever kernel filled it: the byte of the 32-bit form (op | INSERT_EXT | DELETE_EXT)
 struct BtView {
-    const u8* p; int rpl, g, slot; bool tr, i16; int half;
-    __device__ BtView(const SwJob& J, const u8* bt) : p(bt + J.bt_off), rpl((int)J.rpl), g((int)(J.g & 0xFFu)), tr((J.g & kJobTr) != 0),
+    const u8* p; int rpl, g, slot; bool i16; int half;
+    __device__ BtView(const SwJob& J, const u8* bt) : p(bt + J.bt_off), rpl((int)J.rpl), g((int)(J.g & 0xFFu)),
                                                      i16((J.g & kJobI16) != 0), half((J.g & kJobHalf) ? 1 : 0) {
         slot = i16 ? bt_slot16(rpl) : bt_slot(rpl);
     }
     __device__ int cell(int i, int j) const {
-        const int o = tr ? j : i, w = tr ? i : j;                      // position among the lanes | swept position
-        const int l = (o - 1) / rpl, k = (o - 1) - l * rpl;
-        const size_t base = ((size_t)(w + l) * g + l) * slot;
+        const int l = (i - 1) / rpl, k = (i - 1) - l * rpl;          // the lane that owns row i and its row in the lane
+        const size_t base = ((size_t)(j + l) * g + l) * slot;
         if (!i16) return p[base + k];
         const int by = p[base + (k >> 2) * 4 + half * 2 + ((k & 3) >> 1)];
         const int nib = (k & 1) ? by >> 4 : by & 15;
@@ -395,79 +385,9 @@ struct LastCol {
     __device__ int operator[](int i) const { return p16 ? (int)(int16_t)(p16[i - 1] >> half) : p32[i]; }
 };
 
-// One lane per pair: best end cell, back-trace, merged element list (in the order getCIGAR holds it).
-__global__ __launch_bounds__(64) void k_sw_trace(const SwJob* __restrict__ jobs, u32 n, const u8* __restrict__ bt,
-                                                 const int32_t* __restrict__ sc, int16_t* __restrict__ elems_all, SwResult* __restrict__ res,
-                                                 int16_t* __restrict__ compact, int n_compact) {
-    const u32 p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= n) return;
-    const SwJob J = jobs[p];
-    if (J.out_index == kNoOutput) return;
-    const int nrow = (int)J.len1, ncol = (int)J.len2, strategy = (int)J.strategy;
-    const LastRow last_row(J, bt, sc);
-    const LastCol last_col(J, bt, sc);
-    const BtView view(J, bt);
-    int16_t* el = elems_all + J.el_off;
-    // PairWiseSW.h:256-285, in anti-diagonal order
-    int best = INT32_MIN, mi = 0, mj = 0;
-    for (int d = 1; d <= nrow + ncol; ++d) {
-        if (d >= nrow + 1 && (strategy == MGX_SW_SOFTCLIP || strategy == MGX_SW_IGNORE)) {
-            const int j = d - nrow;
-            const int s = last_row[j];
-            if (best < s || (best == s && abs(nrow - j) < abs(mi - mj))) { best = s; mi = nrow; mj = j; }
-        }
-        if (d >= ncol + 1) {
-            const int i = d - ncol;
-            const int s = last_col[i];
-            if (best < s || (best == s && (mj == ncol || abs(i - ncol) <= abs(mi - mj)))) { best = s; mi = i; mj = ncol; }
-        }
-    }
-    // PairWiseSW.h:299-408
-    int i, j, m = 0;
-    if (strategy == MGX_SW_INDEL) { i = nrow; j = ncol; }
-    else if (strategy == MGX_SW_LEADING_INDEL) { i = mi; j = ncol; }
-    else { i = mi; j = mj; }
-    if (j < ncol) { el[0] = MGX_SW_SOFTCLIP; el[1] = (int16_t)(ncol - j); m = 1; }
-    int state = 0;
-    while (i > 0 && j > 0) {
-        const int btr = view.cell(i, j);
-        if (state == kInsertExt) { --j; el[2 * m - 1]++; state = btr & kInsertExt; }
-        else if (state == kDeleteExt) { --i; el[2 * m - 1]++; state = btr & kDeleteExt; }
-        else {
-            const int op = btr & 3;
-            if (op == kOpMatch) { --i; --j; el[2 * m] = kOpMatch; el[2 * m + 1] = 1; state = 0; ++m; }
-            else if (op == kOpInsert) { --j; el[2 * m] = kOpInsert; el[2 * m + 1] = 1; state = btr & kInsertExt; ++m; }
-            else { --i; el[2 * m] = kOpDelete; el[2 * m + 1] = 1; state = btr & kDeleteExt; ++m; }
-        }
-    }
-    int offset;
-    if (strategy == MGX_SW_SOFTCLIP) {
-        if (j > 0) { el[2 * m] = MGX_SW_SOFTCLIP; el[2 * m + 1] = (int16_t)j; ++m; }
-        offset = i;
-    } else if (strategy == MGX_SW_IGNORE) {
-        if (j > 0) { el[2 * m] = el[2 * (m - 1)]; el[2 * m + 1] = (int16_t)j; ++m; }
-        offset = (int16_t)(i - j);
-    } else {
-        if (i > 0) { el[2 * m] = kOpDelete; el[2 * m + 1] = (int16_t)i; ++m; }
-        else if (j > 0) { el[2 * m] = kOpInsert; el[2 * m + 1] = (int16_t)j; ++m; }
-        offset = 0;
-    }
-    int w = 0;
-    int16_t prev = el[0];
-    for (int q = 1; q < m; ++q) {
-        const int16_t cur = el[2 * q];
-        if (cur == prev) el[2 * w + 1] = (int16_t)(el[2 * w + 1] + el[2 * q + 1]);
-        else { ++w; el[2 * w] = cur; el[2 * w + 1] = el[2 * q + 1]; prev = cur; }
-    }
-    SwResult r; r.score = best; r.max_i = mi; r.max_j = mj; r.offset = offset; r.n_elems = w + 1;
-    res[J.out_index] = r;
-    // alignments have a handful of elements: those travel back in a fixed-size record per pair
-    int16_t* ce = compact + (size_t)J.out_index * 2 * n_compact;
-    for (int q = 0; q <= w && q < n_compact; ++q) { ce[2 * q] = el[2 * q]; ce[2 * q + 1] = el[2 * q + 1]; }
-}
-
-// The same with one WAVEFRONT per pair.  A lane per pair walks ~275 dependent byte loads of ~2 us each with a third of
-// a wavefront per SIMD to hide them behind; here the 64 lanes fetch the next 64 cells of the current DIAGONAL in one
+// One WAVEFRONT per pair: best end cell, back-trace, merged element list (in the order getCIGAR holds it).  A lane per
+// pair walks ~275 dependent byte loads of ~2 us each with a third of a wavefront per SIMD to hide them
+// behind; here the 64 lanes fetch the next 64 cells of the current DIAGONAL in one
 // gather (lane t: cell (i - t, j - t)) and the walk consumes them from registers, so an alignment of a few hundred
 // matches with a handful of gaps costs a handful of memory round trips.  Inside a gap (extension states) cells are
 // loaded one at a time as before.  The walk itself is wave-uniform; elements are merged on the fly (run-length form,
@@ -620,34 +540,29 @@ __global__ __launch_bounds__(256) void k_sw_gather(const GatherRef* __restrict__
     }
 }
 
-// lanes per pair, positions per lane, and which sequence the lanes own
-struct Shape { int g, rpl; bool tr; };
-// The lanes own the SHORTER sequence (round 3: the read, in the realignment workload) and sweep the longer one: fewer padding
-// positions and fewer fill/drain steps per useful step (k_sw_fill<.., TR>).  Up to 256 owned positions two pairs share a
-// wavefront (32 lanes x 1..8) whenever the batch is large enough to fill the device that way; otherwise, and beyond, one pair
-// per wavefront (64 lanes x 1..32) so that every SIMD still has several wavefronts to hide the dependent integer chain of a
-// step behind.  MGX_SW_TRANSPOSE=0 keeps the lanes on the reference (round 2's shapes; A/B and tests).
-Shape shape_for(int len1, int len2, bool paired, bool transpose) {
-    const bool tr = transpose && len2 < len1;
-    const int n_own = tr ? len2 : len1;
+// lanes per pair and reference positions per lane
+struct Shape { int g, rpl; };
+// The lanes own the reference and sweep the alternate.  Up to 256 reference positions two pairs share a wavefront
+// (32 lanes x 1..8) whenever the batch is large enough to fill the device that way; otherwise, and beyond, one pair per
+// wavefront (64 lanes x 1..32) so that every SIMD still has several wavefronts to hide the dependent integer chain of a
+// step behind.
+Shape shape_for(int len1, bool paired) {
     if (paired) {
         static const int cls32[] = {1, 2, 3, 4, 5, 6, 7, 8, 12, 16};
-        for (int r : cls32) if (n_own <= 32 * r) return Shape{32, r, tr};
+        for (int r : cls32) if (len1 <= 32 * r) return Shape{32, r};
     }
     static const int cls64[] = {1, 2, 3, 4, 5, 6, 8, 16, 32};
-    for (int r : cls64) if (n_own <= 64 * r) return Shape{64, r, tr};
-    return Shape{0, 0, false};
+    for (int r : cls64) if (len1 <= 64 * r) return Shape{64, r};
+    return Shape{0, 0};
 }
 // knobs of one call, read from the environment once (tests and A/B runs set them between calls)
 struct Knobs {
     int paired = -1;          // MGX_SW_PAIRED: force two lane groups per wavefront (1) or one (0)
     bool use16 = true;        // MGX_SW_I16=0: the 32-bit fill for every pair
-    bool transpose = false;   // MGX_SW_TRANSPOSE=1: 32-bit fill with the lanes over the shorter sequence
     u64 arena = 0;            // MGX_SW_ARENA_LIMIT
     Knobs() {
         if (const char* e = getenv("MGX_SW_PAIRED")) paired = atoi(e) != 0;
         if (const char* e = getenv("MGX_SW_I16")) use16 = atoi(e) != 0;
-        if (const char* e = getenv("MGX_SW_TRANSPOSE")) transpose = atoi(e) != 0;
         if (const char* e = getenv("MGX_SW_ARENA_LIMIT")) { const long long v = atoll(e); if (v > 0) arena = (u64)v; }
     }
 };
@@ -656,9 +571,9 @@ constexpr u32 kPairedFrom = 8192;             // pairs in a chunk from which two
 // ---- the packed 16-bit fill (k_sw_fill16): shapes and admission
 Shape shape16_for(int len1, bool paired) {
     static const int cls[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 20, 24, 32};
-    if (paired) for (int r : cls) if (len1 <= 32 * r) return Shape{32, r, false};
-    for (int r : cls) if (len1 <= 64 * r) return Shape{64, r, false};
-    return Shape{0, 0, false};
+    if (paired) for (int r : cls) if (len1 <= 32 * r) return Shape{32, r};
+    for (int r : cls) if (len1 <= 64 * r) return Shape{64, r};
+    return Shape{0, 0};
 }
 // Every value k_sw_fill16 computes for a cell of the pair's own matrix, and every difference of two of them, must fit 16 bits.
 //   H(i, j) >= the all-diagonal path from the boundary: blo + min(len) * min(match, mismatch, 0)
@@ -693,8 +608,7 @@ inline u64 bt_bytes16(u64 steps_max, const Shape& sh) { return ((steps_max + 1) 
 inline u64 lr_bytes16(u64 n_swp, const Shape& sh) { return ((n_swp + 1) * sh.rpl * 4 + 15) & ~15ull; }
 constexpr int kCompactElems = 16;             // merged CIGAR elements copied back per pair without a second look
 inline u64 bt_bytes(u64 len1, u64 len2, const Shape& sh) {
-    const u64 n_own = sh.tr ? len2 : len1, n_swp = sh.tr ? len1 : len2;
-    const u64 n_lanes = (n_own + sh.rpl - 1) / sh.rpl, steps = n_swp + n_lanes - 1;
+    const u64 n_lanes = (len1 + sh.rpl - 1) / sh.rpl, steps = len2 + n_lanes - 1;
     return ((steps + 1) * sh.g * bt_slot(sh.rpl) + 15) & ~15ull;
 }
 
@@ -759,13 +673,11 @@ namespace {
 constexpr u64 kArenaLimit = 4ull << 30;
 
 template <int G, int RPL>
-void launch_fill(mgx_sw* c, const SwJob* jobs, u32 n, u32 max_swept, bool tr, SwParams P) {
+void launch_fill(mgx_sw* c, const SwJob* jobs, u32 n, u32 max_swept, SwParams P) {
     constexpr u32 GPW = 64 / G;
     const u32 stride = (max_swept + 15) & ~15u;
-    if (tr) hipLaunchKernelGGL((k_sw_fill<G, RPL, true>), dim3((n + GPW - 1) / GPW), dim3(64), GPW * stride, c->stream, jobs, n, c->d_s1.p, c->d_s2.p,
-                               c->d_bt.p, c->d_sc.p, stride, P);
-    else    hipLaunchKernelGGL((k_sw_fill<G, RPL, false>), dim3((n + GPW - 1) / GPW), dim3(64), GPW * stride, c->stream, jobs, n, c->d_s1.p, c->d_s2.p,
-                               c->d_bt.p, c->d_sc.p, stride, P);
+    hipLaunchKernelGGL((k_sw_fill<G, RPL>), dim3((n + GPW - 1) / GPW), dim3(64), GPW * stride, c->stream, jobs, n, c->d_s1.p, c->d_s2.p,
+                       c->d_bt.p, c->d_sc.p, stride, P);
 }
 
 // pairs [lo, hi) of the input, already validated
@@ -825,9 +737,9 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
             J.cls = (uint16_t)((sh.g == 64 ? 64 : 0) + (32 - sh.rpl));                                  // < 128
             c->stats.n_pairs_i16++;
         } else {
-            const Shape sh = shape_for((int)J.len1, (int)J.len2, paired, knobs.transpose);
+            const Shape sh = shape_for((int)J.len1, paired);
             J.rpl = (uint8_t)sh.rpl; J.g = (uint8_t)sh.g;
-            J.cls = (uint16_t)(128 + (sh.g == 64 ? 64 : 0) + (sh.tr ? 128 : 0) + sh.rpl);               // < 384
+            J.cls = (uint16_t)(128 + (sh.g == 64 ? 64 : 0) + sh.rpl);                                   // < 256
         }
     }
     std::vector<u32> order(n);
@@ -836,9 +748,9 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         for (u32 q = 0; q < n; ++q) cnt[32767 - pre[q].len2 + 1]++;
         for (u32 k = 0; k < 32768; ++k) cnt[k + 1] += cnt[k];
         for (u32 q = 0; q < n; ++q) tmp[cnt[32767 - pre[q].len2]++] = q;
-        u32 c2[385] = {0};
+        u32 c2[257] = {0};
         for (u32 q = 0; q < n; ++q) c2[pre[q].cls + 1]++;
-        for (int k = 0; k < 384; ++k) c2[k + 1] += c2[k];
+        for (int k = 0; k < 256; ++k) c2[k + 1] += c2[k];
         for (u32 x = 0; x < n; ++x) order[c2[pre[tmp[x]].cls]++] = tmp[x];
     }
     SwJob* const jobs = reinterpret_cast<SwJob*>(pin + a1 + a2);             // built in place, in launch order
@@ -851,7 +763,7 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         J.len1 = R.len1; J.len2 = R.len2; J.rpl = R.rpl; J.strategy = in->strategy[p]; J.out_index = q;
         J.sc_off = J.off1 + J.off2 + 2ull * q; J.el_off = 2 * J.sc_off;
         J.low16 = R.low16;
-        J.g = (u32)R.g | (R.cls < 128 ? kJobI16 : (R.cls >= 256 ? kJobTr : 0u));
+        J.g = (u32)R.g | (R.cls < 128 ? kJobI16 : 0u);
         return J;
     };
     u64 bt = 0;
@@ -860,7 +772,7 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         if (pre[q0].cls < 128) {
             // one class: lane groups of two pairs, whole wavefronts
             const u32 cl = pre[q0].cls;
-            const Shape sh{(int)pre[q0].g, (int)pre[q0].rpl, false};
+            const Shape sh{(int)pre[q0].g, (int)pre[q0].rpl};
             const u32 per_wave = 2 * (64 / sh.g);
             u32 y = x;
             while (y < n && pre[order[y]].cls == cl) ++y;
@@ -889,7 +801,7 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
             x = y;
         } else {
             SwJob J = make_job(q0);
-            const Shape sh{(int)(J.g & 0xFFu), (int)J.rpl, (J.g & kJobTr) != 0};
+            const Shape sh{(int)(J.g & 0xFFu), (int)J.rpl};
             J.bt_off = bt; bt += bt_bytes(J.len1, J.len2, sh);
             jobs[n_jobs++] = J;
             ++x;
@@ -929,20 +841,19 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
             a = b;
             continue;
         }
-        const bool tr = (jobs[a].g & kJobTr) != 0;
-        while (b < n_jobs && jobs[b].rpl == jobs[a].rpl && jobs[b].g == jobs[a].g) { m2 = std::max(m2, tr ? jobs[b].len1 : jobs[b].len2); ++b; }
-#define MGX_SW_CASE(g, r) case r: launch_fill<g, r>(c, dj, b - a, m2, tr, P); break;
+        while (b < n_jobs && jobs[b].rpl == jobs[a].rpl && jobs[b].g == jobs[a].g) { m2 = std::max(m2, jobs[b].len2); ++b; }
+#define MGX_SW_CASE(g, r) case r: launch_fill<g, r>(c, dj, b - a, m2, P); break;
         if ((jobs[a].g & 0xFFu) == 32) {
             switch (jobs[a].rpl) {
                 MGX_SW_CASE(32, 1) MGX_SW_CASE(32, 2) MGX_SW_CASE(32, 3) MGX_SW_CASE(32, 4) MGX_SW_CASE(32, 5) MGX_SW_CASE(32, 6) MGX_SW_CASE(32, 7)
                 MGX_SW_CASE(32, 8) MGX_SW_CASE(32, 12)
-                default: launch_fill<32, 16>(c, dj, b - a, m2, tr, P); break;
+                default: launch_fill<32, 16>(c, dj, b - a, m2, P); break;
             }
         } else {
             switch (jobs[a].rpl) {
                 MGX_SW_CASE(64, 1) MGX_SW_CASE(64, 2) MGX_SW_CASE(64, 3) MGX_SW_CASE(64, 4) MGX_SW_CASE(64, 5) MGX_SW_CASE(64, 6) MGX_SW_CASE(64, 8)
                 MGX_SW_CASE(64, 16)
-                default: launch_fill<64, 32>(c, dj, b - a, m2, tr, P); break;
+                default: launch_fill<64, 32>(c, dj, b - a, m2, P); break;
             }
         }
 #undef MGX_SW_CASE
@@ -950,13 +861,8 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         a = b;
     }
     HIP_TRY(hipEventRecord(c->ev[1], s));
-    static const bool lane_trace = [] { const char* e = getenv("MGX_SW_TRACE"); return e && !strcmp(e, "lane"); }();   // A/B: one lane per pair
-    if (lane_trace)
-        hipLaunchKernelGGL(k_sw_trace, dim3((n_jobs + 63) / 64), dim3(64), 0, s, c->d_jobs.p, n_jobs, c->d_bt.p, c->d_sc.p, c->d_el.p, c->d_res.p,
-                           c->d_cel.p, kCompactElems);
-    else
-        hipLaunchKernelGGL(k_sw_trace_wave, dim3(n_jobs), dim3(64), 0, s, c->d_jobs.p, n_jobs, c->d_bt.p, c->d_sc.p, c->d_el.p, c->d_res.p,
-                           c->d_cel.p, kCompactElems);
+    hipLaunchKernelGGL(k_sw_trace_wave, dim3(n_jobs), dim3(64), 0, s, c->d_jobs.p, n_jobs, c->d_bt.p, c->d_sc.p, c->d_el.p, c->d_res.p,
+                       c->d_cel.p, kCompactElems);
     HIP_TRY(hipEventRecord(c->ev[2], s));
     HIP_TRY(hipGetLastError());
     tp[3] = now();
@@ -1108,8 +1014,7 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
             // (the paired form and the 16-bit form are smaller) plus the 16-bit kernel's edge rows
             const u64 l1 = in->ref_off[hi + 1] - in->ref_off[hi], l2 = in->alt_off[hi + 1] - in->alt_off[hi];
             const u64 rows = (l1 + 63) / 64, slot = rows <= 8 ? ((rows + 3) & ~3ull) : rows <= 16 ? 16 : 32;
-            const u64 swept = knobs.transpose ? std::max(l1, l2) : l2;
-            const u64 need = (swept + 64 + 1) * 64 * slot + 8 * (l2 + 1) * ((l1 + 31) / 32 * 3 / 2 + 2) + 8 * (l1 + 64) + 64;
+            const u64 need = (l2 + 64 + 1) * 64 * slot + 8 * (l2 + 1) * ((l1 + 31) / 32 * 3 / 2 + 2) + 8 * (l1 + 64) + 64;
             if (hi > lo && bt + need > limit) break;
             bt += need; ++hi;
         }

@@ -573,293 +573,6 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Packed fp32 (round 3): the same recurrence with two rows of a lane in every VALU instruction
-// (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  On gfx950 a packed instruction costs about 3.0-3.3 SIMD cycles
-// against 2.0-2.1 for the scalar one (tools/pk_microbench.hip, profiles/r03_pk_microbench.txt): 1.3x per cell IF
-// nothing has to be moved into place.  Layout that needs no moves:
-//   * a lane's RPL = 2P rows are two HALF-LANES of P consecutive rows; register pair k holds row k of the low half
-//     in .x and row k of the high half (row P + k of the lane) in .y;
-//   * the high half runs ONE COLUMN BEHIND the low half: half-lane q = 2j + half processes column d - q at step d.
-//     Then "the row above" of pair k is pair k - 1 for BOTH components (previous column for M's diagonal input,
-//     same column for the X chain), i.e. an aligned register pair; the only exceptions are pair 0, whose row above
-//     is (the next lane up, through DPP as before | row P - 1 of this lane's own low half, one v_mov), kept in two
-//     alternating boundary sets exactly like the shifted-in values of the scalar kernel;
-//   * the X chain down the rows of a column (X^[r] needs M[r-1], X^[r-1] of the same column) becomes two
-//     interleaved chains of P packed operations instead of one of 2P scalar ones;
-//   * the emissions of a pair belong to two haplotype columns (c and c - 1): the LDS table is laid out
-//     [half][k][code][lane] and read with two ds_read_b32 per pair, the high half through the address of the
-//     previous step (no address arithmetic of its own).
-// A group of G lanes is 2G half-lanes, so fill/drain costs nh - 1 steps for nh = ceil(R / P) half-lanes in use
-// (up to 2G - 1 instead of G - 1).  Every cell is computed by the same operations in the same order as in
-// pairhmm_body, so the results are bit-identical to the scalar kernel's (tests/test_pairhmm_gpu.py).
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
-constexpr int kPkCodes = 4;                                    // A C T G: a haplotype with an 'N' is left to the fp64 kernel
-constexpr int kPkRowStride = kPkCodes * 64 * 4 + 4;            // bytes between row k and k + 1 of a half's table: 1024 + 4, and
-                                                               // P * 1028 between the halves: no two reads of a step are a
-                                                               // multiple of 256 bytes or less than 1024 bytes apart, so none
-                                                               // can be merged into a ds_read2 / ds_read2st64 (which would put
-                                                               // values of two different pairs into one register pair)
-template <int P> constexpr int etab_pk_bytes_per_wave() { return (2 * P * kPkRowStride + 15) & ~15; }
-
-template <int G, int P>
-__device__ __forceinline__ void pairhmm_body_pk(const KernelArgs& a, uint8_t* smem, const uint32_t block, const uint32_t n_blocks) {
-    typedef float T;
-    constexpr int RPL = 2 * P;
-    constexpr int GPW = 64 / G;
-    constexpr int S = lane_stride<G>();
-    constexpr int PAD = 2 * G;                    // haplotype codes: [0, PAD) pad | [PAD, PAD + H) codes | pad
-    const int gpb = (int)blockDim.x / G;
-    const int tid = (int)threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int j = G < 16 ? (lane & 15) / S : lane % G;
-    const int grp = wave * GPW + (G < 16 ? (lane >> 4) * S + (lane & 15) % S : lane / G);
-    const int n_waves = (int)blockDim.x >> 6;
-    uint8_t* etab = smem + (size_t)wave * etab_pk_bytes_per_wave<P>();
-    uint8_t* hapbuf = smem + (size_t)n_waves * etab_pk_bytes_per_wave<P>() + (size_t)grp * a.lds_stride;
-    const T* __restrict__ ph2pr = (const T*)a.ph2pr;
-    const T* __restrict__ mm = (const T*)a.mm;
-    const T* __restrict__ ph2pr_div3 = (const T*)a.ph2pr_div3;
-    const T* __restrict__ gap_ratio = (const T*)a.gap_ratio;
-    const uint32_t n_jobs = a.n_dyn ? *a.n_dyn : a.n_static;
-
-    for (uint32_t base = block * (uint32_t)gpb; base < n_jobs; base += n_blocks * (uint32_t)gpb) {
-        const uint32_t slot = base + (uint32_t)grp;
-        const bool live = slot < n_jobs;
-        uint32_t job_idx = 0;
-        Job job;
-        job.read_off = 0; job.hap_off = 0; job.R = 0; job.H = 0; job.pair = 0; job.pad_ = 0;
-        if (live) {
-            job_idx = a.job_list ? a.job_list[slot] : a.job_first + slot;
-            job = a.jobs[job_idx];
-        }
-        const int R = (int)job.R, H = (int)job.H;
-
-        // ---- haplotype codes into LDS (stride >= max H of the bin + 4G + 8).  The emission table below holds the four
-        //      codes A C T G only (8 KB instead of 10 KB per wavefront: 16 instead of 13 workgroups per CU, and the packed
-        //      instructions need the wavefronts: tools/pk_microbench.hip); pad columns read as 'A' (their values never
-        //      reach a counted cell) and a test case whose haplotype holds an 'N' goes to the double-precision list.
-        __syncthreads();
-        bool to_f64 = false;                              // this test case is left to the fp64 kernel
-        {
-            const uint8_t* hp = a.hap_bases + job.hap_off;
-            const int n_words = (int)a.lds_stride >> 2;
-            uint32_t* hb32 = reinterpret_cast<uint32_t*>(hapbuf);
-            for (int w = j; w < n_words; w += G) {
-                const int c0 = 4 * w - PAD;
-                uint32_t packed;
-                if (live && c0 >= 0 && c0 + 4 <= H) {
-                    uint32_t raw;
-                    __builtin_memcpy(&raw, hp + c0, 4);
-                    packed = base_code4(raw);
-                } else {
-                    packed = 0;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const int c = c0 + t;
-                        const int code = (live && c >= 0 && c < H) ? base_code(hp[c]) : 0;
-                        packed |= (uint32_t)code << (8 * t);
-                    }
-                }
-                const uint32_t x = packed ^ (0x01010101u * (uint32_t)kCodeN);      // a zero byte where the code is N
-                to_f64 |= ((x - 0x01010101u) & ~x & 0x80808080u) != 0;
-                hb32[w] = packed & 0x03030303u;
-            }
-        }
-
-        const int nh = (R + P - 1) / P;                   // half-lanes in use
-        const int top_clones = nh * P - R;                // spare rows at the top of half-lane 0 (< P)
-        const int qf = nh - 1;                            // the half-lane whose bottom row is read row R
-        const T init_y = Prec<T>::initial() / (T)(H > 0 ? H : 1);
-
-        // ---- per-row constants in two passes, so that few values are live at a time (the 128 registers of 4 wavefronts
-        //      per SIMD are all spoken for by the sweep).  Slot t = half * P + k of the lane holds read row
-        //      j * RPL + t - top_clones; register pair k = (slot k, slot P + k).
-        //      Pass 1: pGAPM of every row (0 for clones and unused slots) -> g' = pGAPM of the row below, and pMY of every
-        //      row (1 for clones: pMY_0 := 1) -> pMY' = pMY of the row above.
-        T g_own[RPL], my_own[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) {
-            const int rho = j * RPL + t - top_clones;
-            const int q = 2 * j + (t >= P ? 1 : 0);
-            g_own[t] = 0;
-            my_own[t] = 0;
-            if (live && q < nh && rho >= 0) {
-                const int qc = a.gcp[job.read_off + (uint64_t)rho] & 127;
-                g_own[t] = (T)1.0 - ph2pr[qc];
-                my_own[t] = ph2pr[a.del[job.read_off + (uint64_t)rho] & 127];
-                to_f64 |= (qc == 0);                      // pGAPM == 0: the cell divides by it (see below)
-            } else if (live && q < nh) {
-                my_own[t] = 1;
-            }
-        }
-        const T g_next_lane = shr1_down<G>(g_own[0]);
-        const T my_prev_lane = shr1<G>((T)1.0, my_own[RPL - 1]);     // lane j - 1's bottom row; the boundary row for lane 0
-        //      Pass 2: the coefficients of pairhmm_body's 6-operation cell and the emission table, row by row.
-        f2 K0[P], K1[P], K2[P], K3[P], K4[P], pm[P], px[P], py[P];
-        {
-            float* et = reinterpret_cast<float*>(etab) + lane;
-#pragma unroll
-            for (int t = 0; t < RPL; ++t) {
-                const int rho = j * RPL + t - top_clones;
-                const int q = 2 * j + (t >= P ? 1 : 0);
-                T gb = (t + 1 < RPL) ? g_own[t + 1] : g_next_lane;
-                if (j == (qf >> 1) && t == ((qf & 1) ? RPL - 1 : P - 1)) gb = (T)1.0;      // read row R: unscaled
-                T c0 = 0, cA = 0, cB = 0, cC = 0, cD = 0, y0 = 0, eM = 0, eX = 0;
-                int rb = 0;
-                if (live && q < nh) {
-                    if (rho < 0) {                        // a clone of row 0: y = INITIAL / H for ever (D = 1)
-                        cD = 1; y0 = init_y;
-                    } else {
-                        const uint64_t o = job.read_off + (uint64_t)rho;
-                        const int qi = a.ins[o] & 127, qd = a.del[o] & 127, qc = a.gcp[o] & 127;
-                        const int qq = a.qual[o] & 127;
-                        const int mn = qi <= qd ? qi : qd, mx = qi <= qd ? qd : qi;
-                        c0 = mm[((mx * (mx + 1)) >> 1) + mn];
-                        cA = gb * ph2pr[qi];              // A = g' * pMX
-                        cB = gb * gap_ratio[qc];          // B = g' * pXX / g
-                        cC = g_own[t] * (t > 0 ? my_own[t - 1] : my_prev_lane);     // q = g * pMY'
-                        cD = ph2pr[qc];                   // D = pYY
-                        eM = (T)1.0 - ph2pr[qq];
-                        rb = base_code(a.bases[o]);
-                        eX = (rb == kCodeN) ? eM : ph2pr_div3[qq];
-                    }
-                }
-#pragma unroll
-                for (int code = 0; code < kPkCodes; ++code)
-                    et[t * (kPkRowStride / 4) + code * 64] = (code == rb) ? eM : eX;        // t = half * P + k
-                const int k = t % P;
-                if (t < P) { K0[k].x = c0; K1[k].x = cA; K2[k].x = cB; K3[k].x = cC; K4[k].x = cD; py[k].x = y0; }
-                else       { K0[k].y = c0; K1[k].y = cA; K2[k].y = cB; K3[k].y = cC; K4[k].y = cD; py[k].y = y0; }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < P; ++k) { pm[k] = f2{0, 0}; px[k] = f2{0, 0}; }
-        const T y_above = init_y;
-        const T py_mid = py[P - 1].x;
-        __syncthreads();
-
-        const int nsteps_g = live ? (H + nh - 1) : 0;
-        int nmax = nsteps_g, nmin = live ? nsteps_g : 0x7fffffff;
-        if constexpr (GPW > 1) {
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                if (off >= S && off < (G < 16 ? 16 : G)) continue;
-                const int o1 = __shfl_xor(nmax, off, 64), o2 = __shfl_xor(nmin, off, 64);
-                nmax = o1 > nmax ? o1 : nmax;
-                nmin = o2 < nmin ? o2 : nmin;
-            }
-        }
-        nmax = __builtin_amdgcn_readfirstlane(nmax);
-        nmin = __builtin_amdgcn_readfirstlane(nmin);
-        if (nmin > nmax) nmin = nmax;
-
-        const uint8_t* hp_lane = hapbuf + (PAD - 2 * j);       // hp_lane[d] = code of the LOW half's column at step d
-        const uint8_t* et_lane = etab + lane * 4;
-        // A test case with a gap-continuation byte of 0 (pGAPM == 0) cannot take the 6-operation form (B divides by pGAPM) and
-        // this kernel carries no plain form (its second copy of the sweep costs 22 registers: 3 instead of 4 wavefronts
-        // per SIMD): such a test case goes to the double-precision list, whose kernel has both forms.  The decision is
-        // per test case (its group's lanes), never per wavefront, so a value does not depend on the batch it is in.
-        uint64_t gmask;                                        // the lanes of this lane's group
-        if constexpr (G == 64) gmask = ~0ull;
-        else if constexpr (G == 16) gmask = 0xFFFFull << (lane & 48);
-        else gmask = (uint64_t)((G == 8 ? 0x5555u : 0x1111u) << ((lane & 15) % S)) << (lane & 48);
-        const bool group_to_f64 = (__ballot((int)to_f64) & gmask) != 0;
-
-        f2 sumM = {0, 0}, sumX = {0, 0};
-
-        {
-            const T old_y = (j == 0) ? y_above : (T)0;
-            // two boundary sets: .x shifted in from the lane above (lane 0 of the group keeps (0, 0, y_above) through the
-            // DPP `old` operand), .y = row P - 1 of this lane's low half as it was one / two steps ago
-            f2 uaM = {0, 0}, uaX = {0, 0}, uaY = {old_y, py_mid}, ubM = {0, 0}, ubX = {0, 0}, ubY = {old_y, py_mid};
-
-            auto column = [&](const f2 (&ec)[P], f2& o2M, f2& o2X, f2& o2Y, const f2 o1M, const f2 o1X, bool count) {
-                // the 6-operation cell of pairhmm_body, two rows per instruction
-                f2 Mn[P], Xn[P], Yn[P];
-                Mn[0] = pk_fma(K3[0], o2Y, pk_fma(o2M, K0[0], o2X)) * ec[0];
-                Xn[0] = pk_fma(o1X, K2[0], o1M * K1[0]);
-                Yn[0] = pk_fma(py[0], K4[0], pm[0]);
-#pragma unroll
-                for (int k = 1; k < P; ++k) {
-                    Mn[k] = pk_fma(K3[k], py[k - 1], pk_fma(pm[k - 1], K0[k], px[k - 1])) * ec[k];
-                    Xn[k] = pk_fma(Xn[k - 1], K2[k], Mn[k - 1] * K1[k]);
-                    Yn[k] = pk_fma(py[k], K4[k], pm[k]);
-                }
-#pragma unroll
-                for (int k = 0; k < P; ++k) { pm[k] = Mn[k]; px[k] = Xn[k]; py[k] = Yn[k]; }
-                if (count) { sumM += Mn[P - 1]; sumX += Xn[P - 1]; }
-                o2M.x = shr1<G>(o2M.x, Mn[P - 1].y); o2M.y = Mn[P - 1].x;
-                o2X.x = shr1<G>(o2X.x, Xn[P - 1].y); o2X.y = Xn[P - 1].x;
-                o2Y.x = shr1<G>(o2Y.x, Yn[P - 1].y); o2Y.y = Yn[P - 1].x;
-            };
-            // emissions of the step whose low-half code is h, the high half takes the previous step's code
-            auto load_e = [&](int h, int hprev, f2 (&dst)[P]) {
-                const uint8_t* pc = et_lane + (h << 8);
-                const uint8_t* pp = et_lane + (hprev << 8) + P * kPkRowStride;
-#pragma unroll
-                for (int k = 0; k < P; ++k) {
-                    dst[k].x = *reinterpret_cast<const float*>(pc + k * kPkRowStride);
-                    dst[k].y = *reinterpret_cast<const float*>(pp + k * kPkRowStride);
-                }
-            };
-
-            f2 e[P];
-            int d = 0;
-            int h0 = hp_lane[0], h1 = hp_lane[1];
-            load_e(h0, (int)hp_lane[-1], e);
-            // The scheduling barriers keep the LDS reads of a column one whole column of arithmetic ahead of their use: left
-            // alone, the scheduler sinks every read next to its consumer to shorten live ranges and the loop waits on LDS
-            // latency twice per iteration (measured: 6.5 ms against 5.4 ms for the scalar kernel on 1 M 128 x 256 test cases).
-            for (; d + 2 <= nmin; d += 2) {
-                f2 e1[P];
-                load_e(h1, h0, e1);
-                const int h2 = hp_lane[d + 2], h3 = hp_lane[d + 3];
-                __builtin_amdgcn_sched_barrier(0);
-                column(e, uaM, uaX, uaY, ubM, ubX, true);
-                __builtin_amdgcn_sched_barrier(0);
-                load_e(h2, h1, e);
-                __builtin_amdgcn_sched_barrier(0);
-                column(e1, ubM, ubX, ubY, uaM, uaX, true);
-                __builtin_amdgcn_sched_barrier(0);
-                h0 = h2; h1 = h3;
-            }
-            for (; d < nmax; ++d) {
-                const int hn = hp_lane[d + 1];
-                column(e, uaM, uaX, uaY, ubM, ubX, d < nsteps_g);
-                f2 t;
-                t = uaM; uaM = ubM; ubM = t;
-                t = uaX; uaX = ubX; ubX = t;
-                t = uaY; uaY = ubY; ubY = t;
-                load_e(hn, h0, e);
-                h0 = hn;
-            }
-        }
-
-        if (live && j == (qf >> 1)) {
-            const T res = (qf & 1) ? (sumM.y + sumX.y) : (sumM.x + sumX.x);
-            if (group_to_f64 || res < 1e-28f) {
-                const uint32_t k = atomicAdd(a.rerun_count, 1u);
-                a.rerun_list[k] = job_idx;
-            } else {
-                a.out_log10[job.pair] = (double)(log10f(res) - a.log10_initial_f);
-            }
-        }
-    }
-}
-
-#ifndef MGX_HMM_PK_MINWAVES
-#define MGX_HMM_PK_MINWAVES 4
-#endif
-template <int G, int P>
-__global__ __launch_bounds__(256, P == 4 ? MGX_HMM_PK_MINWAVES : 1) void pairhmm_fwd_pk(KernelArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    pairhmm_body_pk<G, P>(a, smem, blockIdx.x, gridDim.x);
-}
-
 // fp32 classes of up to 8 rows per lane fit the register budget of 4 wavefronts per SIMD (128 VGPRs) natively -- 8 rows
 // per lane at exactly 128 -- except 7 rows per lane (129 registers), which the bound brings to 128 at the cost of one or
 // two values parked in scratch outside the sweep.  The bound is applied to that class ONLY: on the 8-row classes it
@@ -1119,16 +832,6 @@ __global__ __launch_bounds__(256) void pairhmm_normalize_filter_rows(double* __r
 }
 
 using KernelFn = void (*)(KernelArgs);
-
-// the packed fp32 kernel of a class with an even number of rows per lane (P = RPL / 2 register pairs)
-inline KernelFn pick_kernel_pk(int G, int P) {
-#define MGX_CASE(g, p) if (G == g && P == p) return pairhmm_fwd_pk<g, p>;
-    MGX_CASE(4, 1) MGX_CASE(4, 2) MGX_CASE(4, 3) MGX_CASE(4, 4)
-    MGX_CASE(8, 1) MGX_CASE(8, 2) MGX_CASE(8, 3) MGX_CASE(8, 4)
-    MGX_CASE(16, 1) MGX_CASE(16, 2) MGX_CASE(16, 3) MGX_CASE(16, 4)
-#undef MGX_CASE
-    return nullptr;
-}
 
 template <typename T>
 KernelFn pick_kernel(int G, int RPL) {

@@ -50,10 +50,11 @@ typedef struct mgx_pairhmm_batch mgx_pairhmm_batch_t;
 /* flags for mgx_pairhmm_create */
 #define MGX_PAIRHMM_FORCE_DOUBLE 1u /* PairHMMNativeArgumentCollection.useDoublePrecision */
 #define MGX_PAIRHMM_TIMING       2u /* record HIP events around every kernel launch */
-#define MGX_PAIRHMM_PACKED_FP32  4u /* classes with an even number of rows per lane run pairhmm_fwd_pk (two rows per v_pk_*_f32
-                                     * instruction).  Bit-identical results; measured SLOWER than the default kernel on every
-                                     * shape (a packed instruction occupies the fp32 pipe as long as two scalar
-                                     * ones), so it is off unless asked for (or MGX_PAIRHMM_PK=1) */
+#define MGX_PAIRHMM_PACKED_FP32  4u /* accepted and ignored: the packed fp32 kernel it selected was slower than the default
+                                     * kernel on every shape and has been removed.  A context created with it
+                                     * runs the default kernels.  One visible difference: a test case whose gap-continuation
+                                     * byte is 0 used to go to the fp64 list under this flag; it now takes the default fp32
+                                     * kernel's plain form and returns the default path's result. */
 /* bits 8..15 (both mgx_pairhmm_create and mgx_sortdedup_create): optional CU partition, an 8-bit
  * pattern repeated over the CU index; 0 or 0xFF = all CUs.  MGX_CU_PATTERN(0x3F) keeps 6 CUs of 8. */
 #define MGX_CU_PATTERN(p) (((unsigned)(p) & 0xFFu) << 8)

@@ -163,10 +163,9 @@ def test_16_bit_fill_at_the_ends_of_its_range(sw_engine, sw_oracle):
         assert sw_engine.stats()["n_pairs_i16"] > 0
 
 
-def test_transposed_fill(sw_engine, sw_oracle, synth, monkeypatch):
-    """MGX_SW_TRANSPOSE=1 (opt-in: measured slower on the realignment shape): the 32-bit kernel with the lanes over the
-    alternate sequence whenever it is the shorter one"""
-    monkeypatch.setenv("MGX_SW_TRANSPOSE", "1")
+def test_32bit_fill_paired_and_unpaired(sw_engine, sw_oracle, synth, monkeypatch):
+    """the 32-bit kernel for every pair (MGX_SW_I16=0), with two pairs per wavefront and with one, on references both
+    longer and shorter than their alternates"""
     monkeypatch.setenv("MGX_SW_I16", "0")
     for paired in ("0", "1"):
         monkeypatch.setenv("MGX_SW_PAIRED", paired)

@@ -117,7 +117,6 @@ while time.time() - t0 < budget:
         else:
             os.environ["MGX_SW_PAIRED"] = str(rng.choice(["0", "1"]))
             os.environ["MGX_SW_I16"] = str(rng.choice(["0", "1", "1", "1"]))          # the packed 16-bit fill (round 3) or the 32-bit one for every pair
-            os.environ["MGX_SW_TRANSPOSE"] = str(rng.choice(["0", "0", "1"]))
             w = synth.gen_sw_pairs(int(rng.integers(1, 400)), seed, ref_range=(1, int(rng.choice([60, 300, 700, 2048]))), alt_range=(1, int(rng.choice([40, 200, 600]))))
             params = tuple(int(x) for x in rng.choice([[25, -50, -110, -6], [3, -1, -4, -3], [1, -2, -3, -1], [10, -15, -30, -5]]))
             if rng.integers(0, 3) == 0:         # anything: the 16-bit admission rule decides pair by pair
