@@ -1,5 +1,7 @@
-"""Host-side handle on the BGZF compressor's C ABI (include/mgx_bgzf.h).  The compression runs on the device only."""
+"""Host-side handle on the BGZF C ABI (include/mgx_bgzf.h): the compressor and the inflater run on the device only; the
+block scanner (scan_blocks) is host code."""
 import ctypes as C
+import errno
 
 import numpy as np
 
@@ -127,3 +129,112 @@ class BgzfStore:
         if self.h:
             self.lib.mgx_bgzf_store_destroy(self.h)
             self.h = None
+
+
+SCAN_END, SCAN_PARTIAL, SCAN_NOT_BGZF, SCAN_FULL = 0, 1, 2, 3
+
+
+def scan_blocks(data, max_blocks=None):
+    """mgx_bgzf_scan_blocks (host only): (block offsets [n + 1], ISIZEs [n], CRCs [n], stop reason)."""
+    lib = native.load()
+    data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    if max_blocks is None:
+        max_blocks = len(data) // 26 + 1
+    off = np.zeros(max_blocks + 1, dtype=np.uint64)
+    isize = np.zeros(max(max_blocks, 1), dtype=np.uint32)
+    crc = np.zeros(max(max_blocks, 1), dtype=np.uint32)
+    n, stop = C.c_uint64(), C.c_int()
+    native.check(lib.mgx_bgzf_scan_blocks(_ptr(data), len(data), max_blocks, _ptr(off), _ptr(isize), _ptr(crc), C.byref(n), C.byref(stop)))
+    k = int(n.value)
+    return off[:k + 1], isize[:k], crc[:k], int(stop.value)
+
+
+class BgzfInflater:
+    """The inflate side of mgx_bgzf_t: BGZF blocks -> their bytes, one wavefront per block on the device."""
+
+    def __init__(self, device=0):
+        self.lib = native.load()
+        h = C.c_void_p()
+        native.check(self.lib.mgx_bgzf_create(device, 0, C.byref(h)))
+        self.h = h
+
+    def decompress(self, data):
+        """Whole BGZF blocks (pageable memory, one shot) -> bytes."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        _, isize, _, _ = scan_blocks(data)
+        total = int(isize.sum(dtype=np.uint64))
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        n = C.c_uint64()
+        native.check(self.lib.mgx_bgzf_decompress(self.h, _ptr(data), len(data), _ptr(out), total, C.byref(n)))
+        return out[: int(n.value)].tobytes()
+
+    def batch(self, in_capacity, out_capacity, max_blocks):
+        return InflateBatch(self, in_capacity, out_capacity, max_blocks)
+
+    def stats(self):
+        st = native.BgzfInflateStats()
+        native.check(self.lib.mgx_bgzf_inflate_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in native.BgzfInflateStats._fields_}
+
+    def close(self):
+        if self.h:
+            self.lib.mgx_bgzf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class InflateBatch:
+    """mgx_bgzf_inflate_t: whole blocks into the pinned input (fill), submit, wait."""
+
+    def __init__(self, inf, in_capacity, out_capacity, max_blocks):
+        self.inf, self.lib = inf, inf.lib
+        b = C.c_void_p()
+        native.check(self.lib.mgx_bgzf_inflate_batch_create(inf.h, in_capacity, out_capacity, max_blocks, C.byref(b)))
+        self.b = b
+        self.in_capacity, self.out_capacity, self.max_blocks = in_capacity, out_capacity, max_blocks
+        self.input = np.ctypeslib.as_array(C.cast(self.lib.mgx_bgzf_inflate_batch_input(b), C.POINTER(C.c_uint8)), shape=(in_capacity,))
+        io, oo = C.c_void_p(), C.c_void_p()
+        native.check(self.lib.mgx_bgzf_inflate_batch_offsets(b, C.byref(io), C.byref(oo)))
+        self.in_off = np.ctypeslib.as_array(C.cast(io, C.POINTER(C.c_uint64)), shape=(max_blocks + 1,))
+        self.out_off = np.ctypeslib.as_array(C.cast(oo, C.POINTER(C.c_uint64)), shape=(max_blocks + 1,))
+        self.n_blocks = 0
+
+    def fill(self, blocks, isizes=None):
+        """blocks: whole BGZF members (bytes); the output sizes are their ISIZE fields unless given."""
+        at, out = 0, 0
+        self.in_off[0] = 0; self.out_off[0] = 0
+        for i, blk in enumerate(blocks):
+            self.input[at:at + len(blk)] = np.frombuffer(blk, dtype=np.uint8)
+            at += len(blk)
+            out += isizes[i] if isizes is not None else int.from_bytes(blk[-4:], "little") if len(blk) >= 4 else 0
+            self.in_off[i + 1] = at; self.out_off[i + 1] = out
+        return len(blocks)
+
+    def submit(self, n_blocks):
+        native.check(self.lib.mgx_bgzf_inflate_batch_submit(self.inf.h, self.b, n_blocks))
+        self.n_blocks = n_blocks
+
+    def wait(self):
+        """(bytes of every block back to back, status word per block, error message or None)."""
+        out, st = C.c_void_p(), C.c_void_p()
+        rc = self.lib.mgx_bgzf_inflate_batch_wait(self.inf.h, self.b, C.byref(out), C.byref(st))
+        err = None
+        if rc != 0:
+            if rc != -errno.EBADMSG:                             # bad blocks; anything else is a failure
+                native.check(rc)
+            err = self.lib.mgx_last_error().decode()
+        n = self.n_blocks
+        total = int(self.out_off[n])
+        data = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), shape=(max(total, 1),))[:total].tobytes()
+        status = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint32)), shape=(max(n, 1),))[:n].copy()
+        return data, status, err
+
+    def close(self):
+        if self.b:
+            self.lib.mgx_bgzf_inflate_batch_destroy(self.inf.h, self.b)
+            self.b = None

@@ -4,6 +4,9 @@
 //     sortmardup [-I input.sam] [-t threads] -O output.bam
 // text SAM from a file or stdin; output.bam is replaced if it exists; output.bam.bai is written
 // next to it; stage timings go to stdout (time_stamp(), main.cpp:597-607).
+// Input formats: plain SAM text; BGZF-compressed SAM (inflated on the device in batches, the text parsed in place from
+// the pinned buffers: GzSource); plain gzip, one member or several (zlib on the reader thread: serial).
+// The gzip magic in the first two bytes decides; BAM input is refused.
 //
 // Ingest is a pipeline over bounded slices of the text, the shape of the reference's reader thread feeding its
 // shuffle threads through a bounded queue of line blocks (main.cpp:505-562, 129-192):
@@ -28,6 +31,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <zlib.h>
 
 #include <atomic>
 #include <chrono>
@@ -61,7 +65,10 @@ void time_stamp(const char* hint) {
     g_last = now;
 }
 
-struct Slice { uint64_t seq = 0; std::string text; uint64_t file_off = 0; size_t file_len = 0; bool from_file = false; };   // owned text (stdin) or a range of the input file
+struct Slice {                       // owned text (stdin), a range of the input file, or text inside an inflated buffer
+    uint64_t seq = 0; std::string text; uint64_t file_off = 0; size_t file_len = 0; bool from_file = false;
+    const char* ext = nullptr; size_t ext_len = 0; std::shared_ptr<void> hold;      // compressed input: parsed in place
+};
 
 struct Chunk {                       // one parsed + packed slice
     std::vector<uint16_t> flag; std::vector<int32_t> tid; std::vector<int64_t> pos; std::vector<int32_t> end;
@@ -142,6 +149,256 @@ void parse_slice(const char* data, size_t size, const samtext::Header& h, uint64
     std::vector<uint64_t>().swap(c->cigar_off); std::vector<uint64_t>().swap(c->qname_off);
 }
 
+// ---- compressed input ------------------------------------------------------------------------------------------------
+// A piece of inflated text; `hold` keeps its buffer alive (a batch's pinned output: the slices cut from it are parsed in
+// place, and the buffer goes back to the source when the last of them is done).
+struct TextChunk { const char* data = nullptr; size_t size = 0; std::shared_ptr<void> hold; };
+
+// gzip / BGZF input -> inflated text, in order (htslib reads compressed SAM the same way: bgzf.c:1100-1180).
+//   BGZF: the block scanner finds whole blocks in what was read (straight into a batch's pinned input), a batch is inflated
+//         on the device (mgx_bgzf_inflate_*) and its text comes back into the batch's pinned output, which the
+//         parsers read in place.  kSlots batches, up to kDepth of them in flight; a batch is reused once the text cut from it
+//         has been parsed.  MGX_CLI_INFLATE=host inflates the same batches with zlib on a gang of `threads` host threads
+//         that the reader starts per batch, beside the parsers (A/B).  MGX_CLI_INFLATE_BATCH: compressed bytes per batch.
+//   gzip: from the first member that is not BGZF on (bgzf.c:1143-1148), zlib on this thread: correct, but serial.
+class GzSource {
+public:
+    static constexpr int kSlots = 4, kDepth = 2;
+
+    GzSource(FILE* f, std::string head, int device, int threads, bool host) : f_(f), pending_(head.begin(), head.end()), device_(device),
+                                                                            threads_(std::max(1, threads)), host_(host) {
+        // compressed / inflated bytes per batch: by default ~2000 blocks of level-6 SAM text, what the kernel needs to fill
+        // the device (tools/dev_bgzf_inflate.py: 2.2 GB/s at 512 blocks per batch, 7.9 GB/s from 2048 on)
+        if (const char* e = getenv("MGX_CLI_INFLATE_BATCH")) { const long long v = atoll(e); if (v > 0) in_cap_ = std::max<uint64_t>((uint64_t)v, 256u << 10); }
+        out_cap_ = 4 * in_cap_;                  // a batch takes fewer blocks when the text inflates more than 4 x
+        max_blocks_ = (uint32_t)std::min<uint64_t>(1u << 18, in_cap_ / 26 + 1);
+    }
+    ~GzSource() {
+        for (Slot& s : slots_) {
+            if (s.b) mgx_bgzf_inflate_batch_destroy(ctx_, s.b);
+        }
+        if (ctx_) mgx_bgzf_destroy(ctx_);
+        if (zinit_) inflateEnd(&zs_);
+    }
+    const std::string& err() const { return err_; }
+    // Stops the source: a next() waiting for a batch to come free returns false (the pipeline failed: the slices that
+    // hold the batches may never be parsed).
+    void abort() {
+        { std::lock_guard<std::mutex> g(mu_); aborted_ = true; }
+        cv_.notify_all();
+    }
+    // device memory the inflate batches will still take, beyond what they hold now (for the -z device memory check, which
+    // sees the batches allocated so far as used), and the inflation ratio so far
+    uint64_t hbm_bytes_to_come() const {
+        int made = 0;
+        for (const Slot& s : slots_) made += s.b != nullptr;
+        return host_ ? 0 : (uint64_t)(kSlots - made) * (in_cap_ + out_cap_ + 2 * ((uint64_t)max_blocks_ + 1) * 8 + (uint64_t)max_blocks_ * 4);
+    }
+    double ratio() const { return in_bytes_ ? (double)out_bytes_ / (double)in_bytes_ : 1.0; }
+    uint64_t in_bytes() const { return in_bytes_; }
+    uint64_t out_bytes() const { return out_bytes_; }
+    double seconds_waiting() const { return wait_s_; }
+
+    // The next piece of text; false at the end of the input or on an error (err() says which).
+    bool next(TextChunk* out) {
+        if (!err_.empty()) return false;
+        if (!gzip_) {
+            for (;;) {
+                while ((int)flight_.size() < kDepth && !bgzf_done_ && free_slot() >= 0) if (!fill_and_submit(free_slot())) return false;
+                if (!flight_.empty()) break;
+                if (bgzf_done_) break;
+                std::unique_lock<std::mutex> lk(mu_);                // every batch holds text being parsed: wait for one
+                cv_.wait(lk, [&] { if (aborted_) return true; for (const Slot& s : slots_) if (!s.busy) return true; return false; });
+                if (aborted_) return false;
+            }
+            if (!flight_.empty()) {
+                const int k = flight_.front();
+                flight_.pop_front();
+                Slot& s = slots_[k];
+                const char* text = nullptr;
+                if (!host_) {
+                    const auto w0 = std::chrono::steady_clock::now();
+                    const uint8_t* o; const uint32_t* st;
+                    if (mgx_bgzf_inflate_batch_wait(ctx_, s.b, &o, &st)) {
+                        err_ = std::string("compressed input, at about byte ") + std::to_string(s.at) + ": " + mgx_last_error();
+                        return false;
+                    }
+                    wait_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+                    text = (const char*)o;
+                } else text = s.host_out.data();
+                out->data = text; out->size = s.n_out;
+                out->hold = std::shared_ptr<void>(static_cast<void*>(&s), [this, k](void*) { release(k); });
+                return true;
+            }
+            if (!pending_.empty() && !gzip_tail_) {
+                err_ = "compressed input is truncated: it ends inside a BGZF block";
+                return false;
+            }
+            if (!gzip_tail_) {
+                if (!eof_block_) fprintf(stderr, "sortmardup: warning: the BGZF input has no EOF block (truncated file?)\n");
+                return false;
+            }
+            gzip_ = true;                                             // plain gzip from here on
+        }
+        return next_gzip(out);
+    }
+
+private:
+    struct Slot {
+        mgx_bgzf_inflate_t* b = nullptr;
+        uint8_t* in = nullptr; uint64_t* io = nullptr; uint64_t* oo = nullptr;
+        std::vector<uint8_t> host_in; std::vector<char> host_out;
+        uint64_t n_out = 0, at = 0;
+        bool busy = false;
+    };
+    int free_slot() {
+        std::lock_guard<std::mutex> g(mu_);
+        if (aborted_) return -1;
+        for (int i = 0; i < kSlots; ++i) if (!slots_[i].busy) return i;
+        return -1;
+    }
+    void release(int k) {
+        { std::lock_guard<std::mutex> g(mu_); slots_[k].busy = false; }
+        cv_.notify_all();
+    }
+    bool setup(Slot& s) {
+        if (host_) {
+            s.host_in.resize(in_cap_); s.host_out.resize(out_cap_);
+            s.io = new uint64_t[max_blocks_ + 1]; s.oo = new uint64_t[max_blocks_ + 1];
+            host_off_.emplace_back(s.io); host_off_.emplace_back(s.oo);
+            s.in = s.host_in.data();
+            return true;
+        }
+        if (!ctx_ && mgx_bgzf_create(device_, 0, &ctx_)) { err_ = std::string("GPU: ") + mgx_last_error(); return false; }
+        if (mgx_bgzf_inflate_batch_create(ctx_, in_cap_, out_cap_, max_blocks_, &s.b) || mgx_bgzf_inflate_batch_offsets(s.b, &s.io, &s.oo)) {
+            err_ = std::string("GPU: ") + mgx_last_error(); return false;
+        }
+        s.in = mgx_bgzf_inflate_batch_input(s.b);
+        return true;
+    }
+    // Reads compressed bytes into slot k (after what the last batch left over), finds its whole blocks and starts them.
+    bool fill_and_submit(int k) {
+        Slot& s = slots_[k];
+        if (!s.in && !setup(s)) return false;
+        uint64_t n = pending_.size();
+        if (n) memcpy(s.in, pending_.data(), n);
+        pending_.clear();
+        while (n < in_cap_ && !file_eof_) {
+            const size_t g = fread(s.in + n, 1, in_cap_ - n, f_);
+            if (g == 0) { if (ferror(f_)) { err_ = "read error on the input"; return false; } file_eof_ = true; }
+            n += g;
+        }
+        isize_.resize(max_blocks_);
+        uint64_t nb = 0; int stop = 0;
+        if (mgx_bgzf_scan_blocks(s.in, n, max_blocks_, s.io, isize_.data(), nullptr, &nb, &stop)) { err_ = std::string("compressed input: ") + mgx_last_error(); return false; }
+        uint32_t k_used = 0; uint64_t out = 0;
+        s.oo[0] = 0;
+        while (k_used < nb && out + isize_[k_used] <= out_cap_) { out += isize_[k_used]; s.oo[++k_used] = out; }
+        const uint64_t used = s.io[k_used];
+        if (k_used) eof_block_ = isize_[k_used - 1] == 0;
+        if (stop == MGX_BGZF_SCAN_NOT_BGZF && k_used == nb) {
+            gz_rest_.assign(s.in + used, s.in + n);                    // a plain gzip member (or something else) starts here
+            gzip_tail_ = true; bgzf_done_ = true;
+        } else {
+            pending_.assign(s.in + used, s.in + n);                    // an incomplete block, or what did not fit
+            if (file_eof_ && k_used == 0) bgzf_done_ = true;           // nothing more will complete it
+        }
+        if (k_used == 0) return true;
+        s.at = in_bytes_;
+        in_bytes_ += used; out_bytes_ += out;
+        s.n_out = out;
+        { std::lock_guard<std::mutex> g(mu_); s.busy = true; }
+        if (!host_) {
+            if (mgx_bgzf_inflate_batch_submit(ctx_, s.b, k_used)) { err_ = std::string("GPU: ") + mgx_last_error(); return false; }
+        } else if (!host_inflate(s, k_used)) return false;
+        flight_.push_back(k);
+        return true;
+    }
+    // MGX_CLI_INFLATE=host: the batch's blocks with zlib, split over threads_ threads
+    bool host_inflate(Slot& s, uint32_t nb) {
+        std::vector<std::thread> gang;
+        std::vector<std::string> errs(threads_);
+        for (int t = 0; t < threads_; ++t)
+            gang.emplace_back([&, t]() {
+                z_stream z{};
+                if (inflateInit2(&z, -15) != Z_OK) { errs[t] = "inflateInit2 failed"; return; }
+                for (uint32_t i = (uint32_t)((uint64_t)nb * t / threads_), e = (uint32_t)((uint64_t)nb * (t + 1) / threads_); i < e; ++i) {
+                    const uint8_t* blk = s.in + s.io[i];
+                    const uint64_t bs = s.io[i + 1] - s.io[i], isize = s.oo[i + 1] - s.oo[i];
+                    uint8_t* dst = reinterpret_cast<uint8_t*>(s.host_out.data()) + s.oo[i];
+                    inflateReset(&z);
+                    z.next_in = const_cast<uint8_t*>(blk + 18); z.avail_in = (uInt)(bs - 26);
+                    z.next_out = dst; z.avail_out = (uInt)isize;
+                    const int r = inflate(&z, Z_FINISH);
+                    uint32_t crc_want;
+                    memcpy(&crc_want, blk + bs - 8, 4);
+                    if (r != Z_STREAM_END || z.total_out != isize || (uint32_t)crc32(0L, dst, (uInt)isize) != crc_want) {
+                        errs[t] = "compressed input: BGZF block at offset " + std::to_string(s.at + s.io[i]) + " is corrupt";
+                        break;
+                    }
+                }
+                inflateEnd(&z);
+            });
+        for (auto& g : gang) g.join();
+        for (auto& e : errs) if (!e.empty()) { err_ = e; return false; }
+        return true;
+    }
+    // plain gzip members, one after the other, with zlib on this thread
+    bool next_gzip(TextChunk* out) {
+        if (!zinit_) {
+            if (inflateInit2(&zs_, 15 + 16) != Z_OK) { err_ = "inflateInit2 failed"; return false; }
+            zinit_ = true;
+            zin_.swap(gz_rest_);
+            in_bytes_ += zin_.size();
+            zs_.next_in = zin_.data(); zs_.avail_in = (uInt)zin_.size();
+        }
+        auto buf = std::make_shared<std::vector<char>>(16u << 20);
+        size_t got = 0;
+        while (got < buf->size()) {
+            if (zs_.avail_in == 0) {
+                if (file_eof_) break;
+                zin_.resize(4u << 20);
+                const size_t g = fread(zin_.data(), 1, zin_.size(), f_);
+                if (g == 0) { if (ferror(f_)) { err_ = "read error on the input"; return false; } file_eof_ = true; break; }
+                zs_.next_in = zin_.data(); zs_.avail_in = (uInt)g;
+                in_bytes_ += g;
+            }
+            if (!in_member_) { inflateReset(&zs_); in_member_ = true; }
+            zs_.next_out = reinterpret_cast<Bytef*>(buf->data() + got); zs_.avail_out = (uInt)(buf->size() - got);
+            const int r = inflate(&zs_, Z_NO_FLUSH);
+            got = buf->size() - zs_.avail_out;
+            if (r == Z_STREAM_END) in_member_ = false;
+            else if (r != Z_OK && r != Z_BUF_ERROR) { err_ = std::string("compressed input: gzip stream is corrupt (") + (zs_.msg ? zs_.msg : "zlib error") + ")"; return false; }
+        }
+        if (got == 0) {
+            if (in_member_) { err_ = "compressed input is truncated: it ends inside a gzip member"; return false; }
+            return false;
+        }
+        out_bytes_ += got;
+        out->data = buf->data(); out->size = got; out->hold = buf;
+        return true;
+    }
+
+    FILE* f_;
+    std::vector<uint8_t> pending_, gz_rest_, zin_;
+    std::vector<uint32_t> isize_;
+    std::vector<std::unique_ptr<uint64_t[]>> host_off_;
+    int device_, threads_;
+    bool host_;
+    mgx_bgzf_t* ctx_ = nullptr;
+    Slot slots_[kSlots];
+    std::deque<int> flight_;
+    uint64_t in_cap_ = 64ull << 20, out_cap_ = 0;
+    uint32_t max_blocks_ = 0;
+    std::mutex mu_; std::condition_variable cv_;
+    bool aborted_ = false;
+    bool file_eof_ = false, bgzf_done_ = false, gzip_tail_ = false, gzip_ = false, eof_block_ = false;
+    z_stream zs_{}; bool zinit_ = false, in_member_ = false;
+    uint64_t in_bytes_ = 0, out_bytes_ = 0;
+    double wait_s_ = 0;
+    std::string err_;
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -194,7 +451,19 @@ int main(int argc, char** argv) {
     // by pread into their own buffer): the reader only looks at a few KB around every cut to place it on a queryname-group
     // boundary.  (Mapping the file and letting every page fault on its own cost 1.8 M page faults per 7 GB and made the ingest time
     // vary by 50 % from run to run.)  stdin goes through read() and owned slices.
-    const int in_fd = (in_path && file_bytes) ? fileno(f) : -1;
+    const int in_fd0 = (in_path && file_bytes) ? fileno(f) : -1;
+    // compressed input (gzip / BGZF) is recognised by the gzip magic in its first two bytes
+    bool gz = false;
+    std::string first_bytes;                                 // what the check read from a stream
+    {
+        unsigned char m[2] = {0, 0};
+        size_t got = 0;
+        if (in_fd0 >= 0) got = pread(in_fd0, m, 2, 0) == 2 ? 2 : 0;
+        else for (int c0; got < 2 && (c0 = fgetc(f)) != EOF;) m[got++] = (unsigned char)c0;
+        gz = got == 2 && m[0] == 0x1f && m[1] == 0x8b;
+        if (in_fd0 < 0) first_bytes.assign(reinterpret_cast<char*>(m), got);
+    }
+    const int in_fd = gz ? -1 : in_fd0;
     const bool map = in_fd >= 0;
     const size_t map_size = (size_t)file_bytes;
     // Round 3: the parsers read their slice IN PLACE from a mapping of the file, after one madvise(MADV_POPULATE_READ) per slice has
@@ -225,7 +494,7 @@ int main(int argc, char** argv) {
     };
 
     // ---- header: read until a line that does not start with '@' is complete
-    std::string carry;                                       // text read but not yet handed to a parser
+    std::string carry = gz ? std::string() : first_bytes;   // text read but not yet handed to a parser
     samtext::Header hdr;
     bool eof = false;
     std::vector<char> buf(1u << 20);
@@ -238,7 +507,42 @@ int main(int argc, char** argv) {
         }
     };
     size_t map_pos = 0;
-    if (map) {
+    std::unique_ptr<GzSource> src;                          // compressed input
+    TextChunk gz_first; size_t gz_first_off = 0; bool gz_have = false;
+    std::string gz_carry;                                    // inflated text not yet in a slice
+    if (gz) {
+        const char* e = getenv("MGX_CLI_INFLATE");
+        src.reset(new GzSource(f, first_bytes, device, threads, e && !strcmp(e, "host")));
+        // the header: '@' lines from the first pieces of text (kept apart; the body is cut from the pieces in place)
+        std::string head;
+        for (bool first = true;; first = false) {
+            TextChunk t;
+            if (!src->next(&t)) {
+                if (!src->err().empty()) { fprintf(stderr, "%s\n", src->err().c_str()); return 1; }
+                break;
+            }
+            if (first && t.size >= 4 && !memcmp(t.data, "BAM\1", 4)) {
+                fprintf(stderr, "%s is BAM, not SAM: sortmardup reads SAM text (plain, gzip or BGZF compressed)\n", in_path ? in_path : "stdin");
+                return 1;
+            }
+            size_t p = 0;
+            if (!head.empty() && head.back() != '\n') {         // a header line that goes on in this piece
+                const char* nl = (const char*)memchr(t.data, '\n', t.size);
+                if (!nl) { head.append(t.data, t.size); continue; }
+                p = (size_t)(nl - t.data) + 1;
+                head.append(t.data, p);
+            }
+            while (p < t.size && t.data[p] == '@') {
+                const char* nl = (const char*)memchr(t.data + p, '\n', t.size - p);
+                const size_t e2 = nl ? (size_t)(nl - t.data) + 1 : t.size;
+                head.append(t.data + p, e2 - p);
+                p = e2;
+            }
+            if (p < t.size) { gz_first = std::move(t); gz_first_off = p; gz_have = true; break; }
+        }
+        const size_t body = samtext::parse_header(head.data(), head.size(), &hdr);
+        gz_carry.assign(head, body, std::string::npos);
+    } else if (map) {
         // the header: the file's head, more of it until a line that does not start with '@' is in sight
         std::vector<char> head;
         for (size_t want = 1u << 20;; want *= 4) {
@@ -266,12 +570,15 @@ int main(int argc, char** argv) {
         if (body_seen || eof) break;
         read_more(1u << 20);
     }
-    if (!map) {
+    if (!map && !gz) {
         const size_t body = samtext::parse_header(carry.data(), carry.size(), &hdr);
         carry.erase(0, body);
     }
     uint64_t L = 0;
     for (uint64_t x : hdr.ref_len) L += x;
+    // bytes of SAM text, for the sizes below: of compressed input, the file's size times the ratio of what is inflated so far
+    const uint64_t text_bytes = gz ? (uint64_t)((double)file_bytes * src->ratio()) : file_bytes;
+    const uint64_t inflate_hbm = gz ? src->hbm_bytes_to_come() : 0;
 
     // The device contexts come up on a thread of their own (the HIP runtime takes a few tenths of a second to start)
     // while the first slices are already being parsed; a parser waits for them only when it has bytes for the device.
@@ -287,14 +594,14 @@ int main(int argc, char** argv) {
         auto since = [&]() { return std::chrono::duration<double>(clk::now() - i0).count(); };
         // What the parsers wait for comes first: the record store (runtime start, streams, the first piece of HBM) and the
         // sort context; the compressor's own state is set up afterwards, while the text is being parsed.
-        if (use_store && file_bytes) {
+        if (use_store && text_bytes) {
             // -z device keeps every BAM byte in HBM next to the sort's buffers; when the input cannot fit, say so now and keep
             // the bytes in host memory instead of failing in the middle of the ingest.  BAM bytes are about half
             // the SAM text; the sort and the emit need about 100 bytes per record of ~360 text bytes on top.
             uint64_t free_b = 0, total_b = 0;
             if (mgx_bgzf_device_memory(device, &free_b, &total_b) == 0) {
                 if (const char* e = getenv("MGX_CLI_DEVICE_FREE")) free_b = strtoull(e, nullptr, 10);      // tests: pretend
-                const uint64_t need = file_bytes * 6 / 10 + (file_bytes / 360) * 100 + (1ull << 30);
+                const uint64_t need = text_bytes * 6 / 10 + (text_bytes / 360) * 100 + (1ull << 30) + inflate_hbm;
                 if (need > free_b) {
                     fprintf(stderr, "sortmardup: about %.1f GB of device memory needed for -z device, %.1f GB free: keeping the BAM bytes in host memory (-z pinned)\n",
                             need / 1e9, free_b / 1e9);
@@ -305,9 +612,9 @@ int main(int argc, char** argv) {
         if (tr) fprintf(stderr, "  bring-up: runtime up, device memory known at %.3f s\n", since());
         if (use_store && mgx_bgzf_create(device, 0, &zctx)) ok = false;
         if (tr) fprintf(stderr, "  bring-up: compressor context at %.3f s\n", since());
-        if (ok && use_store && (mgx_bgzf_store_create(zctx, &store) || mgx_bgzf_store_reserve(store, file_bytes ? file_bytes * 6 / 10 : (1ull << 30)))) ok = false;
+        if (ok && use_store && (mgx_bgzf_store_create(zctx, &store) || mgx_bgzf_store_reserve(store, text_bytes ? text_bytes * 6 / 10 : (1ull << 30)))) ok = false;
         if (tr) fprintf(stderr, "  bring-up: record store ready at %.3f s\n", since());
-        if (ok && (mgx_sortdedup_create(device, 0, &sd) || mgx_sortdedup_upload_begin(sd, L, file_bytes / 256))) ok = false;
+        if (ok && (mgx_sortdedup_create(device, 0, &sd) || mgx_sortdedup_upload_begin(sd, L, text_bytes / 256))) ok = false;
         if (tr) fprintf(stderr, "  bring-up: sort context ready at %.3f s\n", since());
         {
             std::lock_guard<std::mutex> g(gpu_mu);
@@ -339,9 +646,14 @@ int main(int argc, char** argv) {
     std::vector<std::unique_ptr<Chunk>> kept_chunks;         // committed slices: their writer records, and (not -z device) the BAM bytes
     bamout::NoInitVector<Kept> by_arrival;                   // flattened after the ingest (its pages first touched by the copying gang)
     auto fail = [&](const std::string& msg) {
-        std::lock_guard<std::mutex> g(mu);
-        if (!failed.exchange(true)) first_error = msg;
-        cv_work.notify_all(); cv_room.notify_all();
+        std::deque<Slice> dropped;                           // (released outside the lock: a slice may hold an inflate batch)
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (!failed.exchange(true)) first_error = msg;
+            dropped.swap(queue);                             // nothing queued will be parsed now
+            cv_work.notify_all(); cv_room.notify_all();
+        }
+        if (src) src->abort();                               // a reader waiting for a batch to come free stops waiting
     };
     double commit_seconds = 0, upload_seconds = 0;           // serial part of the ingest (MGX_CLI_TRACE)
     // The in-order commit is the one serial step of the ingest: it only turns slice-local mate indices into arrival
@@ -431,8 +743,10 @@ int main(int argc, char** argv) {
                     if (text_buf.size() < sl.file_len) text_buf.resize(sl.file_len);
                     if (!pread_all(in_fd, text_buf.data(), sl.file_len, sl.file_off)) { fail("read error on the input file"); return; }
                     parse_slice(text_buf.data(), sl.file_len, hdr, L, ch.get());
-                } else parse_slice(sl.text.data(), sl.text.size(), hdr, L, ch.get());
+                } else if (sl.ext) parse_slice(sl.ext, sl.ext_len, hdr, L, ch.get());
+                else parse_slice(sl.text.data(), sl.text.size(), hdr, L, ch.get());
                 std::string().swap(sl.text);
+                sl.hold.reset();                             // an inflated buffer goes back to the source once its text is parsed
                 if (!ch->err.empty()) { fail("SAM parse error: " + ch->err); return; }
                 // (bounded: 12 slices per thread -- ~80 MB of parsed records, 1.3 GB over 16 threads -- cover a 4 M-record input whole;
                 // with 32 the peak resident set of a 20 M-record run grew from 5.8 to 9.2 GB for 0.1 s of ingest)
@@ -490,7 +804,79 @@ int main(int argc, char** argv) {
         queue.push_back(std::move(sl));
         cv_work.notify_one();
     }
-    while (!map && !failed.load()) {
+    if (gz) {
+        // Compressed input: pieces of inflated text are cut at queryname-group boundaries IN PLACE (the parsers read the
+        // pinned buffer the device wrote); only a group that straddles two pieces is copied, into an owned slice.
+        auto push = [&](Slice sl) -> bool {
+            sl.seq = seq++;
+            std::unique_lock<std::mutex> lk(mu);
+            cv_room.wait(lk, [&] { return queue.size() < queue_cap || failed.load(); });
+            if (failed.load()) return false;
+            queue.push_back(std::move(sl));
+            cv_work.notify_one();
+            return true;
+        };
+        auto in_place = [&](const TextChunk& t, size_t at, size_t n) { Slice sl; sl.ext = t.data + at; sl.ext_len = n; sl.hold = t.hold; return push(std::move(sl)); };
+        TextChunk t = std::move(gz_first);
+        size_t pos = gz_first_off;
+        bool ok = true;
+        for (bool have = gz_have; have && ok && !failed.load(); t = TextChunk(), pos = 0, have = ok && !failed.load() && src->next(&t)) {
+            const char* d = t.data;
+            const size_t n = t.size;
+            if (!gz_carry.empty() && pos < n) {
+                // the carried group goes on into this piece up to the first line of another queryname
+                size_t p = pos;
+                if (gz_carry.back() != '\n') {
+                    const char* nl = (const char*)memchr(d + p, '\n', n - p);
+                    p = nl ? (size_t)(nl - d) + 1 : n;
+                    gz_carry.append(d + pos, p - pos);
+                    pos = p;
+                }
+                if (gz_carry.back() == '\n') {
+                    const size_t lb = gz_carry.size() >= 2 ? gz_carry.rfind('\n', gz_carry.size() - 2) : std::string::npos;
+                    const char* l0 = gz_carry.data() + (lb == std::string::npos ? 0 : lb + 1);
+                    const std::string qn(l0, line_qname_end(l0, gz_carry.data() + gz_carry.size()));
+                    bool ended = false;
+                    while (p < n) {
+                        const char* nl = (const char*)memchr(d + p, '\n', n - p);
+                        const char* le = nl ? nl : d + n;
+                        const char* qe = line_qname_end(d + p, le);
+                        if (!nl && qe == le) break;                  // a partial line whose queryname is not complete yet
+                        if ((size_t)(qe - (d + p)) != qn.size() || memcmp(d + p, qn.data(), qn.size())) { ended = true; break; }
+                        if (!nl) break;
+                        p = (size_t)(nl - d) + 1;
+                    }
+                    gz_carry.append(d + pos, p - pos);
+                    pos = p;
+                    if (ended) { Slice sl; sl.text.swap(gz_carry); ok = push(std::move(sl)); gz_carry.clear(); }
+                    else if (pos < n) { gz_carry.append(d + pos, n - pos); pos = n; }
+                }
+            }
+            while (ok && pos < n && gz_carry.empty()) {
+                const size_t rest = n - pos;
+                if (rest > window) {
+                    size_t lim = window, cut = 0;
+                    for (;;) {
+                        const char* nl = (const char*)memrchr(d + pos, '\n', lim);
+                        cut = nl ? last_group_start(d + pos, (size_t)(nl - (d + pos)) + 1) : 0;
+                        if (cut || lim == rest) break;
+                        lim = std::min(rest, lim * 2);
+                    }
+                    if (cut) { ok = in_place(t, pos, cut); pos += cut; continue; }
+                }
+                // the tail: its complete groups in place; the last group (it may go on in the next piece) is carried
+                const char* nl = (const char*)memrchr(d + pos, '\n', rest);
+                const size_t g = nl ? last_group_start(d + pos, (size_t)(nl - (d + pos)) + 1) : 0;
+                if (g) { ok = in_place(t, pos, g); pos += g; }
+                gz_carry.assign(d + pos, n - pos);
+                pos = n;
+            }
+        }
+        t = TextChunk();
+        if (!src->err().empty()) fail(src->err());
+        else if (ok && !failed.load() && !gz_carry.empty()) { Slice sl; sl.text.swap(gz_carry); push(std::move(sl)); }
+    }
+    while (!map && !gz && !failed.load()) {
         if (carry.size() < window && !eof) read_more(window - carry.size());
         if (carry.empty() && eof) break;
         size_t cut;
@@ -518,6 +904,11 @@ int main(int argc, char** argv) {
         cv_work.notify_all();
     }
     for (auto& th : pool) th.join();
+    if (src && getenv("MGX_CLI_TRACE"))
+        fprintf(stderr, "  inflate: %.3f GB compressed -> %.3f GB of text, %.3f s waiting for the device\n", src->in_bytes() / 1e9, src->out_bytes() / 1e9, src->seconds_waiting());
+    queue.clear();                                           // (after a failure: slices never parsed still hold inflated text)
+    gz_first = TextChunk();
+    src.reset();                                             // the inflate batches' pinned and device memory
     gpu_init.join();
     if (!gpu_ready()) { fprintf(stderr, "GPU: %s\n", gpu_error.c_str()); return 1; }
     if (in_path) fclose(f);

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/mgx_bgzf.h"
+#include "mgx_bgzf_ctx.h"
 #include "mgx_common.h"
 
 using mgx::set_error;
@@ -916,21 +917,6 @@ __global__ __launch_bounds__(256) void k_store_gather(const u64* addr, const u32
 }
 
 }  // namespace
-
-struct mgx_bgzf {
-    int device = 0;
-    int n_cu = 0;
-    hipStream_t stream = nullptr;              // all batches of a context run in order on one stream
-    hipStream_t copy = nullptr;                // packed blocks travel back on a stream of their own, behind their batch's kernels only
-    hipStream_t up = nullptr;                  // ... and a batch's input travels up on a third one, under the kernels of the batch before
-    std::mutex prep_mu; bool prepared = false; // the compressor's scratch and kernel attributes: set up at first use (or mgx_bgzf_prepare)
-    u32* d_scratch = nullptr; u32 grid = 0;
-    u32* d_n_stored = nullptr;
-    unsigned long long* d_prof = nullptr;
-    u32 lazy = 1, cost_base = 10, cost_rle = 6;
-    u64 n_blocks = 0, bytes_in = 0, bytes_out = 0;
-    float ms_kernels = 0, ms_pack = 0;
-};
 
 struct mgx_bgzf_batch {
     u64 in_cap = 0; u32 max_blocks = 0;

@@ -1,0 +1,26 @@
+// mgx_bgzf_ctx.h -- the BGZF context (include/mgx_bgzf.h) as its two translation units see it: the compressor
+// (mgx_bgzf.hip) and the inflater (mgx_bgzf_inflate.hip) share its device and streams.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <mutex>
+
+struct mgx_bgzf {
+    int device = 0;
+    int n_cu = 0;
+    hipStream_t stream = nullptr;              // all batches of a context run in order on one stream
+    hipStream_t copy = nullptr;                // packed blocks travel back on a stream of their own, behind their batch's kernels only
+    hipStream_t up = nullptr;                  // ... and a batch's input travels up on a third one, under the kernels of the batch before
+    std::mutex prep_mu; bool prepared = false; // the compressor's scratch and kernel attributes: set up at first use (or mgx_bgzf_prepare)
+    uint32_t* d_scratch = nullptr; uint32_t grid = 0;
+    uint32_t* d_n_stored = nullptr;
+    unsigned long long* d_prof = nullptr;
+    uint32_t lazy = 1, cost_base = 10, cost_rle = 6;
+    uint64_t n_blocks = 0, bytes_in = 0, bytes_out = 0;
+    float ms_kernels = 0, ms_pack = 0;
+    // inflate (mgx_bgzf_inflate.hip)
+    std::mutex inf_mu;
+    uint64_t inf_blocks = 0, inf_bytes_in = 0, inf_bytes_out = 0;
+    float inf_ms_kernel = 0;
+};

@@ -212,5 +212,22 @@ BGZF_SYMBOLS = {
     "mgx_bgzf_store_put": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mgx_bgzf_store_emit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+
+class BgzfInflateStats(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("ms_kernel", C.c_float)]
+
+
+BGZF_SYMBOLS.update({
+    "mgx_bgzf_scan_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "mgx_bgzf_inflate_batch_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mgx_bgzf_inflate_batch_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "mgx_bgzf_inflate_batch_input": (C.c_void_p, [C.c_void_p]),
+    "mgx_bgzf_inflate_batch_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "mgx_bgzf_inflate_batch_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "mgx_bgzf_inflate_batch_wait": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "mgx_bgzf_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mgx_bgzf_inflate_stats": (C.c_int, [C.c_void_p, C.POINTER(BgzfInflateStats)]),
+})
 BGZF_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p)
 SYMBOLS.update(BGZF_SYMBOLS)

@@ -88,6 +88,51 @@ typedef struct mgx_bgzf_stats {
 } mgx_bgzf_stats_t;
 int mgx_bgzf_stats(mgx_bgzf_t* ctx, mgx_bgzf_stats_t* out);
 
+/* ---- Inflate: BGZF blocks -> their bytes, on the device ----------------------------------------------
+ * The read side of what htslib does in bgzf_read_block / inflate_block (bgzf.c:716-780, 1100-1180): every block is a whole
+ * gzip member, its compressed size is in its header (BSIZE) and its inflated size in its trailer (ISIZE), so a batch's
+ * block starts AND output offsets are known before anything is decoded.  One wavefront decodes one block (stored, fixed
+ * and dynamic Huffman DEFLATE blocks, no history across members), checks the CRC-32 and ISIZE, and writes a status word;
+ * corrupt input is a returned error (-EBADMSG, mgx_last_error() names the first bad block and why), never a fault. */
+
+/* Host only, no device: walks the BSIZE chain of data[0, n).  Block i starts at block_offsets[i] (n_blocks + 1 entries
+ * are written: the last is where the walk stopped); isize / crc (either may be NULL) get each block's trailer fields.
+ * *stop says why the walk ended: */
+#define MGX_BGZF_SCAN_END 0        /* the data ends right after the last block */
+#define MGX_BGZF_SCAN_PARTIAL 1    /* an incomplete block at the end: more input is needed */
+#define MGX_BGZF_SCAN_NOT_BGZF 2   /* the bytes at the stop offset are not a BGZF member (plain gzip, or not gzip) */
+#define MGX_BGZF_SCAN_FULL 3       /* max_blocks blocks were found */
+/* Returns 0, -EINVAL (NULL argument) or -EILSEQ (a BGZF header with an impossible size or ISIZE: the message names it). */
+int mgx_bgzf_scan_blocks(const uint8_t* data, uint64_t n, uint64_t max_blocks, uint64_t* block_offsets, uint32_t* isize,
+                         uint32_t* crc, uint64_t* n_blocks, int* stop);
+
+/* A batch owns pinned input (whole BGZF blocks back to back, filled by the caller), device buffers, and pinned output.
+ * in_offsets[0 .. n_blocks] are the blocks' offsets in the input (in_offsets[0] = 0), out_offsets[0 .. n_blocks] the
+ * prefix sums of their ISIZEs (out_offsets[0] = 0).  submit() only enqueues (H2D, kernel, D2H): several batches may be in
+ * flight on one context, beside compress batches. */
+typedef struct mgx_bgzf_inflate mgx_bgzf_inflate_t;
+int mgx_bgzf_inflate_batch_create(mgx_bgzf_t* ctx, uint64_t in_capacity, uint64_t out_capacity, uint32_t max_blocks,
+                                  mgx_bgzf_inflate_t** out);
+void mgx_bgzf_inflate_batch_destroy(mgx_bgzf_t* ctx, mgx_bgzf_inflate_t* b);
+uint8_t* mgx_bgzf_inflate_batch_input(mgx_bgzf_inflate_t* b);        /* [in_capacity] */
+/* *in_offsets, *out_offsets: [max_blocks + 1] each, pinned, filled by the caller */
+int mgx_bgzf_inflate_batch_offsets(mgx_bgzf_inflate_t* b, uint64_t** in_offsets, uint64_t** out_offsets);
+int mgx_bgzf_inflate_batch_submit(mgx_bgzf_t* ctx, mgx_bgzf_inflate_t* b, uint32_t n_blocks);
+/* Waits for the batch.  *out = the inflated bytes back to back (pinned, owned by the batch, valid until the next submit);
+ * *status = one word per block (0 = good; may be NULL).  Returns 0, or -EBADMSG when a block is bad: the other blocks'
+ * bytes are still in place, and the context stays usable. */
+int mgx_bgzf_inflate_batch_wait(mgx_bgzf_t* ctx, mgx_bgzf_inflate_t* b, const uint8_t** out, const uint32_t** status);
+
+/* One shot over pageable memory: in[0, n_in) must be whole BGZF blocks (an EOF block included or not); the bytes go to
+ * out (capacity out_capacity, at least the sum of the ISIZEs), *n_out = how many. */
+int mgx_bgzf_decompress(mgx_bgzf_t* ctx, const uint8_t* in, uint64_t n_in, uint8_t* out, uint64_t out_capacity, uint64_t* n_out);
+
+typedef struct mgx_bgzf_inflate_stats {
+    uint64_t n_blocks, bytes_in, bytes_out;   /* inflated since create */
+    float ms_kernel;                          /* last batch waited for: the inflate kernel (HIP events on its stream) */
+} mgx_bgzf_inflate_stats_t;
+int mgx_bgzf_inflate_stats(mgx_bgzf_t* ctx, mgx_bgzf_inflate_stats_t* out);
+
 #ifdef __cplusplus
 }
 #endif
