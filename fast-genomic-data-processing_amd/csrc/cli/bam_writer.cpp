@@ -2,6 +2,7 @@
 #include "bam_writer.h"
 
 #include "../../../include/mgx_bgzf.h"
+#include "gang.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -252,10 +253,7 @@ bool write_bai(const std::string& path, const samtext::Header& hdr, const Record
     else {
         std::vector<std::vector<RefIndex>> part(T, std::vector<RefIndex>(idx.size()));
         std::vector<uint64_t> part_no(T, 0);
-        std::vector<std::thread> gang;
-        for (size_t t = 0; t < T; ++t)
-            gang.emplace_back([&, t]() { auto v = voff; index_part(recs, recs.size() * t / T, recs.size() * (t + 1) / T, v, part[t], &part_no[t]); });
-        for (auto& th : gang) th.join();
+        gang::run_gang(T, [&](size_t t) { auto v = voff; const auto r = gang::gang_range(recs.size(), t, T); index_part(recs, r.begin, r.end, v, part[t], &part_no[t]); });
         for (size_t t = 0; t < T; ++t) {
             n_no_coor += part_no[t];
             for (size_t r = 0; r < idx.size(); ++r) {
@@ -515,17 +513,13 @@ bool write_bam_store(const std::string& path, const samtext::Header& hdr, const 
     std::unique_ptr<uint32_t[]> order(new uint32_t[n + 1]), len(new uint32_t[n + 1]);
     std::unique_ptr<uint8_t[]> dup(new uint8_t[n + 1]);
     std::unique_ptr<uint64_t[]> addr(new uint64_t[n + 1]), uoff(new uint64_t[n + 1]);
-    {
-        std::vector<std::thread> gang;
-        const size_t T = (size_t)std::max(1, std::min(threads, 16));
-        for (size_t t = 0; t < T; ++t)
-            gang.emplace_back([&, t]() {
-                for (size_t q = n * t / T, e = n * (t + 1) / T; q < e; ++q) {
-                    order[q] = (uint32_t)q; len[q] = recs[q].len; dup[q] = recs[q].set_dup; addr[q] = (uint64_t)(uintptr_t)recs[q].blob;
-                }
-            });
-        for (auto& th : gang) th.join();
-    }
+    const size_t T = (size_t)std::max(1, std::min(threads, 16));
+    gang::run_gang(T, [&](size_t t) {
+        const auto r = gang::gang_range(n, t, T);
+        for (size_t q = r.begin; q < r.end; ++q) {
+            order[q] = (uint32_t)q; len[q] = recs[q].len; dup[q] = recs[q].set_dup; addr[q] = (uint64_t)(uintptr_t)recs[q].blob;
+        }
+    });
     g_store_arrays_ready.store(1);
     stamp("arrays ready");
     // The sink must be done with a batch's bytes when it returns.  Round 3: it simply writes them -- one pwrite of the whole batch

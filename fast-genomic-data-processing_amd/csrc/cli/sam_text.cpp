@@ -58,15 +58,17 @@ size_t parse_header(const char* data, size_t size, Header* h) {
 namespace {
 
 const uint8_t* nt16_table() {
-    static uint8_t t[256];
-    static bool init = false;
-    if (!init) {
-        memset(t, 15, sizeof t);
+    // (built by the static's initialiser, which runs once: the parser threads start at the same moment, and a second
+    // thread refilling the table turned another thread's bases into N for the length of its memset)
+    struct Table { uint8_t t[256]; };
+    static const Table table = [] {
+        Table x;
+        memset(x.t, 15, sizeof x.t);
         const char* codes = "=ACMGRSVTWYHKDBN";
-        for (int i = 0; i < 16; ++i) { t[(uint8_t)codes[i]] = (uint8_t)i; t[(uint8_t)(codes[i] | 0x20)] = (uint8_t)i; }
-        init = true;
-    }
-    return t;
+        for (int i = 0; i < 16; ++i) { x.t[(uint8_t)codes[i]] = (uint8_t)i; x.t[(uint8_t)(codes[i] | 0x20)] = (uint8_t)i; }
+        return x;
+    }();
+    return table.t;
 }
 
 // the first tab in [p, end), or end.  Most fields of a SAM line are a few bytes long: a call of memchr per field costs more than
