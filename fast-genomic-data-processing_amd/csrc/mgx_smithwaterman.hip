@@ -40,6 +40,7 @@
 
 #include "../../include/mgx_smithwaterman.h"
 #include "mgx_common.h"
+#include "sw_i16_rule.h"
 
 using mgx::set_error;
 
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
 // and the four decisions of a cell -- E opened, F opened, E beats the diagonal, F beats both -- are the SIGN BITS of four packed
 // differences, merged with v_bfi into one nibble per pair: ~25 instructions per two cells.  Values are the reference's exactly as long
 // as nothing wraps: the host admits a pair only when every real value and every difference of two of them fits 16 bits
-// (I16Rule below: bounds from the lengths and the scoring parameters; LOW_INIT_VALUE becomes a per-pair value below every real one),
+// (I16Rule, sw_i16_rule.h: bounds from the lengths and the scoring parameters; LOW_INIT_VALUE becomes a per-pair value below every real one),
 // everything else takes k_sw_fill.  Cells outside a pair's own matrix (the other half is longer, padding rows) may wrap: nothing real
 // reads them.
 //   * back-trace: one 32-bit word per lane, step and four rows: low half = the first pair's four nibbles (row 4q in bits 0-3),
@@ -575,35 +576,8 @@ Shape shape16_for(int len1, bool paired) {
     for (int r : cls) if (len1 <= 64 * r) return Shape{64, r};
     return Shape{0, 0};
 }
-// Every value k_sw_fill16 computes for a cell of the pair's own matrix, and every difference of two of them, must fit 16 bits.
-//   H(i, j) >= the all-diagonal path from the boundary: blo + min(len) * min(match, mismatch, 0)
-//   any H, E, F <= the best a path can collect: bhi + min(len) * max(match, mismatch, 0) when gaps cost (open, extend <= 0)
-//   one more open / extend / match on top of either: `pad`
-// LOW_INIT_VALUE only ever meets a real value as LOW + extend against H + open (first column of E, first row of F) and must lose
-// strictly: low = L - |extend| - 1.  MATRIX_MIN_CUTOFF (-1e8) cannot bind inside 16 bits.
-struct I16Rule {
-    int64_t open, extend, dlo, dhi, pos, a_ext, pad;
-    bool gaps_cost;
-    explicit I16Rule(const SwParams& P) : open(P.open), extend(P.extend), dlo(std::min(P.match, P.mismatch)), dhi(std::max(P.match, P.mismatch)) {
-        pos = std::max<int64_t>({dhi, open, extend, 0});
-        a_ext = std::llabs((long long)extend);
-        pad = std::llabs((long long)open) + a_ext + std::max(std::llabs((long long)P.match), std::llabs((long long)P.mismatch));
-        gaps_cost = open <= 0 && extend <= 0;
-    }
-    bool admits(int64_t n, int64_t m, int32_t* low16) const {
-        if (m > 4096) return false;                          // two alternates per lane group are staged in LDS as 32-bit words
-        const int64_t mx = std::max(n, m), mn = std::min(n, m);
-        const int64_t b_end = open + (mx - 1) * extend;
-        const int64_t blo = std::min<int64_t>({0, open, b_end}), bhi = std::max<int64_t>({0, open, b_end});
-        const int64_t u0 = gaps_cost ? bhi + mn * std::max<int64_t>(dhi, 0) : bhi + (n + m) * pos;
-        const int64_t lh = blo + mn * std::min<int64_t>(dlo, 0);
-        const int64_t lo = lh - pad, up = u0 + pad;
-        const int64_t low = lo - a_ext - 1, ll = low - a_ext;
-        if (ll < -32768 || up > 32767 || up - ll > 32767) return false;
-        *low16 = (int32_t)low;
-        return true;
-    }
-};
+// admission: I16Rule (sw_i16_rule.h), bounds on every value and difference from the lengths and the scoring parameters
+using mgx_sw16::I16Rule;
 inline u64 bt_bytes16(u64 steps_max, const Shape& sh) { return ((steps_max + 1) * sh.g * bt_slot16(sh.rpl) + 15) & ~15ull; }
 inline u64 lr_bytes16(u64 n_swp, const Shape& sh) { return ((n_swp + 1) * sh.rpl * 4 + 15) & ~15ull; }
 constexpr int kCompactElems = 16;             // merged CIGAR elements copied back per pair without a second look
@@ -690,7 +664,7 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
     tp[0] = now();
     const bool paired = knobs.paired >= 0 ? knobs.paired != 0 : n >= kPairedFrom;
     const SwParams P{params->match, params->mismatch, params->gap_open, params->gap_extend};
-    const I16Rule rule(P);
+    const I16Rule rule(P.match, P.mismatch, P.open, P.extend);
     const u64 base1 = in->ref_off[lo], base2 = in->alt_off[lo];
     const u64 n1 = in->ref_off[hi] - base1, n2 = in->alt_off[hi] - base2;
     // the sequences travel to pinned memory on a helper thread while this one lays out the jobs

@@ -194,3 +194,150 @@ def test_largest_sizes_and_many_chunks(sw_engine, sw_oracle, synth, monkeypatch)
     assert np.array_equal(got_o, want_o) and np.array_equal(got_s, want_s) and got_c == want_c
     st = sw_engine.stats()
     assert st["n_pairs_i16"] == 600 and st["n_launches"] >= 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The packed 16-bit fill along its admission frontier.  Whether a pair is admitted is asked of the host driver
+# (tests/cpp/sw_i16_rule_driver.cpp over csrc/sw_i16_rule.h), never of the device; CIGAR, offset and score come from the
+# oracle; n_pairs_i16 must equal the driver's count, so a pair meant for the 16-bit kernel cannot pass through the 32-bit one.
+import sw_frontier as F  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def rule_driver(tmp_path_factory):
+    return F.Driver(tmp_path_factory.mktemp("sw_i16_rule"), sanitize=False)
+
+
+def _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, families, monkeypatch, want=None):
+    """one batch through the engine under each lane-group family; -> the driver's admission per pair"""
+    lens = [(len(r), len(a)) for r, a in pairs]
+    adm = rule_driver.admitted(params, lens)
+    w = F.concat(pairs, strat)
+    want_c, want_o, want_s = sw_oracle.batch(w, params)
+    for paired in families:
+        monkeypatch.setenv("MGX_SW_PAIRED", paired)
+        if want is not None:             # the partners the batch was built for do meet
+            assert set(F.lane_groups(lens, adm, paired == "1")) == set(want(paired == "1")), (params, paired)
+        got_c, got_o, got_s = sw_engine.align_batch(w["ref_off"], w["ref"], w["alt_off"], w["alt"], w["strategy"], params, want_score=True)
+        bad = [q for q in range(len(pairs)) if got_s[q] != want_s[q] or got_o[q] != want_o[q] or got_c[q] != want_c[q]]
+        assert not bad, (params, paired, [(lens[q], int(strat[q]), adm[q]) for q in bad[:8]])
+        assert sw_engine.stats()["n_pairs_i16"] == sum(adm), (params, paired)
+    return adm
+
+
+@pytest.mark.parametrize("paired", ["0", "1"])
+@pytest.mark.parametrize("params", F.REAL_SETS, ids=str)
+def test_frontier_of_the_real_parameters_in_every_row_class(sw_engine, sw_oracle, rule_driver, monkeypatch, params, paired):
+    """for a reference at the top or the bottom of every row class of the family: the largest admitted alternate (bisection
+    over the driver), one base less, and one more -- which comes back through the 32-bit kernel, as the count shows.
+    Extremal sequences and strategies rotate over the classes."""
+    pairs, strat, expect = [], [], []
+    for c, (r, n_lo, n_hi) in enumerate(F.class_lengths(paired == "1")):
+        n = n_hi if c % 2 == 0 else n_lo
+        m = rule_driver.largest_admitted_alt(params, n)
+        for d, mm in enumerate((m - 1, m, m + 1)):
+            if mm < 1:
+                continue
+            for e in range(2):
+                pairs.append(F.extremal(F.EXTREMAL_KINDS[(3 * c + 2 * d + e) % 8], n, mm)); strat.append(F.STRATEGIES[(c + d + e) % 4])
+                expect.append(mm <= m)
+    adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, (paired,), monkeypatch)
+    assert adm == expect and any(adm) and not all(adm)
+
+
+@pytest.mark.parametrize("name,params,side", F.SCALED_SETS, ids=[s[0] for s in F.SCALED_SETS])
+def test_frontier_of_scaled_parameters_cuts_through_the_batch(sw_engine, sw_oracle, rule_driver, monkeypatch, name, params, side):
+    """the dense boxes of test_sw_i16_rule_host.py as one batch per parameter set, in row-major order of (n, m): admitted and
+    refused pairs interleave.  One rotating extremal pair per point, all of them under every strategy within two steps of
+    the frontier."""
+    pts = [(n, m) for n in range(1, side + 1) for m in range(1, side + 1)]
+    ok = dict(zip(pts, rule_driver.admitted(params, pts)))
+    pairs, strat = [], []
+    for q, (n, m) in enumerate(pts):
+        hood = [ok.get((n + d, m + e), False) for d in range(-2, 3) for e in range(-2, 3) if n + d >= 1 and m + e >= 1]
+        if any(hood) and not all(hood):
+            for st in F.STRATEGIES:
+                for kind in F.EXTREMAL_KINDS:
+                    pairs.append(F.extremal(kind, n, m)); strat.append(st)
+        else:
+            pairs.append(F.extremal(F.EXTREMAL_KINDS[q % 8], n, m)); strat.append(F.STRATEGIES[(q // 8) % 4])
+    adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, ("0", "1"), monkeypatch)
+    assert 0 < sum(adm) < len(adm)
+    flips = sum(1 for a, b in zip(adm, adm[1:]) if a != b)
+    assert flips >= side // 2                # the frontier runs through the batch, not along its end
+
+
+@pytest.mark.parametrize("params", [F.STANDARD_NGS, F.FLAT], ids=str)
+def test_frontier_pair_with_an_unequal_partner(sw_engine, sw_oracle, rule_driver, monkeypatch, params):
+    """A frontier pair (reference at the top of its row class, largest admitted alternate) sharing its lane group with a very
+    different partner.  The admitted pairs of a batch are launched class by class and, inside a class, longest alternate
+    first, equal alternates in input order; neighbours of that order share a lane group, the first in the low halves (kJobHalf
+    clear), the second in the high halves (kJobHalf set).  So every class below holds exactly the two pairs that are to meet
+    (sw_frontier.lane_groups restates the order and the test checks the meeting):
+      (a) class of 1 row per lane: the frontier pair and a 1 x 1 pair -> frontier low, 1 x 1 high
+      (b) two classes: the frontier pair and a pair of the same class with a quarter of the alternate -> frontier low
+      (c) two classes: the frontier pair alone -> frontier low, a filler job high (odd class size)
+      (d) three classes: the frontier pair and, listed before it, the frontier pair of the shortest reference of the class,
+          whose alternate is at least as long -> frontier HIGH, under a partner that sweeps on after its last column
+    A shorter partner cannot sit in the low halves and a filler cannot either: the order puts the longer alternate first."""
+    fam = {}
+    for paired in (False, True):
+        cl = {r: (lo, hi) for r, lo, hi in F.class_lengths(paired)}
+        big = {r: rule_driver.largest_admitted_alt(params, cl[r][1]) for r in cl}
+        usable = [r for r in cl if r > 1 and big[r] >= 8]              # long references admit no alternate under large parameters
+        assert big[1] >= 8 and len(usable) >= 7
+        picks = [usable[(len(usable) - 1) * x // 6] for x in range(7)]              # spread from 2 rows per lane to the most
+        roles = dict(b=(picks[1], picks[5]), c=(picks[2], picks[4]), d=(picks[0], picks[3], picks[6]))
+        big_lo = {r: rule_driver.largest_admitted_alt(params, cl[r][0]) for r in roles["d"]}
+        assert len(set(picks)) == 7 and all(big_lo[r] >= big[r] for r in big_lo)
+        fam[paired] = (cl, big, big_lo, roles)
+    for k, kind in enumerate(F.EXTREMAL_KINDS):
+        for paired in (False, True):
+            cl, big, big_lo, roles = fam[paired]
+            st = F.STRATEGIES[k % 4]
+            rnd = F.extremal("gap_middle", 1, 1)
+            pairs, strat, groups = [rnd, F.extremal(kind, cl[1][1], big[1])], [F.STRATEGIES[(k + 1) % 4], st], [(1, 0)]          # (a)
+            for r in roles["b"]:                                                                                           # (b)
+                q = len(pairs)
+                pairs += [F.extremal("gap_last", cl[r][1] - 3, big[r] // 4), F.extremal(kind, cl[r][1], big[r])]
+                strat += [F.STRATEGIES[(k + 2) % 4], st]; groups.append((q + 1, q))
+            for r in roles["c"]:                                                                                           # (c)
+                pairs.append(F.extremal(kind, cl[r][1], big[r])); strat.append(st); groups.append((len(pairs) - 1, None))
+            for r in roles["d"]:                                                                                       # (d)
+                q = len(pairs)
+                pairs += [F.extremal(F.EXTREMAL_KINDS[(k + 3) % 8], cl[r][0], big_lo[r]), F.extremal(kind, cl[r][1], big[r])]
+                strat += [F.STRATEGIES[(k + 3) % 4], st]; groups.append((q, q + 1))
+            adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, ("1" if paired else "0",), monkeypatch,
+                                  want=lambda p, g=groups: g)
+            assert all(adm)
+
+
+def test_frontier_at_the_lds_limit_of_the_alternate(sw_engine, sw_oracle, rule_driver, monkeypatch):
+    """alternates of 4095 and 4096 bases (two of them fill the LDS stage of a lane group) are admitted, 4097 are not, under
+    parameters whose scores allow all three; two 4096-base alternates in one lane group; one with a short partner"""
+    params = F.ORIGINAL_DEFAULT
+    pairs, strat, expect = [], [], []
+    for a, n in enumerate((1, 200, 2048)):
+        for b, m in enumerate((4095, 4096, 4097)):
+            for e in range(2):
+                pairs.append(F.extremal(F.EXTREMAL_KINDS[(3 * a + 2 * b + 5 * e) % 8], n, m)); strat.append(F.STRATEGIES[(a + b + e) % 4])
+                expect.append(m <= 4096)
+    adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, ("0", "1"), monkeypatch)
+    assert adm == expect
+    # references of 199 / 200 bases share a row class in both families, and so do 290 / 300; each class holds one lane group
+    pairs = [F.extremal("gap_middle", 200, 4096), F.extremal("all_mismatch", 199, 4096), F.extremal("gap_first", 290, 5), F.extremal("all_match", 300, 4096)]
+    adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, [10, 9, 12, 11], ("0", "1"), monkeypatch,
+                          want=lambda p: [(0, 1), (3, 2)])
+    assert all(adm)
+
+
+def test_frontier_pairs_in_many_chunks(sw_engine, sw_oracle, rule_driver, monkeypatch):
+    """largest-admitted pairs under a small arena: the chunk bound holds for the 16-bit layout at its largest"""
+    params = F.STANDARD_NGS
+    pairs, strat = [], []
+    for q in range(40):
+        n = (1000, 2048, 640, 64)[q % 4]
+        pairs.append(F.extremal(F.EXTREMAL_KINDS[q % 8], n, rule_driver.largest_admitted_alt(params, n))); strat.append(F.STRATEGIES[(q // 8) % 4])
+    monkeypatch.setenv("MGX_SW_ARENA_LIMIT", str(4 << 20))
+    adm = _frontier_batch(sw_engine, sw_oracle, rule_driver, params, pairs, strat, ("0",), monkeypatch)
+    assert all(adm) and sw_engine.stats()["n_launches"] >= 5
