@@ -61,9 +61,7 @@ struct Bin {
     bool strip = false;              // reads longer than 1024 bases: the strip-mined kernel, one test case per workgroup
 };
 
-}  // namespace
 
-namespace {
 // One device allocation + (for batches up to kStageLimit) a pinned host mirror of the same size.
 // Slabs are recycled through the context, so a stream of region-sized batches does no hipMalloc.
 struct Slab {
@@ -109,12 +107,12 @@ struct mgx_pairhmm_batch {
     uint32_t* d_rerun_count = nullptr;
     double* d_out = nullptr;
     std::vector<Job> host_jobs;    // only kept for unstaged (very large) batches
-    // whole-region form (mgx_pairhmm_region): normalise / filter epilogue over [n_reads][n_haps]
+    // whole-region form (mgx_pairhmm_regions): normalise / filter epilogue over every read's row of the output
     bool has_model = false;
-    uint32_t n_reads = 0, n_haps = 0;
+    uint32_t n_reads = 0;
     uint64_t* d_read_len = nullptr;
     uint8_t* d_keep = nullptr;
-    uint32_t *d_row_off = nullptr, *d_row_nh = nullptr;   // several regions in one batch: per-read output row
+    uint32_t *d_row_off = nullptr, *d_row_nh = nullptr;   // per read: where its row starts and how many haplotypes it holds
     size_t o_keep = 0;
     double log10_rate = 0, max_err = 0;
     hipEvent_t uploaded = nullptr;
@@ -391,335 +389,312 @@ void mgx_pairhmm_batch_destroy(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
 
 namespace {
 
-// Batch of every read against every haplotype (pair_read == pair_hap == NULL):
-// out[r * n_haps + h].  Host work is O(n_reads + n_haps); job descriptors are made on the device.
-int create_cross(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, mgx_pairhmm_batch* b,
-                 const uint8_t* mapq = nullptr, const mgx_read_model_t* model = nullptr) {
-    const uint64_t nr = in->n_reads, nh = in->n_haps;
-    const uint64_t n = nr * nh;
-    if (n > 0xFFFFFFF0ull) { set_error("more than 2^32 test cases in one batch"); return -E2BIG; }
-    b->n_pairs = n;
-    b->stats.n_pairs = n;
-    int rc;
-    uint64_t count[kBins] = {0};
-    std::vector<uint8_t> rbin(nr);
-    uint64_t sumR_bin[kBins] = {0}, sumH = 0;
-    uint32_t max_h = 0;
-    for (uint64_t r = 0; r < nr; ++r) {
-        const uint64_t R = in->read_off[r + 1] - in->read_off[r];
-        if (R == 0) { set_error("read %llu is empty", (unsigned long long)r); return -EINVAL; }
-        int G, RPL;
-        shape_of((uint32_t)std::min<uint64_t>(R, 0xFFFFFFFFull), &G, &RPL);
-        if (G == 0) { set_error("read %llu: read of %llu bases exceeds the %d-row limit", (unsigned long long)r, (unsigned long long)R, kMaxRowsStrip); return -E2BIG; }
-        rbin[r] = (uint8_t)bin_index(G, RPL);
-        count[rbin[r]] += nh;
-    }
-    std::vector<SeqRef> haps(nh);
-    for (uint64_t h = 0; h < nh; ++h) {
-        const uint64_t H = in->hap_off[h + 1] - in->hap_off[h];
-        if (H == 0) { set_error("haplotype %llu is empty", (unsigned long long)h); return -EINVAL; }
-        if (H > 0x7FFFFFF0ull) { set_error("haplotype too long"); return -E2BIG; }
-        haps[h] = SeqRef{in->hap_off[h], (uint32_t)H, (uint32_t)h};
-        sumH += H; max_h = std::max<uint32_t>(max_h, (uint32_t)H);
-    }
-    std::stable_sort(haps.begin(), haps.end(), [](const SeqRef& a, const SeqRef& b2) { return a.len > b2.len; });
-    int remap[kBins];
-    merge_small_bins(count, remap);
-    uint64_t reads_in[kBins] = {0}, rstart[kBins + 1] = {0};
-    for (uint64_t r = 0; r < nr; ++r) { rbin[r] = (uint8_t)remap[rbin[r]]; reads_in[rbin[r]]++; sumR_bin[rbin[r]] += in->read_off[r + 1] - in->read_off[r]; }
-    for (int k = 0; k < kBins; ++k) rstart[k + 1] = rstart[k] + reads_in[k];
-    // slab layout
-    const uint64_t read_bytes = in->read_off[nr], hap_bytes = in->hap_off[nh];
+// Where the arrays of a batch lie in its slab.  The inputs are written once (one H2D copy when staged through the
+// pinned mirror), [out | used | keep] is read back with one D2H copy, what follows is device scratch.  The pair-list
+// form writes its jobs on the host, first in the mirror; the cross-product form uploads the tables that the device
+// enumerates them from and keeps the jobs in scratch.
+struct SlabLayout {
+    // sizes: set by the caller
+    uint64_t n = 0, n_reads = 0, n_haps = 0, n_regions = 0, read_bytes = 0, hap_bytes = 0;
+    bool cross = false, model = false;
+    // offsets: set by lay_out_slab (the results' offsets go to the batch: o_out, o_used, o_keep)
+    size_t rtab = 0, rreg = 0, rpre = 0, gtab = 0, htab = 0;      // cross-product form: what the jobs are enumerated from
+    size_t jobs = 0, bases = 0, qual = 0, ins = 0, del = 0, gcp = 0, hap = 0;
+    size_t mapq = 0, rlen = 0, roff = 0, rnh = 0;                 // with a read model: per read, for the model and the epilogue
+    size_t rlist = 0, rcount = 0;
+    size_t pin_bytes = 0;                                         // the pinned mirror covers the inputs and the results only
+    bool staged = true;
+};
+
+// Decides the offsets, takes a slab of that size -- with a pinned mirror if always_stage or if inputs and results fit
+// kStageLimit -- and points the batch into it.
+int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_batch* b) {
     size_t off = 0;
-    const size_t o_rtab = off;  off = align_up(off + nr * sizeof(SeqRef));
-    const size_t o_htab = off;  off = align_up(off + nh * sizeof(SeqRef));
-    const size_t o_bases = off; off = align_up(off + read_bytes);
-    const size_t o_qual = off;  off = align_up(off + read_bytes);
-    const size_t o_ins = off;   off = align_up(off + read_bytes);
-    const size_t o_del = off;   off = align_up(off + read_bytes);
-    const size_t o_gcp = off;   off = align_up(off + read_bytes);
-    const size_t o_hap = off;   off = align_up(off + hap_bytes);
-    const size_t o_mapq = off;  off = align_up(off + (model ? nr : 0));
-    const size_t o_rlen = off;  off = align_up(off + (model ? nr * sizeof(uint64_t) : 0));
+    auto take = [&off](size_t bytes) { const size_t at = off; off = align_up(off + bytes); return at; };
+    const uint64_t n = L->n, per_read = L->model ? L->n_reads : 0;
+    if (L->cross) {
+        L->rtab = take(L->n_reads * sizeof(SeqRef));
+        L->rreg = take(L->n_reads * sizeof(uint32_t));
+        L->rpre = take((L->n_reads + 1) * sizeof(uint32_t));
+        L->gtab = take(L->n_regions * sizeof(RegionRef));
+        L->htab = take(L->n_haps * sizeof(SeqRef));
+    } else {
+        L->jobs = take(n * sizeof(Job));
+    }
+    L->bases = take(L->read_bytes);
+    L->qual = take(L->read_bytes);
+    L->ins = take(L->read_bytes);
+    L->del = take(L->read_bytes);
+    L->gcp = take(L->read_bytes);
+    L->hap = take(L->hap_bytes);
+    L->mapq = take(per_read);
+    L->rlen = take(per_read * sizeof(uint64_t));
+    L->roff = take(per_read * sizeof(uint32_t));
+    L->rnh = take(per_read * sizeof(uint32_t));
     b->in_bytes = off;
-    b->o_out = off;             off = align_up(off + n * sizeof(double));
-    b->o_used = off;            off = align_up(off + n);
-    b->o_keep = off;            off = align_up(off + (model ? nr : 0));
+    b->o_out = take(n * sizeof(double));
+    b->o_used = take(n);
+    b->o_keep = take(per_read);
     b->result_bytes = off - b->o_out;
-    const size_t pin_bytes = off;              // the pinned mirror covers the inputs and the results only
-    const size_t o_jobs = off;  off = align_up(off + n * sizeof(Job));
-    const size_t o_rlist = off; off = align_up(off + 2 * n * sizeof(uint32_t));   // fp64 re-run lists | exact-tier list
-    const size_t o_rcount = off; off = align_up(off + 64 * sizeof(uint32_t));
-    if ((rc = acquire_slab(c, off, pin_bytes, &b->slab))) return rc;
-    uint8_t* dv = b->slab.dev; uint8_t* pin = b->slab.pin;
-    b->d_jobs = (Job*)(dv + o_jobs);
-    b->d_bases = dv + o_bases; b->d_qual = dv + o_qual; b->d_ins = dv + o_ins; b->d_del = dv + o_del;
-    b->d_gcp = dv + o_gcp; b->d_hap = dv + o_hap;
+    L->pin_bytes = off;
+    if (L->cross) L->jobs = take(n * sizeof(Job));
+    L->rlist = take(2 * n * sizeof(uint32_t));       // fp64 re-run lists | exact-tier list
+    L->rcount = take(64 * sizeof(uint32_t));
+    L->staged = always_stage || L->pin_bytes <= kStageLimit;
+    if (const int rc = acquire_slab(c, off, L->staged ? L->pin_bytes : 0, &b->slab)) return rc;
+    uint8_t* dv = b->slab.dev;
+    b->d_jobs = (Job*)(dv + L->jobs);
+    b->d_bases = dv + L->bases; b->d_qual = dv + L->qual; b->d_ins = dv + L->ins; b->d_del = dv + L->del;
+    b->d_gcp = dv + L->gcp; b->d_hap = dv + L->hap;
     b->d_out = (double*)(dv + b->o_out); b->d_used = dv + b->o_used;
-    b->d_rerun_list = (uint32_t*)(dv + o_rlist); b->d_rerun_count = (uint32_t*)(dv + o_rcount);
-    SeqRef* rtab = (SeqRef*)(pin + o_rtab);
-    {
-        uint64_t cur[kBins];
-        for (int k = 0; k < kBins; ++k) cur[k] = rstart[k];
-        for (uint64_t r = 0; r < nr; ++r)
-            rtab[cur[rbin[r]]++] = SeqRef{in->read_off[r], (uint32_t)(in->read_off[r + 1] - in->read_off[r]), (uint32_t)r};
+    b->d_rerun_list = (uint32_t*)(dv + L->rlist); b->d_rerun_count = (uint32_t*)(dv + L->rcount);
+    if (L->model) {
+        b->d_read_len = (uint64_t*)(dv + L->rlen); b->d_keep = dv + b->o_keep;
+        b->d_row_off = (uint32_t*)(dv + L->roff); b->d_row_nh = (uint32_t*)(dv + L->rnh);
     }
-    memcpy(pin + o_htab, haps.data(), nh * sizeof(SeqRef));
-    memcpy(pin + o_bases, in->bases, read_bytes); memcpy(pin + o_qual, in->qual, read_bytes);
-    memcpy(pin + o_ins, in->ins, read_bytes);     memcpy(pin + o_del, in->del, read_bytes);
-    memcpy(pin + o_gcp, in->gcp, read_bytes);     memcpy(pin + o_hap, in->hap_bases, hap_bytes);
-    hipStream_t s = c->copy;
-    if (model) {
-        for (uint64_t r = 0; r < nr; ++r) {
-            ((uint64_t*)(pin + o_rlen))[r] = in->read_off[r + 1] - in->read_off[r];
-        }
-        memcpy(pin + o_mapq, mapq, nr);
-        b->has_model = true; b->n_reads = (uint32_t)nr; b->n_haps = (uint32_t)nh;
-        b->d_read_len = (uint64_t*)(dv + o_rlen); b->d_keep = dv + b->o_keep;
-        b->log10_rate = model->log10_mismapping_rate; b->max_err = model->max_error_per_base;
-    }
-    HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
-    if (model) {
-        // modifyReadQualities + gap continuation penalties, in place on the uploaded arrays
-        ReadModel rm{};
-        rm.rate_factor = model->pcr_rate_factor; rm.bq_threshold = model->base_quality_threshold;
-        rm.constant_gcp = model->constant_gcp;
-        for (int i = 0; i <= 20; ++i) {      // PairHMMLikelihoodCalculationEngine.cpp:45-61
-            const double d = 40.0 - std::exp((double)i / ((double)std::max(rm.rate_factor, 1) * M_PI));
-            const int v = (d > 0.0 ? (int)(d + 0.5) : (int)(d - 0.5)) + 1;
-            rm.pcr_cache[i] = (uint8_t)(char)std::max(10, v);
-        }
-        hipLaunchKernelGGL(pairhmm_read_model, dim3((uint32_t)nr), dim3(128), 0, s, (const SeqRef*)(dv + o_rtab),
-                           b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, (const uint8_t*)(dv + o_mapq), rm);
-    }
-    uint64_t job_begin = 0;
-    for (int k = 0; k < kBins; ++k) {
-        if (!reads_in[k]) continue;
-        Bin bin;
-        bin_shape(k, &bin);
-        bin.job_begin = (uint32_t)job_begin;
-        bin.job_count = (uint32_t)(reads_in[k] * nh);
-        bin.max_h = max_h;
-        bin.cells = sumR_bin[k] * sumH;
-        bin.alg_bytes = 5 * sumR_bin[k] * nh + reads_in[k] * (sumH + 4 * nh);
-        if ((rc = finalize_bin(bin, c->n_cu))) return rc;
-        hipLaunchKernelGGL(pairhmm_make_jobs, dim3((bin.job_count + 255) / 256), dim3(256), 0, s,
-                           (const SeqRef*)(dv + o_rtab) + rstart[k], (const SeqRef*)(dv + o_htab), (uint32_t)nh,
-                           bin.job_count, b->d_jobs + job_begin);
-        b->stats.cells += bin.cells; b->stats.alg_bytes += bin.alg_bytes;
-        b->bins.push_back(bin);
-        job_begin += bin.job_count;
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->uploaded, s));
     return 0;
 }
 
-// Row F1: the cross-product test cases of several regions in one batch -- one upload, one set of
-// launches, one download.  Host work is linear in reads + haplotypes (the test cases are enumerated
-// on the device), so coalescing a thousand small regions costs microseconds, not a pair list.
-int create_cross_multi(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regs, mgx_pairhmm_batch* b,
-                       std::vector<uint64_t>* out_base, const uint8_t* const* mapq = nullptr, const mgx_read_model_t* model = nullptr) {
+// modifyReadQualities + gap continuation penalties as the device applies them (pairhmm_read_model)
+ReadModel make_read_model(const mgx_read_model_t& model) {
+    ReadModel rm{};
+    rm.rate_factor = model.pcr_rate_factor; rm.bq_threshold = model.base_quality_threshold;
+    rm.constant_gcp = model.constant_gcp;
+    for (int i = 0; i <= 20; ++i) {      // PairHMMLikelihoodCalculationEngine.cpp:45-61
+        const double d = 40.0 - std::exp((double)i / ((double)std::max(rm.rate_factor, 1) * M_PI));
+        const int v = (d > 0.0 ? (int)(d + 0.5) : (int)(d - 0.5)) + 1;
+        rm.pcr_cache[i] = (uint8_t)(char)std::max(10, v);
+    }
+    return rm;
+}
+
+// Row F1: the cross-product test cases (pair_read == pair_hap == NULL: every read against every haplotype,
+// out[r * n_haps + h]) of one or several regions in one batch -- one upload, one set of launches, one download.
+// Host work is linear in reads + haplotypes (the test cases are enumerated on the device), so coalescing a
+// thousand small regions costs microseconds, not a pair list.
+struct CrossRead { uint64_t off; uint32_t len, region; uint8_t bin; };
+struct CrossPlan {
     uint64_t nr = 0, nh = 0, n = 0, read_bytes = 0, hap_bytes = 0;
+    std::vector<CrossRead> reads;          // in global read order: offsets rebased to the batch's concatenated arrays
+    std::vector<RegionRef> regions;
+    std::vector<SeqRef> haps;              // region by region, each in stable order of decreasing length
+    uint32_t max_h = 0;
+    uint64_t reads_in[kBins] = {0}, rstart[kBins + 1] = {0}, jobs_in[kBins] = {0}, cells_in[kBins] = {0}, bytes_in[kBins] = {0};
+};
+
+// totals of the batch, and where every region's [reads][haps] block starts in the output
+int cross_totals(uint32_t n_regions, const mgx_pairhmm_input_t* regs, CrossPlan* p, std::vector<uint64_t>* out_base) {
     out_base->assign(n_regions + 1, 0);
     for (uint32_t g = 0; g < n_regions; ++g) {
         const mgx_pairhmm_input_t& in = regs[g];
         if (in.pair_read || in.pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
-        nr += in.n_reads; nh += in.n_haps; n += in.n_reads * in.n_haps;
-        if (in.n_reads) read_bytes += in.read_off[in.n_reads] - in.read_off[0];
-        if (in.n_haps) hap_bytes += in.hap_off[in.n_haps] - in.hap_off[0];
-        (*out_base)[g + 1] = n;
+        p->nr += in.n_reads; p->nh += in.n_haps; p->n += in.n_reads * in.n_haps;
+        if (in.n_reads) p->read_bytes += in.read_off[in.n_reads] - in.read_off[0];
+        if (in.n_haps) p->hap_bytes += in.hap_off[in.n_haps] - in.hap_off[0];
+        (*out_base)[g + 1] = p->n;
     }
-    if (n > 0xFFFFFFF0ull || nr > 0xFFFFFFF0ull) { set_error("more than 2^32 test cases in one batch"); return -E2BIG; }
-    b->n_pairs = n;
-    b->stats.n_pairs = n;
-    if (n == 0) return 0;
-    int rc;
-    // global read table: bin, length, region; job counts per bin
-    struct RInfo { uint64_t off; uint32_t len, region; uint8_t bin; };
-    std::vector<RInfo> rinfo(nr);
-    std::vector<RegionRef> rtab_regions(n_regions);
-    std::vector<SeqRef> haps(nh);
-    uint64_t count[kBins] = {0};
-    uint32_t max_h = 0;
-    {
-        uint64_t r_at = 0, h_at = 0, rb = 0, hb = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            const mgx_pairhmm_input_t& in = regs[g];
-            RegionRef& R = rtab_regions[g];
-            R.hap_begin = (uint32_t)h_at; R.n_haps = (uint32_t)in.n_haps; R.read_base = (uint32_t)r_at; R.out_base = (uint32_t)(*out_base)[g];
-            for (uint64_t h = 0; h < in.n_haps; ++h) {
-                const uint64_t H = in.hap_off[h + 1] - in.hap_off[h];
-                if (H == 0) { set_error("region %u: haplotype %llu is empty", g, (unsigned long long)h); return -EINVAL; }
-                if (H > 0x7FFFFFF0ull) { set_error("haplotype too long"); return -E2BIG; }
-                haps[h_at + h] = SeqRef{hb + (in.hap_off[h] - in.hap_off[0]), (uint32_t)H, (uint32_t)h};
-                max_h = std::max<uint32_t>(max_h, (uint32_t)H);
-            }
-            std::stable_sort(haps.begin() + h_at, haps.begin() + h_at + in.n_haps, [](const SeqRef& a, const SeqRef& b2) { return a.len > b2.len; });
-            for (uint64_t r = 0; r < in.n_reads; ++r) {
-                const uint64_t Rl = in.read_off[r + 1] - in.read_off[r];
-                if (Rl == 0) { set_error("region %u: read %llu is empty", g, (unsigned long long)r); return -EINVAL; }
-                int G, RPL;
-                shape_of((uint32_t)std::min<uint64_t>(Rl, 0xFFFFFFFFull), &G, &RPL);
-                if (G == 0) { set_error("region %u: read of %llu bases exceeds the %d-row limit", g, (unsigned long long)Rl, kMaxRowsStrip); return -E2BIG; }
-                RInfo& ri = rinfo[r_at + r];
-                ri.off = rb + (in.read_off[r] - in.read_off[0]); ri.len = (uint32_t)Rl; ri.region = g; ri.bin = (uint8_t)bin_index(G, RPL);
-                count[ri.bin] += in.n_haps;
-            }
-            if (in.n_reads) rb += in.read_off[in.n_reads] - in.read_off[0];
-            if (in.n_haps) hb += in.hap_off[in.n_haps] - in.hap_off[0];
-            r_at += in.n_reads; h_at += in.n_haps;
+    if (p->n > 0xFFFFFFF0ull || p->nr > 0xFFFFFFF0ull) { set_error("more than 2^32 test cases in one batch"); return -E2BIG; }
+    return 0;
+}
+
+// read, region and haplotype tables; job counts per read-length class in count[]
+int cross_tables(uint32_t n_regions, const mgx_pairhmm_input_t* regs, const std::vector<uint64_t>& out_base, CrossPlan* p,
+                 uint64_t (&count)[kBins]) {
+    p->reads.resize(p->nr); p->regions.resize(n_regions); p->haps.resize(p->nh);
+    uint64_t r_at = 0, h_at = 0, rb = 0, hb = 0;
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        const mgx_pairhmm_input_t& in = regs[g];
+        RegionRef& R = p->regions[g];
+        R.hap_begin = (uint32_t)h_at; R.n_haps = (uint32_t)in.n_haps; R.read_base = (uint32_t)r_at; R.out_base = (uint32_t)out_base[g];
+        for (uint64_t h = 0; h < in.n_haps; ++h) {
+            const uint64_t H = in.hap_off[h + 1] - in.hap_off[h];
+            if (H == 0) { set_error("region %u: haplotype %llu is empty", g, (unsigned long long)h); return -EINVAL; }
+            if (H > 0x7FFFFFF0ull) { set_error("haplotype too long"); return -E2BIG; }
+            p->haps[h_at + h] = SeqRef{hb + (in.hap_off[h] - in.hap_off[0]), (uint32_t)H, (uint32_t)h};
+            p->max_h = std::max<uint32_t>(p->max_h, (uint32_t)H);
         }
+        std::stable_sort(p->haps.begin() + h_at, p->haps.begin() + h_at + in.n_haps, [](const SeqRef& a, const SeqRef& b2) { return a.len > b2.len; });
+        for (uint64_t r = 0; r < in.n_reads; ++r) {
+            const uint64_t Rl = in.read_off[r + 1] - in.read_off[r];
+            if (Rl == 0) { set_error("region %u: read %llu is empty", g, (unsigned long long)r); return -EINVAL; }
+            int G, RPL;
+            shape_of((uint32_t)std::min<uint64_t>(Rl, 0xFFFFFFFFull), &G, &RPL);
+            if (G == 0) { set_error("region %u: read of %llu bases exceeds the %d-row limit", g, (unsigned long long)Rl, kMaxRowsStrip); return -E2BIG; }
+            CrossRead& ri = p->reads[r_at + r];
+            ri.off = rb + (in.read_off[r] - in.read_off[0]); ri.len = (uint32_t)Rl; ri.region = g; ri.bin = (uint8_t)bin_index(G, RPL);
+            count[ri.bin] += in.n_haps;
+        }
+        if (in.n_reads) rb += in.read_off[in.n_reads] - in.read_off[0];
+        if (in.n_haps) hb += in.hap_off[in.n_haps] - in.hap_off[0];
+        r_at += in.n_reads; h_at += in.n_haps;
     }
+    return 0;
+}
+
+// folds the small classes and sums, per class, reads, jobs, cells and bytes
+void cross_bins(CrossPlan* p, uint64_t (&count)[kBins]) {
     int remap[kBins];
     merge_small_bins(count, remap);
-    uint64_t reads_in[kBins] = {0}, rstart[kBins + 1] = {0}, jobs_in[kBins] = {0}, cells_in[kBins] = {0}, bytes_in[kBins] = {0};
-    std::vector<uint64_t> sumH(n_regions, 0);
-    for (uint32_t g = 0; g < n_regions; ++g)
-        for (uint32_t h = 0; h < rtab_regions[g].n_haps; ++h) sumH[g] += haps[rtab_regions[g].hap_begin + h].len;
-    for (uint64_t r = 0; r < nr; ++r) {
-        RInfo& ri = rinfo[r];
+    std::vector<uint64_t> sumH(p->regions.size(), 0);
+    for (size_t g = 0; g < p->regions.size(); ++g)
+        for (uint32_t h = 0; h < p->regions[g].n_haps; ++h) sumH[g] += p->haps[p->regions[g].hap_begin + h].len;
+    for (CrossRead& ri : p->reads) {
         ri.bin = (uint8_t)remap[ri.bin];
-        const RegionRef& R = rtab_regions[ri.region];
-        reads_in[ri.bin]++; jobs_in[ri.bin] += R.n_haps; cells_in[ri.bin] += (uint64_t)ri.len * sumH[ri.region];
-        bytes_in[ri.bin] += 5ull * ri.len * R.n_haps + sumH[ri.region] + 4ull * R.n_haps;
+        const RegionRef& R = p->regions[ri.region];
+        p->reads_in[ri.bin]++; p->jobs_in[ri.bin] += R.n_haps; p->cells_in[ri.bin] += (uint64_t)ri.len * sumH[ri.region];
+        p->bytes_in[ri.bin] += 5ull * ri.len * R.n_haps + sumH[ri.region] + 4ull * R.n_haps;
     }
-    for (int k = 0; k < kBins; ++k) rstart[k + 1] = rstart[k] + reads_in[k];
-    // slab layout
-    size_t off = 0;
-    const size_t o_rtab = off;  off = align_up(off + nr * sizeof(SeqRef));
-    const size_t o_rreg = off;  off = align_up(off + nr * sizeof(uint32_t));
-    const size_t o_rpre = off;  off = align_up(off + (nr + 1) * sizeof(uint32_t));
-    const size_t o_gtab = off;  off = align_up(off + n_regions * sizeof(RegionRef));
-    const size_t o_htab = off;  off = align_up(off + nh * sizeof(SeqRef));
-    const size_t o_bases = off; off = align_up(off + read_bytes);
-    const size_t o_qual = off;  off = align_up(off + read_bytes);
-    const size_t o_ins = off;   off = align_up(off + read_bytes);
-    const size_t o_del = off;   off = align_up(off + read_bytes);
-    const size_t o_gcp = off;   off = align_up(off + read_bytes);
-    const size_t o_hap = off;   off = align_up(off + hap_bytes);
-    const size_t o_mapq = off;  off = align_up(off + (model ? nr : 0));
-    const size_t o_rlen = off;  off = align_up(off + (model ? nr * sizeof(uint64_t) : 0));
-    const size_t o_roff = off;  off = align_up(off + (model ? nr * sizeof(uint32_t) : 0));
-    const size_t o_rnh = off;   off = align_up(off + (model ? nr * sizeof(uint32_t) : 0));
-    b->in_bytes = off;
-    b->o_out = off;             off = align_up(off + n * sizeof(double));
-    b->o_used = off;            off = align_up(off + n);
-    b->o_keep = off;            off = align_up(off + (model ? nr : 0));
-    b->result_bytes = off - b->o_out;
-    const size_t pin_bytes = off;              // the pinned mirror covers the inputs and the results only
-    const size_t o_jobs = off;  off = align_up(off + n * sizeof(Job));
-    const size_t o_rlist = off; off = align_up(off + 2 * n * sizeof(uint32_t));   // fp64 re-run lists | exact-tier list
-    const size_t o_rcount = off; off = align_up(off + 64 * sizeof(uint32_t));
-    if ((rc = acquire_slab(c, off, pin_bytes, &b->slab))) return rc;
+    for (int k = 0; k < kBins; ++k) p->rstart[k + 1] = p->rstart[k] + p->reads_in[k];
+}
+
+// the enumeration tables and the sequences, into the pinned mirror
+void cross_stage(const CrossPlan& p, uint32_t n_regions, const mgx_pairhmm_input_t* regs, const SlabLayout& L, uint8_t* pin) {
+    SeqRef* rtab = (SeqRef*)(pin + L.rtab);
+    uint32_t* rreg = (uint32_t*)(pin + L.rreg);
+    uint32_t* rpre = (uint32_t*)(pin + L.rpre);
+    uint64_t cur[kBins];
+    for (int k = 0; k < kBins; ++k) cur[k] = p.rstart[k];
+    for (uint64_t r = 0; r < p.nr; ++r) {          // read table in (class, input) order
+        const CrossRead& ri = p.reads[r];
+        const uint64_t at = cur[ri.bin]++;
+        rtab[at] = SeqRef{ri.off, ri.len, (uint32_t)r};
+        rreg[at] = ri.region;
+    }
+    uint32_t run = 0;
+    for (uint64_t at = 0; at < p.nr; ++at) { rpre[at] = run; run += p.regions[rreg[at]].n_haps; }
+    rpre[p.nr] = run;
+    memcpy(pin + L.gtab, p.regions.data(), n_regions * sizeof(RegionRef));
+    memcpy(pin + L.htab, p.haps.data(), p.nh * sizeof(SeqRef));
+    size_t rb = 0, hb = 0;
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        const mgx_pairhmm_input_t& in = regs[g];
+        if (in.n_reads) {
+            const uint64_t o0 = in.read_off[0], len = in.read_off[in.n_reads] - o0;
+            memcpy(pin + L.bases + rb, in.bases + o0, len); memcpy(pin + L.qual + rb, in.qual + o0, len);
+            memcpy(pin + L.ins + rb, in.ins + o0, len);     memcpy(pin + L.del + rb, in.del + o0, len);
+            memcpy(pin + L.gcp + rb, in.gcp + o0, len);
+            rb += len;
+        }
+        if (in.n_haps) {
+            const uint64_t o0 = in.hap_off[0], len = in.hap_off[in.n_haps] - o0;
+            memcpy(pin + L.hap + hb, in.hap_bases + o0, len);
+            hb += len;
+        }
+    }
+}
+
+// per read, in global read order: MAPQ, length, and its row of the output
+int cross_stage_model(uint32_t n_regions, const mgx_pairhmm_input_t* regs, const uint8_t* const* mapq,
+                      const std::vector<uint64_t>& out_base, const SlabLayout& L, uint8_t* pin) {
+    uint64_t* rlen = (uint64_t*)(pin + L.rlen);
+    uint32_t* roff = (uint32_t*)(pin + L.roff);
+    uint32_t* rnh = (uint32_t*)(pin + L.rnh);
+    uint64_t r_at = 0;
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        const mgx_pairhmm_input_t& in = regs[g];
+        if (in.n_reads && !mapq[g]) { set_error("region %u: mapq is NULL", g); return -EINVAL; }
+        for (uint64_t r = 0; r < in.n_reads; ++r) {
+            rlen[r_at + r] = in.read_off[r + 1] - in.read_off[r];
+            roff[r_at + r] = (uint32_t)(out_base[g] + r * in.n_haps);
+            rnh[r_at + r] = (uint32_t)in.n_haps;
+        }
+        if (in.n_reads) memcpy(pin + L.mapq + r_at, mapq[g], in.n_reads);
+        r_at += in.n_reads;
+    }
+    return 0;
+}
+
+int create_cross(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regs, mgx_pairhmm_batch* b,
+                 std::vector<uint64_t>* out_base, const uint8_t* const* mapq = nullptr, const mgx_read_model_t* model = nullptr) {
+    CrossPlan p;
+    int rc;
+    if ((rc = cross_totals(n_regions, regs, &p, out_base))) return rc;
+    b->n_pairs = p.n;
+    b->stats.n_pairs = p.n;
+    if (p.n == 0) return 0;
+    uint64_t count[kBins] = {0};
+    if ((rc = cross_tables(n_regions, regs, *out_base, &p, count))) return rc;
+    cross_bins(&p, count);
+    SlabLayout L;
+    L.n = p.n; L.n_reads = p.nr; L.n_haps = p.nh; L.n_regions = n_regions; L.read_bytes = p.read_bytes; L.hap_bytes = p.hap_bytes;
+    L.cross = true; L.model = model != nullptr;
+    if ((rc = lay_out_slab(c, true, &L, b))) return rc;
     uint8_t* dv = b->slab.dev; uint8_t* pin = b->slab.pin;
-    b->d_jobs = (Job*)(dv + o_jobs);
-    b->d_bases = dv + o_bases; b->d_qual = dv + o_qual; b->d_ins = dv + o_ins; b->d_del = dv + o_del;
-    b->d_gcp = dv + o_gcp; b->d_hap = dv + o_hap;
-    b->d_out = (double*)(dv + b->o_out); b->d_used = dv + b->o_used;
-    b->d_rerun_list = (uint32_t*)(dv + o_rlist); b->d_rerun_count = (uint32_t*)(dv + o_rcount);
-    SeqRef* rtab = (SeqRef*)(pin + o_rtab);
-    uint32_t* rreg = (uint32_t*)(pin + o_rreg);
-    uint32_t* rpre = (uint32_t*)(pin + o_rpre);
-    {
-        uint64_t cur[kBins];
-        for (int k = 0; k < kBins; ++k) cur[k] = rstart[k];
-        for (uint64_t r = 0; r < nr; ++r) {
-            const RInfo& ri = rinfo[r];
-            const uint64_t at = cur[ri.bin]++;
-            rtab[at] = SeqRef{ri.off, ri.len, (uint32_t)r};
-            rreg[at] = ri.region;
-        }
-        uint32_t run = 0;
-        for (uint64_t at = 0; at < nr; ++at) { rpre[at] = run; run += rtab_regions[rreg[at]].n_haps; }
-        rpre[nr] = run;
-    }
-    memcpy(pin + o_gtab, rtab_regions.data(), n_regions * sizeof(RegionRef));
-    memcpy(pin + o_htab, haps.data(), nh * sizeof(SeqRef));
-    {
-        size_t rb = 0, hb = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            const mgx_pairhmm_input_t& in = regs[g];
-            if (in.n_reads) {
-                const uint64_t o0 = in.read_off[0], len = in.read_off[in.n_reads] - o0;
-                memcpy(pin + o_bases + rb, in.bases + o0, len); memcpy(pin + o_qual + rb, in.qual + o0, len);
-                memcpy(pin + o_ins + rb, in.ins + o0, len);     memcpy(pin + o_del + rb, in.del + o0, len);
-                memcpy(pin + o_gcp + rb, in.gcp + o0, len);
-                rb += len;
-            }
-            if (in.n_haps) {
-                const uint64_t o0 = in.hap_off[0], len = in.hap_off[in.n_haps] - o0;
-                memcpy(pin + o_hap + hb, in.hap_bases + o0, len);
-                hb += len;
-            }
-        }
-    }
+    cross_stage(p, n_regions, regs, L, pin);
     hipStream_t s = c->copy;
     if (model) {
-        // per read, in global read order: MAPQ, length, and its row of the output
-        uint64_t* rlen = (uint64_t*)(pin + o_rlen);
-        uint32_t* roff = (uint32_t*)(pin + o_roff);
-        uint32_t* rnh = (uint32_t*)(pin + o_rnh);
-        uint64_t r_at = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            const mgx_pairhmm_input_t& in = regs[g];
-            if (in.n_reads && !mapq[g]) { set_error("region %u: mapq is NULL", g); return -EINVAL; }
-            for (uint64_t r = 0; r < in.n_reads; ++r) {
-                const uint64_t len = in.read_off[r + 1] - in.read_off[r];
-                rlen[r_at + r] = len;
-                roff[r_at + r] = (uint32_t)((*out_base)[g] + r * in.n_haps);
-                rnh[r_at + r] = (uint32_t)in.n_haps;
-            }
-            if (in.n_reads) memcpy(pin + o_mapq + r_at, mapq[g], in.n_reads);
-            r_at += in.n_reads;
-        }
-        b->has_model = true; b->n_reads = (uint32_t)nr; b->n_haps = 0;
-        b->d_read_len = (uint64_t*)(dv + o_rlen); b->d_keep = dv + b->o_keep;
-        b->d_row_off = (uint32_t*)(dv + o_roff); b->d_row_nh = (uint32_t*)(dv + o_rnh);
+        if ((rc = cross_stage_model(n_regions, regs, mapq, *out_base, L, pin))) return rc;
+        b->has_model = true; b->n_reads = (uint32_t)p.nr;
         b->log10_rate = model->log10_mismapping_rate; b->max_err = model->max_error_per_base;
     }
     HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
-    if (model) {
-        ReadModel rm{};
-        rm.rate_factor = model->pcr_rate_factor; rm.bq_threshold = model->base_quality_threshold;
-        rm.constant_gcp = model->constant_gcp;
-        for (int i = 0; i <= 20; ++i) {      // PairHMMLikelihoodCalculationEngine.cpp:45-61
-            const double d = 40.0 - std::exp((double)i / ((double)std::max(rm.rate_factor, 1) * M_PI));
-            const int v = (d > 0.0 ? (int)(d + 0.5) : (int)(d - 0.5)) + 1;
-            rm.pcr_cache[i] = (uint8_t)(char)std::max(10, v);
-        }
-        hipLaunchKernelGGL(pairhmm_read_model, dim3((uint32_t)nr), dim3(128), 0, s, (const SeqRef*)(dv + o_rtab),
-                           b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, (const uint8_t*)(dv + o_mapq), rm);
-    }
+    if (model)      // modifyReadQualities + gap continuation penalties, in place on the uploaded arrays
+        hipLaunchKernelGGL(pairhmm_read_model, dim3((uint32_t)p.nr), dim3(128), 0, s, (const SeqRef*)(dv + L.rtab),
+                           b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, (const uint8_t*)(dv + L.mapq), make_read_model(*model));
     uint64_t job_begin = 0;
     for (int k = 0; k < kBins; ++k) {
-        if (!reads_in[k]) continue;
+        if (!p.reads_in[k]) continue;
         Bin bin;
         bin_shape(k, &bin);
         bin.job_begin = (uint32_t)job_begin;
-        bin.job_count = (uint32_t)jobs_in[k];
-        bin.max_h = max_h;
-        bin.cells = cells_in[k];
-        bin.alg_bytes = bytes_in[k];
+        bin.job_count = (uint32_t)p.jobs_in[k];
+        bin.max_h = p.max_h;
+        bin.cells = p.cells_in[k];
+        bin.alg_bytes = p.bytes_in[k];
         if ((rc = finalize_bin(bin, c->n_cu))) return rc;
         b->stats.cells += bin.cells; b->stats.alg_bytes += bin.alg_bytes;
         b->bins.push_back(bin);
         job_begin += bin.job_count;
     }
     // one enumeration launch for all bins: jobs are laid out in read-table order, which is bin order
-    hipLaunchKernelGGL(pairhmm_make_jobs_multi, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const SeqRef*)(dv + o_rtab),
-                       (const uint32_t*)(dv + o_rreg), (const uint32_t*)(dv + o_rpre), (uint32_t)nr, (const RegionRef*)(dv + o_gtab),
-                       (const SeqRef*)(dv + o_htab), (uint32_t)n, b->d_jobs);
+    hipLaunchKernelGGL(pairhmm_make_jobs_multi, dim3((uint32_t)((p.n + 255) / 256)), dim3(256), 0, s, (const SeqRef*)(dv + L.rtab),
+                       (const uint32_t*)(dv + L.rreg), (const uint32_t*)(dv + L.rpre), (uint32_t)p.nr, (const RegionRef*)(dv + L.gtab),
+                       (const SeqRef*)(dv + L.htab), (uint32_t)p.n, b->d_jobs);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(b->uploaded, s));
     return 0;
 }
 
-}  // namespace
-
-namespace {
+// Upload of a pair-list batch: one copy out of the pinned mirror, or (very large batches) one per array.
+int upload_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, const SlabLayout& L, const Job* jobs,
+                 mgx_pairhmm_batch* b) {
+    const uint64_t read_bytes = L.read_bytes, hap_bytes = L.hap_bytes;
+    uint8_t* dv = b->slab.dev;
+    hipStream_t s = c->copy;
+    if (L.staged) {
+        uint8_t* pin = b->slab.pin;
+        if (plan) {
+            mgx::pack_copy(in, *plan, pin + L.bases, pin + L.qual, pin + L.ins, pin + L.del, pin + L.gcp, pin + L.hap);
+        } else if (read_bytes + hap_bytes < (32u << 20)) {
+            memcpy(pin + L.bases, in->bases, read_bytes); memcpy(pin + L.qual, in->qual, read_bytes);
+            memcpy(pin + L.ins, in->ins, read_bytes);     memcpy(pin + L.del, in->del, read_bytes);
+            memcpy(pin + L.gcp, in->gcp, read_bytes);     memcpy(pin + L.hap, in->hap_bases, hap_bytes);
+        } else {
+            // a large one-shot batch: the six arrays are staged by six threads (one core copies ~10 GB/s)
+            const void* src[6] = {in->bases, in->qual, in->ins, in->del, in->gcp, in->hap_bases};
+            uint8_t* dst[6] = {pin + L.bases, pin + L.qual, pin + L.ins, pin + L.del, pin + L.gcp, pin + L.hap};
+            const size_t len[6] = {(size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)hap_bytes};
+            std::thread th[6];
+            for (int k = 0; k < 6; ++k) th[k] = std::thread([=] { memcpy(dst[k], src[k], len[k]); });
+            for (auto& t : th) t.join();
+        }
+        HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(b->d_jobs, jobs, L.n * sizeof(Job), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_bases, in->bases, read_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_qual, in->qual, read_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_ins, in->ins, read_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_del, in->del, read_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_gcp, in->gcp, read_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->d_hap, in->hap_bases, hap_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));          // the caller's buffers may go away after we return
+        b->host_jobs.clear(); b->host_jobs.shrink_to_fit();
+    }
+    HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->uploaded, s));       // batch_run makes the compute stream wait on this
+    return 0;
+}
 
 // Pair-list batch.  plan == nullptr: the test cases of `in` with its read / haplotype arrays copied as
 // they are.  plan != nullptr: test cases [plan->lo, plan->hi) of `in`, only the sequences they reference
@@ -766,32 +741,11 @@ int create_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::Pac
     }
     // ---- one slab for everything; layout decided before the jobs are written so that they can be
     //      built directly in the pinned mirror
-    const uint64_t read_bytes = roff[n_reads];
-    const uint64_t hap_bytes = hoff[n_haps];
-    size_t off = 0;
-    const size_t o_jobs = off;  off = align_up(off + n * sizeof(Job));
-    const size_t o_bases = off; off = align_up(off + read_bytes);
-    const size_t o_qual = off;  off = align_up(off + read_bytes);
-    const size_t o_ins = off;   off = align_up(off + read_bytes);
-    const size_t o_del = off;   off = align_up(off + read_bytes);
-    const size_t o_gcp = off;   off = align_up(off + read_bytes);
-    const size_t o_hap = off;   off = align_up(off + hap_bytes);
-    b->in_bytes = off;
-    b->o_out = off;             off = align_up(off + n * sizeof(double));
-    b->o_used = off;            off = align_up(off + n);
-    b->result_bytes = off - b->o_out;
-    const size_t o_rlist = off; off = align_up(off + 2 * n * sizeof(uint32_t));   // fp64 re-run lists | exact-tier list
-    const size_t o_rcount = off; off = align_up(off + 64 * sizeof(uint32_t));
-    const bool staged = plan || o_rlist <= kStageLimit;
-    if ((rc = acquire_slab(c, off, staged ? o_rlist : 0, &b->slab))) return rc;
-    uint8_t* dv = b->slab.dev;
-    b->d_jobs = (Job*)(dv + o_jobs);
-    b->d_bases = dv + o_bases; b->d_qual = dv + o_qual; b->d_ins = dv + o_ins; b->d_del = dv + o_del;
-    b->d_gcp = dv + o_gcp; b->d_hap = dv + o_hap;
-    b->d_out = (double*)(dv + b->o_out); b->d_used = dv + b->o_used;
-    b->d_rerun_list = (uint32_t*)(dv + o_rlist); b->d_rerun_count = (uint32_t*)(dv + o_rcount);
-    if (!staged) b->host_jobs.resize(n);
-    Job* jobs = staged ? (Job*)(b->slab.pin + o_jobs) : b->host_jobs.data();
+    SlabLayout L;
+    L.n = n; L.n_reads = n_reads; L.n_haps = n_haps; L.read_bytes = roff[n_reads]; L.hap_bytes = hoff[n_haps];
+    if ((rc = lay_out_slab(c, plan != nullptr, &L, b))) return rc;
+    if (!L.staged) b->host_jobs.resize(n);
+    Job* jobs = L.staged ? (Job*)(b->slab.pin + L.jobs) : b->host_jobs.data();
     {
         // key = (bin, H descending): counting sort on H inside each bin keeps the wavefront's groups
         // (consecutive jobs) at near-equal step counts, and longest first means the last workgroups of a
@@ -831,41 +785,7 @@ int create_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::Pac
             b->bins.push_back(bin);
         }
     }
-
-    // ---- upload: one copy out of the pinned mirror, or (very large batches) one per array
-    hipStream_t s = c->copy;
-    if (staged) {
-        uint8_t* pin = b->slab.pin;
-        if (plan) {
-            mgx::pack_copy(in, *plan, pin + o_bases, pin + o_qual, pin + o_ins, pin + o_del, pin + o_gcp, pin + o_hap);
-        } else if (read_bytes + hap_bytes < (32u << 20)) {
-            memcpy(pin + o_bases, in->bases, read_bytes); memcpy(pin + o_qual, in->qual, read_bytes);
-            memcpy(pin + o_ins, in->ins, read_bytes);     memcpy(pin + o_del, in->del, read_bytes);
-            memcpy(pin + o_gcp, in->gcp, read_bytes);     memcpy(pin + o_hap, in->hap_bases, hap_bytes);
-        } else {
-            // a large one-shot batch: the six arrays are staged by six threads (one core copies ~10 GB/s)
-            const void* src[6] = {in->bases, in->qual, in->ins, in->del, in->gcp, in->hap_bases};
-            uint8_t* dst[6] = {pin + o_bases, pin + o_qual, pin + o_ins, pin + o_del, pin + o_gcp, pin + o_hap};
-            const size_t len[6] = {(size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)hap_bytes};
-            std::thread th[6];
-            for (int k = 0; k < 6; ++k) th[k] = std::thread([=] { memcpy(dst[k], src[k], len[k]); });
-            for (auto& t : th) t.join();
-        }
-        HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
-    } else {
-        HIP_TRY(hipMemcpyAsync(b->d_jobs, jobs, n * sizeof(Job), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_bases, in->bases, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_qual, in->qual, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_ins, in->ins, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_del, in->del, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_gcp, in->gcp, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_hap, in->hap_bases, hap_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));          // the caller's buffers may go away after we return
-        b->host_jobs.clear(); b->host_jobs.shrink_to_fit();
-    }
-    HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->uploaded, s));       // batch_run makes the compute stream wait on this
-    return 0;
+    return upload_pairs(c, in, plan, L, jobs, b);
 }
 
 }  // namespace
@@ -879,223 +799,294 @@ int mgx_pairhmm_batch_create(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in,
     HIP_TRY(hipSetDevice(c->device));
     BatchPtr b = new_batch();
     if (!b) return -ENOMEM;
-    if (!in->pair_read && !in->pair_hap && in->n_reads && in->n_haps) rc = create_cross(c, in, b.get());   // cross-product form
+    std::vector<uint64_t> base;
+    if (!in->pair_read && !in->pair_hap && in->n_reads && in->n_haps) rc = create_cross(c, 1, in, b.get(), &base);   // cross-product form: one region
     else rc = create_pairs(c, in, nullptr, b.get());
     if (rc) return rc;
     *out = b.release();
     return 0;
 }
 
-int mgx_pairhmm_batch_run(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
-    if (!c || !b) { set_error("ctx/batch is NULL"); return -EINVAL; }
-    HIP_TRY(hipSetDevice(c->device));
-    if (b->n_pairs == 0) { b->ran = true; return 0; }
-    hipStream_t s = c->compute;
-    const bool timing = (c->flags & MGX_PAIRHMM_TIMING) != 0 && !b->bins.empty();
-    const bool force_f64 = (c->flags & MGX_PAIRHMM_FORCE_DOUBLE) != 0;
-    hipEvent_t* ev = nullptr;                  // this run's event set
-    if (timing) {
-        if (b->ev.empty()) {                   // whichever entry point made the batch: allocated on first use
-            const size_t per = b->bins.size() * 4;
-            b->ev_sets = (uint32_t)std::max<size_t>(1, std::min<size_t>(kMaxEventSets, 1024 / per));
-            b->ev.resize(per * b->ev_sets);
-            for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
-        }
-        ev = b->ev.data() + (size_t)(b->runs_timed % b->ev_sets) * b->bins.size() * 4;
-    }
-    if (b->uploaded) HIP_TRY(hipStreamWaitEvent(s, b->uploaded, 0));
-    HIP_TRY(hipMemsetAsync(b->d_rerun_count, 0, 64 * sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(b->d_used, 0, b->n_pairs, s));
-    // largest class first, classes dealt round-robin to the compute stream and the side streams
-    std::vector<size_t> order(b->bins.size());
-    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return b->bins[x].cells > b->bins[y].cells; });
-    const int n_str = (int)std::min<size_t>((size_t)c->n_streams, b->bins.size());
-    if (n_str > 1) {
-        HIP_TRY(hipEventRecord(c->ev_fork, s));
-        for (int q = 0; q + 1 < n_str; ++q) HIP_TRY(hipStreamWaitEvent(c->aux[q], c->ev_fork, 0));
-    }
-    // Re-runs in double precision: the "narrow" classes (at most 16 lanes x 8 rows: every read up to 128 bases) append
-    // to ONE list (their jobs are a prefix of the job array) that ONE fp64 launch of the 16 x RPLd shape processes --
-    // a test case's value does not depend on the shape that computes it; wider classes keep a list and a launch each.
-    auto narrow = [](const Bin& bn) { return bn.G <= 16 && bn.G * bn.RPL <= 16 * kNarrowMaxRPL; };
+namespace {
+
+constexpr int kSharedCount = 63;      // counter slot of the narrow classes' shared fp64 re-run list
+constexpr int kExactCount = 62;       // ... and of the exact tier's list (second half of d_rerun_list)
+
+// Re-runs in double precision: the "narrow" classes (at most 16 lanes x 8 rows: every read up to 128 bases) append
+// to ONE list (their jobs are a prefix of the job array) that ONE fp64 launch of the 16 x RPLd shape processes --
+// a test case's value does not depend on the shape that computes it; wider classes keep a list and a launch each.
+inline bool is_narrow(const Bin& bn) { return bn.G <= 16 && bn.G * bn.RPL <= 16 * kNarrowMaxRPL; }
+
+// what the steps of one mgx_pairhmm_batch_run share
+struct Run {
+    mgx_pairhmm* c = nullptr;
+    mgx_pairhmm_batch* b = nullptr;
+    hipStream_t s = nullptr;                   // the compute stream
+    bool timing = false, force_f64 = false;
+    hipEvent_t* ev = nullptr;                  // this run's event set (timing only)
+    int n_str = 1;                             // streams the classes are dealt to
+    KernelArgs base{};                         // the arguments every launch starts from
+    std::vector<char> in_multi;                // classes that a multi-class launch has computed
+    size_t first_narrow = 0;                   // books the shared fp64 launch; bins.size() if there is no narrow class
     uint32_t n_narrow_jobs = 0, narrow_max_h = 0, narrow_rows = 0;
-    size_t first_narrow = b->bins.size();
-    for (size_t k = 0; k < b->bins.size(); ++k) {
-        const Bin& bn = b->bins[k];
-        if (!narrow(bn)) continue;
-        if (first_narrow == b->bins.size()) first_narrow = k;
-        n_narrow_jobs = std::max(n_narrow_jobs, bn.job_begin + bn.job_count);
-        narrow_max_h = std::max(narrow_max_h, bn.max_h);
-        narrow_rows = std::max(narrow_rows, (uint32_t)(bn.G * bn.RPL));
+};
+
+// boundary rows of the strip-mined class and of the exact tier: one array per context, grown on demand
+int ensure_strip_scratch(mgx_pairhmm* c, size_t bytes) {
+    if (bytes <= c->strip_cap) return 0;
+    HIP_TRY(hipStreamSynchronize(c->compute));           // an earlier launch may still be using the old array
+    (void)hipFree(c->d_strip); c->d_strip = nullptr; c->strip_cap = 0;
+    HIP_TRY(hipMalloc(&c->d_strip, bytes));
+    c->strip_cap = bytes;
+    return 0;
+}
+
+// this run's event set out of the batch's ring
+int pick_event_set(Run& r) {
+    mgx_pairhmm_batch* b = r.b;
+    if (!r.timing) return 0;
+    if (b->ev.empty()) {                   // whichever entry point made the batch: allocated on first use
+        const size_t per = b->bins.size() * 4;
+        b->ev_sets = (uint32_t)std::max<size_t>(1, std::min<size_t>(kMaxEventSets, 1024 / per));
+        b->ev.resize(per * b->ev_sets);
+        for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
     }
-    constexpr int kSharedCount = 63;                       // counter slot of the shared list
-    constexpr int kExactCount = 62;                        // ... and of the exact tier's list (second half of d_rerun_list)
-    uint32_t* const d_exact_list = b->d_rerun_list + b->n_pairs;
-    KernelArgs base{};
+    r.ev = b->ev.data() + (size_t)(b->runs_timed % b->ev_sets) * b->bins.size() * 4;
+    return 0;
+}
+
+// the compute stream waits for the upload, the counters and flags are cleared, the side streams fork
+int begin_run(Run& r) {
+    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
+    if (b->uploaded) HIP_TRY(hipStreamWaitEvent(r.s, b->uploaded, 0));
+    HIP_TRY(hipMemsetAsync(b->d_rerun_count, 0, 64 * sizeof(uint32_t), r.s));
+    HIP_TRY(hipMemsetAsync(b->d_used, 0, b->n_pairs, r.s));
+    r.n_str = (int)std::min<size_t>((size_t)c->n_streams, b->bins.size());
+    if (r.n_str > 1) {
+        HIP_TRY(hipEventRecord(c->ev_fork, r.s));
+        for (int q = 0; q + 1 < r.n_str; ++q) HIP_TRY(hipStreamWaitEvent(c->aux[q], c->ev_fork, 0));
+    }
+    KernelArgs& base = r.base;
     base.jobs = b->d_jobs;
     base.bases = b->d_bases; base.qual = b->d_qual; base.ins = b->d_ins; base.del = b->d_del;
     base.gcp = b->d_gcp; base.hap_bases = b->d_hap;
     base.out_log10 = b->d_out; base.used_f64 = b->d_used;
     base.log10_initial_f = c->log10_initial_f;
     base.log10_initial_d = c->log10_initial_d;
-    auto launch_f64 = [&](KernelArgs a, int Gd, int RPLd, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t sk) -> int {
-        a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
-        a.rerun_list = d_exact_list; a.rerun_count = b->d_rerun_count + kExactCount;      // job_list / n_dyn are set: the fp64 tier appends here
-        KernelFn f = a.strip_scratch ? (KernelFn)pairhmm_fwd_strip<double> : pick_kernel<double>(Gd, RPLd);
-        if (!f) { set_error("no fp64 kernel for G=%d RPL=%d", Gd, RPLd); return -ENOSYS; }
-        hipLaunchKernelGGL(f, dim3(grid), dim3(block), lds, sk, a);
-        return 0;
-    };
-    // Several narrow classes: one multi-class launch per lane-width set instead of one launch per class
-    // (MGX_PAIRHMM_MULTI=0 keeps the per-class launches).
-    // Only SMALL classes share a launch: measured on an MI355X (profiles/r02_pairhmm_multi_ab.txt) the common launch
-    // costs every class the register budget of the hungriest one (131-149 VGPRs: 3 wavefronts per SIMD; 4 when forced,
-    // with spills), which outweighs the saved drains for classes that fill the device on their own (ragged 1 M test
-    // cases, nine classes of ~29 000 workgroups: 4462 -> 4343 GCUPS) but not for classes of a few thousand workgroups
-    // (reads of 20-32 bases: 2764 -> 3009; region-sized batches).  MGX_PAIRHMM_MULTI: 0 never, 1 small classes (default),
-    // 2 the same with the build forced to 4 wavefronts per SIMD, 3 every narrow class.
-    static const int multi_mode = [] { const char* e = getenv("MGX_PAIRHMM_MULTI"); return e ? atoi(e) : 1; }();
-    const uint32_t multi_below = (multi_mode == 3 || multi_mode == 4) ? 0xFFFFFFFFu : (uint32_t)c->n_cu * 64u;     // workgroups; ~5 device fills
-    const bool multi_ok = multi_mode != 0;
-    std::vector<char> in_multi(b->bins.size(), 0);
+    return 0;
+}
+
+// extent of the narrow classes: what the shared fp64 launch has to cover
+void survey_narrow(Run& r) {
+    const std::vector<Bin>& bins = r.b->bins;
+    r.first_narrow = bins.size();
+    for (size_t k = 0; k < bins.size(); ++k) {
+        const Bin& bn = bins[k];
+        if (!is_narrow(bn)) continue;
+        if (r.first_narrow == bins.size()) r.first_narrow = k;
+        r.n_narrow_jobs = std::max(r.n_narrow_jobs, bn.job_begin + bn.job_count);
+        r.narrow_max_h = std::max(r.narrow_max_h, bn.max_h);
+        r.narrow_rows = std::max(r.narrow_rows, (uint32_t)(bn.G * bn.RPL));
+    }
+}
+
+// an fp64 launch over a job list or a class; what it leaves near the flush-to-zero threshold goes to the exact tier's list
+int launch_f64(const Run& r, KernelArgs a, int Gd, int RPLd, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t sk) {
+    const mgx_pairhmm* c = r.c;
+    a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
+    a.rerun_list = r.b->d_rerun_list + r.b->n_pairs; a.rerun_count = r.b->d_rerun_count + kExactCount;      // job_list / n_dyn are set: the fp64 tier appends here
+    KernelFn f = a.strip_scratch ? (KernelFn)pairhmm_fwd_strip<double> : pick_kernel<double>(Gd, RPLd);
+    if (!f) { set_error("no fp64 kernel for G=%d RPL=%d", Gd, RPLd); return -ENOSYS; }
+    hipLaunchKernelGGL(f, dim3(grid), dim3(block), lds, sk, a);
+    return 0;
+}
+
+// one multi-class launch over the classes `set` (lane-width set gset), booked on the member with the most cells
+int launch_multi(Run& r, int gset, std::vector<size_t>& set) {
+    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
+    // most rows per lane first (the costliest workgroups), wider groups first among equals
+    std::stable_sort(set.begin(), set.end(), [&](size_t x, size_t y) {
+        const Bin &bx = b->bins[x], &by = b->bins[y];
+        return bx.RPL != by.RPL ? bx.RPL > by.RPL : bx.G > by.G;
+    });
+    MultiArgs m{};
+    m.a = r.base;
+    m.a.rerun_list = b->d_rerun_list; m.a.rerun_count = b->d_rerun_count + kSharedCount;
+    m.a.job_list = nullptr; m.a.n_dyn = nullptr;
+    m.a.ph2pr = c->d_ph2pr_f; m.a.mm = c->d_mm_f; m.a.ph2pr_div3 = c->d_div3_f; m.a.gap_ratio = c->d_ratio_f;
+    m.n_bins = (uint32_t)set.size();
+    uint32_t blocks = 0, lds = 0;
+    size_t book = set[0];
+    uint64_t cells = 0, bytes = 0;
+    for (size_t q = 0; q < set.size(); ++q) {
+        const Bin& bn = b->bins[set[q]];
+        m.block_first[q] = blocks; blocks += bn.grid_f32;
+        m.job_first[q] = bn.job_begin; m.job_count[q] = bn.job_count; m.lds_stride[q] = bn.lds_stride;
+        m.G[q] = (uint8_t)bn.G; m.RPL[q] = (uint8_t)bn.RPL;
+        lds = std::max(lds, lds_bytes(bn, true));
+        if (bn.cells > b->bins[book].cells) book = set[q];
+        cells += bn.cells; bytes += bn.alg_bytes;
+        r.in_multi[set[q]] = 1;
+        b->acct_cells[set[q]] = 0; b->acct_bytes[set[q]] = 0;
+    }
+    m.block_first[set.size()] = blocks;
+    b->acct_cells[book] = cells; b->acct_bytes[book] = bytes; b->acct_multi[book] = (int8_t)(1 + gset);
+    if (r.timing) for (size_t q : set) if (q != book) { HIP_TRY(hipEventRecord(r.ev[4 * q + 0], r.s)); HIP_TRY(hipEventRecord(r.ev[4 * q + 1], r.s)); }
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * book + 0], r.s));
+    if (gset == 0) hipLaunchKernelGGL(pairhmm_fwd_multi<0>, dim3(blocks), dim3(64), lds, r.s, m);
+    else           hipLaunchKernelGGL(pairhmm_fwd_multi<1>, dim3(blocks), dim3(64), lds, r.s, m);
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * book + 1], r.s));
+    return 0;
+}
+
+// Several narrow classes: one multi-class launch per lane-width set instead of one launch per class.
+// Only SMALL classes share a launch: measured on an MI355X (profiles/r02_pairhmm_multi_ab.txt) the common launch
+// costs every class the register budget of the hungriest one (131-149 VGPRs: 3 wavefronts per SIMD; 4 when forced,
+// with spills), which outweighs the saved drains for classes that fill the device on their own (ragged 1 M test
+// cases, nine classes of ~29 000 workgroups: 4462 -> 4343 GCUPS) but not for classes of a few thousand workgroups
+// (reads of 20-32 bases: 2764 -> 3009; region-sized batches).  MGX_PAIRHMM_MULTI=0 keeps the per-class launches; any
+// other value is the default.  (The same build forced to 4 wavefronts per SIMD, and sharing a launch among all narrow
+// classes whatever their size, were measured too and lost: DESIGN.md 3.5.)
+int launch_multi_classes(Run& r) {
+    mgx_pairhmm_batch* b = r.b;
+    static const bool multi_ok = [] { const char* e = getenv("MGX_PAIRHMM_MULTI"); return !e || atoi(e) != 0; }();
+    const uint32_t multi_below = (uint32_t)r.c->n_cu * 64u;     // workgroups; ~5 device fills
+    r.in_multi.assign(b->bins.size(), 0);
     b->acct_cells.assign(b->bins.size(), 0); b->acct_bytes.assign(b->bins.size(), 0); b->acct_multi.assign(b->bins.size(), 0);
     for (size_t k = 0; k < b->bins.size(); ++k) { b->acct_cells[k] = b->bins[k].cells; b->acct_bytes[k] = b->bins[k].alg_bytes; }
-    if (multi_ok && !force_f64) {
-        for (int gset = 0; gset < 2; ++gset) {
-            std::vector<size_t> set;
-            for (size_t k = 0; k < b->bins.size(); ++k) {
-                const Bin& bn = b->bins[k];
-                if (narrow(bn) && bn.RPL <= kNarrowMaxRPL && bn.block == 64 && bn.grid_f32 < multi_below && (gset == 0 ? bn.G == 16 : bn.G < 16)) set.push_back(k);
-            }
-            if (set.size() < 2 || set.size() > (size_t)kMultiBins) continue;
-            // most rows per lane first (the costliest workgroups), wider groups first among equals
-            std::stable_sort(set.begin(), set.end(), [&](size_t x, size_t y) {
-                const Bin &bx = b->bins[x], &by = b->bins[y];
-                return bx.RPL != by.RPL ? bx.RPL > by.RPL : bx.G > by.G;
-            });
-            MultiArgs m{};
-            m.a = base;
-            m.a.rerun_list = b->d_rerun_list; m.a.rerun_count = b->d_rerun_count + kSharedCount;
-            m.a.job_list = nullptr; m.a.n_dyn = nullptr;
-            m.a.ph2pr = c->d_ph2pr_f; m.a.mm = c->d_mm_f; m.a.ph2pr_div3 = c->d_div3_f; m.a.gap_ratio = c->d_ratio_f;
-            m.n_bins = (uint32_t)set.size();
-            uint32_t blocks = 0, lds = 0;
-            size_t book = set[0];
-            uint64_t cells = 0, bytes = 0;
-            for (size_t q = 0; q < set.size(); ++q) {
-                const Bin& bn = b->bins[set[q]];
-                m.block_first[q] = blocks; blocks += bn.grid_f32;
-                m.job_first[q] = bn.job_begin; m.job_count[q] = bn.job_count; m.lds_stride[q] = bn.lds_stride;
-                m.G[q] = (uint8_t)bn.G; m.RPL[q] = (uint8_t)bn.RPL;
-                lds = std::max(lds, lds_bytes(bn, true));
-                if (bn.cells > b->bins[book].cells) book = set[q];
-                cells += bn.cells; bytes += bn.alg_bytes;
-                in_multi[set[q]] = 1;
-                b->acct_cells[set[q]] = 0; b->acct_bytes[set[q]] = 0;
-            }
-            m.block_first[set.size()] = blocks;
-            b->acct_cells[book] = cells; b->acct_bytes[book] = bytes; b->acct_multi[book] = (int8_t)(1 + gset);
-            if (timing) for (size_t q : set) if (q != book) { HIP_TRY(hipEventRecord(ev[4 * q + 0], s)); HIP_TRY(hipEventRecord(ev[4 * q + 1], s)); }
-            if (timing) HIP_TRY(hipEventRecord(ev[4 * book + 0], s));
-            if (multi_mode == 2 || multi_mode == 4) {
-                if (gset == 0) hipLaunchKernelGGL(pairhmm_fwd_multi_occ4<0>, dim3(blocks), dim3(64), lds, s, m);
-                else           hipLaunchKernelGGL(pairhmm_fwd_multi_occ4<1>, dim3(blocks), dim3(64), lds, s, m);
-            } else {
-                if (gset == 0) hipLaunchKernelGGL(pairhmm_fwd_multi<0>, dim3(blocks), dim3(64), lds, s, m);
-                else           hipLaunchKernelGGL(pairhmm_fwd_multi<1>, dim3(blocks), dim3(64), lds, s, m);
-            }
-            if (timing) HIP_TRY(hipEventRecord(ev[4 * book + 1], s));
+    if (!multi_ok || r.force_f64) return 0;
+    for (int gset = 0; gset < 2; ++gset) {
+        std::vector<size_t> set;
+        for (size_t k = 0; k < b->bins.size(); ++k) {
+            const Bin& bn = b->bins[k];
+            if (is_narrow(bn) && bn.RPL <= kNarrowMaxRPL && bn.block == 64 && bn.grid_f32 < multi_below && (gset == 0 ? bn.G == 16 : bn.G < 16)) set.push_back(k);
         }
+        if (set.size() < 2 || set.size() > (size_t)kMultiBins) continue;
+        if (const int rc = launch_multi(r, gset, set)) return rc;
     }
-    for (size_t at = 0; at < order.size(); ++at) {
-        const size_t k = order[at];
-        const Bin& bin = b->bins[k];
-        hipStream_t sk = (int)(at % (size_t)n_str) == 0 ? s : c->aux[at % (size_t)n_str - 1];
-        const bool shared = narrow(bin) && !force_f64;
-        KernelArgs a = base;
-        if (bin.strip) {
-            a.strip_stride = (bin.max_h + 63u) & ~63u;
-            const size_t need = (size_t)bin.grid_f32 * 6u * a.strip_stride * sizeof(double);
-            if (need > c->strip_cap) {
-                HIP_TRY(hipStreamSynchronize(s));           // an earlier launch may still be using the old array
-                (void)hipFree(c->d_strip); c->d_strip = nullptr; c->strip_cap = 0;
-                HIP_TRY(hipMalloc(&c->d_strip, need));
-                c->strip_cap = need;
-            }
-            a.strip_scratch = c->d_strip;
-        }
-        a.rerun_list = shared ? b->d_rerun_list : b->d_rerun_list + bin.job_begin;
-        a.rerun_count = b->d_rerun_count + (shared ? kSharedCount : (int)k);
-        a.lds_stride = bin.lds_stride;
-        a.job_first = bin.job_begin;
-        if (!force_f64 && !in_multi[k]) {
-            a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count;
-            a.ph2pr = c->d_ph2pr_f; a.mm = c->d_mm_f; a.ph2pr_div3 = c->d_div3_f; a.gap_ratio = c->d_ratio_f;
-            KernelFn f = bin.strip ? (KernelFn)pairhmm_fwd_strip<float> : pick_kernel<float>(bin.G, bin.RPL);
-            if (!f) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
-            if (timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], sk));
-            hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true), sk, a);
-            if (timing) HIP_TRY(hipEventRecord(ev[4 * k + 1], sk));
-        }
-        const bool books_shared = shared && k == first_narrow;      // the shared launch is booked on the first narrow class
-        if (timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 2], sk));
-        if (!shared) {
-            if (force_f64) { a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count; }
-            else { a.job_list = a.rerun_list; a.n_dyn = a.rerun_count; a.n_static = 0; }
-            const int rc = launch_f64(a, bin.Gd, bin.RPLd, force_f64 ? bin.grid_f64_all : bin.grid_f64, bin.block, lds_bytes(bin, false), sk);
-            if (rc) return rc;
-        }
-        if (timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 3], sk));
-    }
-    for (int q = 0; q + 1 < n_str; ++q) {          // the side streams join the compute stream
-        HIP_TRY(hipEventRecord(c->ev_join[q], c->aux[q]));
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_join[q], 0));
-    }
-    if (n_narrow_jobs && !force_f64) {
-        KernelArgs a = base;
-        a.job_list = b->d_rerun_list; a.n_dyn = b->d_rerun_count + kSharedCount; a.n_static = 0; a.job_first = 0;
-        a.lds_stride = (narrow_max_h + 2u * 16u + 8u + 15u) & ~15u;
-        const int RPLd = (int)((narrow_rows + 15) / 16);
-        const uint32_t grid = std::min<uint32_t>((n_narrow_jobs + 3) / 4, (uint32_t)c->n_cu * 8u);
-        if (timing) HIP_TRY(hipEventRecord(ev[4 * first_narrow + 2], s));
-        const int rc = launch_f64(a, 16, RPLd, grid, 64, 4u * a.lds_stride, s);
-        if (rc) return rc;
-        if (timing) HIP_TRY(hipEventRecord(ev[4 * first_narrow + 3], s));
-    }
-    {
-        // The exact tier: whatever the fp64 launches left within reach of the flush-to-zero threshold (next to nothing
-        // on real data: log10 likelihoods below about -587), one test case per wavefront, the reference's operation order.
-        uint32_t max_h = 0;
-        for (const Bin& bn : b->bins) max_h = std::max(max_h, bn.max_h);
-        KernelArgs a = base;
-        a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
-        a.job_list = d_exact_list; a.n_dyn = b->d_rerun_count + kExactCount; a.n_static = 0; a.job_first = 0;
-        a.rerun_list = nullptr; a.rerun_count = nullptr;
-        a.lds_stride = (max_h + 2u * 64u + 8u + 15u) & ~15u;
-        a.strip_stride = (max_h + 63u) & ~63u;
-        const size_t per_wg = 6u * (size_t)a.strip_stride * sizeof(double);
-        const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)b->n_pairs, (size_t)c->n_cu * 2u, (size_t)(256u << 20) / per_wg}));
-        const size_t need = (size_t)grid * per_wg;
-        if (need > c->strip_cap) {
-            HIP_TRY(hipStreamSynchronize(s));
-            (void)hipFree(c->d_strip); c->d_strip = nullptr; c->strip_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_strip, need));
-            c->strip_cap = need;
-        }
+    return 0;
+}
+
+// class k on stream sk: its fp32 launch unless a multi-class launch has done it, then the fp64 re-run of its own list
+// (the narrow classes share one, launch_shared_f64)
+int launch_class(Run& r, size_t k, hipStream_t sk) {
+    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
+    hipEvent_t* ev = r.ev;
+    const Bin& bin = b->bins[k];
+    const bool shared = is_narrow(bin) && !r.force_f64;
+    KernelArgs a = r.base;
+    if (bin.strip) {
+        a.strip_stride = (bin.max_h + 63u) & ~63u;
+        if (const int rc = ensure_strip_scratch(c, (size_t)bin.grid_f32 * 6u * a.strip_stride * sizeof(double))) return rc;
         a.strip_scratch = c->d_strip;
-        hipLaunchKernelGGL(pairhmm_fwd_exact, dim3(grid), dim3(64), a.lds_stride, s, a);
     }
-    if (b->has_model && b->d_row_off)
-        hipLaunchKernelGGL(pairhmm_normalize_filter_rows, dim3((b->n_reads + 3) / 4), dim3(256), 0, s, b->d_out, b->d_read_len,
-                           b->d_row_off, b->d_row_nh, b->n_reads, b->log10_rate, b->max_err, b->d_keep);
-    else if (b->has_model)
-        hipLaunchKernelGGL(pairhmm_normalize_filter, dim3((b->n_reads + 3) / 4), dim3(256), 0, s, b->d_out, b->d_read_len,
-                           b->n_reads, b->n_haps, b->log10_rate, b->max_err, b->d_keep);
+    a.rerun_list = shared ? b->d_rerun_list : b->d_rerun_list + bin.job_begin;
+    a.rerun_count = b->d_rerun_count + (shared ? kSharedCount : (int)k);
+    a.lds_stride = bin.lds_stride;
+    a.job_first = bin.job_begin;
+    if (!r.force_f64 && !r.in_multi[k]) {
+        a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count;
+        a.ph2pr = c->d_ph2pr_f; a.mm = c->d_mm_f; a.ph2pr_div3 = c->d_div3_f; a.gap_ratio = c->d_ratio_f;
+        KernelFn f = bin.strip ? (KernelFn)pairhmm_fwd_strip<float> : pick_kernel<float>(bin.G, bin.RPL);
+        if (!f) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
+        if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], sk));
+        hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true), sk, a);
+        if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 1], sk));
+    }
+    const bool books_shared = shared && k == r.first_narrow;      // the shared launch is booked on the first narrow class
+    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 2], sk));
+    if (!shared) {
+        if (r.force_f64) { a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count; }
+        else { a.job_list = a.rerun_list; a.n_dyn = a.rerun_count; a.n_static = 0; }
+        const int rc = launch_f64(r, a, bin.Gd, bin.RPLd, r.force_f64 ? bin.grid_f64_all : bin.grid_f64, bin.block, lds_bytes(bin, false), sk);
+        if (rc) return rc;
+    }
+    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 3], sk));
+    return 0;
+}
+
+// largest class first, classes dealt round-robin to the compute stream and the side streams, which then join it
+int launch_classes(Run& r) {
+    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
+    std::vector<size_t> order(b->bins.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return b->bins[x].cells > b->bins[y].cells; });
+    for (size_t at = 0; at < order.size(); ++at) {
+        hipStream_t sk = (int)(at % (size_t)r.n_str) == 0 ? r.s : c->aux[at % (size_t)r.n_str - 1];
+        if (const int rc = launch_class(r, order[at], sk)) return rc;
+    }
+    for (int q = 0; q + 1 < r.n_str; ++q) {
+        HIP_TRY(hipEventRecord(c->ev_join[q], c->aux[q]));
+        HIP_TRY(hipStreamWaitEvent(r.s, c->ev_join[q], 0));
+    }
+    return 0;
+}
+
+// the narrow classes' shared re-run list in one fp64 launch
+int launch_shared_f64(Run& r) {
+    if (!r.n_narrow_jobs || r.force_f64) return 0;
+    KernelArgs a = r.base;
+    a.job_list = r.b->d_rerun_list; a.n_dyn = r.b->d_rerun_count + kSharedCount; a.n_static = 0; a.job_first = 0;
+    a.lds_stride = (r.narrow_max_h + 2u * 16u + 8u + 15u) & ~15u;
+    const int RPLd = (int)((r.narrow_rows + 15) / 16);
+    const uint32_t grid = std::min<uint32_t>((r.n_narrow_jobs + 3) / 4, (uint32_t)r.c->n_cu * 8u);
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * r.first_narrow + 2], r.s));
+    if (const int rc = launch_f64(r, a, 16, RPLd, grid, 64, 4u * a.lds_stride, r.s)) return rc;
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * r.first_narrow + 3], r.s));
+    return 0;
+}
+
+// The exact tier: whatever the fp64 launches left within reach of the flush-to-zero threshold (next to nothing
+// on real data: log10 likelihoods below about -587), one test case per wavefront, the reference's operation order.
+int launch_exact(Run& r) {
+    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
+    uint32_t max_h = 0;
+    for (const Bin& bn : b->bins) max_h = std::max(max_h, bn.max_h);
+    KernelArgs a = r.base;
+    a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
+    a.job_list = b->d_rerun_list + b->n_pairs; a.n_dyn = b->d_rerun_count + kExactCount; a.n_static = 0; a.job_first = 0;
+    a.rerun_list = nullptr; a.rerun_count = nullptr;
+    a.lds_stride = (max_h + 2u * 64u + 8u + 15u) & ~15u;
+    a.strip_stride = (max_h + 63u) & ~63u;
+    const size_t per_wg = 6u * (size_t)a.strip_stride * sizeof(double);
+    const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)b->n_pairs, (size_t)c->n_cu * 2u, (size_t)(256u << 20) / per_wg}));
+    if (const int rc = ensure_strip_scratch(c, (size_t)grid * per_wg)) return rc;
+    a.strip_scratch = c->d_strip;
+    hipLaunchKernelGGL(pairhmm_fwd_exact, dim3(grid), dim3(64), a.lds_stride, r.s, a);
+    return 0;
+}
+
+// whole-region batches: normalise / filter every read's row of the output
+void launch_epilogue(Run& r) {
+    const mgx_pairhmm_batch* b = r.b;
+    if (!b->has_model) return;
+    hipLaunchKernelGGL(pairhmm_normalize_filter_rows, dim3((b->n_reads + 3) / 4), dim3(256), 0, r.s, b->d_out, b->d_read_len,
+                       b->d_row_off, b->d_row_nh, b->n_reads, b->log10_rate, b->max_err, b->d_keep);
+}
+
+}  // namespace
+
+int mgx_pairhmm_batch_run(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
+    if (!c || !b) { set_error("ctx/batch is NULL"); return -EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    if (b->n_pairs == 0) { b->ran = true; return 0; }
+    Run r;
+    r.c = c; r.b = b; r.s = c->compute;
+    r.timing = (c->flags & MGX_PAIRHMM_TIMING) != 0 && !b->bins.empty();
+    r.force_f64 = (c->flags & MGX_PAIRHMM_FORCE_DOUBLE) != 0;
+    int rc;
+    if ((rc = pick_event_set(r))) return rc;
+    if ((rc = begin_run(r))) return rc;
+    survey_narrow(r);
+    if ((rc = launch_multi_classes(r))) return rc;
+    if ((rc = launch_classes(r))) return rc;
+    if ((rc = launch_shared_f64(r))) return rc;
+    if ((rc = launch_exact(r))) return rc;
+    launch_epilogue(r);
     HIP_TRY(hipGetLastError());
-    if (timing) b->runs_timed++;
+    if (r.timing) b->runs_timed++;
     if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->done, s));
+    HIP_TRY(hipEventRecord(b->done, r.s));
     b->ran = true;
     return 0;
 }
@@ -1176,6 +1167,34 @@ int fetch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, size_t bytes) {
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
+
+// The results of a batch made of regions [g0, g1) (base: every region's first test case in the batch, as create_cross
+// returns it), out of the pinned mirror into the caller's array of each region; keep may be NULL, and so may its entries.
+void scatter_region_results(const mgx_pairhmm_batch* b, const std::vector<uint64_t>& base, const mgx_pairhmm_input_t* regions,
+                            uint32_t g0, uint32_t g1, double* const* out, uint8_t* const* keep) {
+    const double* all = (const double*)(b->slab.pin + b->o_out);
+    const uint8_t* kept = b->slab.pin + b->o_keep;
+    uint64_t r_at = 0;
+    for (uint32_t g = g0; g < g1; ++g) {
+        const uint64_t a = base[g - g0], e = base[g - g0 + 1];
+        if (e > a) memcpy(out[g], all + a, (e - a) * sizeof(double));
+        if (keep && keep[g] && e > a) memcpy(keep[g], kept + r_at, regions[g].n_reads);
+        r_at += regions[g].n_reads;
+    }
+}
+
+// Cuts a list of regions into runs of whole regions of about `limit` test cases: a run ends in front of the region
+// that would take it past the limit (a region larger than the limit is a run of its own).  cut: the boundaries.
+void cut_regions(const mgx_pairhmm_input_t* regions, uint32_t n_regions, uint64_t limit, std::vector<uint32_t>* cut) {
+    cut->assign(1, 0);
+    uint64_t in_run = 0;
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        const uint64_t n = regions[g].n_reads * regions[g].n_haps;
+        if (in_run && in_run + n > limit) { cut->push_back(g); in_run = 0; }
+        in_run += n;
+    }
+    if (n_regions) cut->push_back(n_regions);
+}
 }  // namespace
 
 int mgx_pairhmm_batch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, double* out_log10,
@@ -1209,35 +1228,6 @@ void mgx_read_model_defaults(mgx_read_model_t* m) {
     m->max_error_per_base = 0.02;       // EXPECTED_ERROR_RATE_PER_BASE
 }
 
-int mgx_pairhmm_region(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const uint8_t* mapq,
-                       const mgx_read_model_t* model, double* out_log10, uint8_t* out_keep) {
-    if (!c || !in || !mapq || !model || !out_log10) { set_error("NULL argument"); return -EINVAL; }
-    if (in->pair_read || in->pair_hap) { set_error("mgx_pairhmm_region takes the cross-product form (pair arrays NULL)"); return -EINVAL; }
-    int rc = validate(in);
-    if (rc) return rc;
-    if (in->n_reads == 0 || in->n_haps == 0) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    BatchPtr b = new_batch();
-    if (!b) return -ENOMEM;
-    if ((rc = create_cross(c, in, b.get(), mapq, model))) return rc;
-    mgx_pairhmm_batch* raw = b.release();
-    rc = mgx_pairhmm_batch_run(c, raw);
-    if (!rc) {
-        uint8_t* pin = raw->slab.pin;
-        rc = [&]() -> int {
-            HIP_TRY(hipMemcpyAsync(pin + raw->o_out, raw->d_out, raw->result_bytes, hipMemcpyDeviceToHost, c->compute));
-            HIP_TRY(hipStreamSynchronize(c->compute));
-            return 0;
-        }();
-        if (!rc) {
-            memcpy(out_log10, pin + raw->o_out, raw->n_pairs * sizeof(double));
-            if (out_keep) memcpy(out_keep, pin + raw->o_keep, raw->n_reads);
-        }
-    }
-    mgx_pairhmm_batch_destroy(c, raw);
-    return rc;
-}
-
 int mgx_pairhmm_compute(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, double* out_log10) {
     mgx_pairhmm_batch_t* b = nullptr;
     int rc = mgx_pairhmm_batch_create(c, in, &b);
@@ -1261,30 +1251,30 @@ int mgx_pairhmm_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_
     BatchPtr b = new_batch();
     if (!b) return -ENOMEM;
     std::vector<uint64_t> base;
-    if ((rc = create_cross_multi(c, n_regions, regions, b.get(), &base, mapq, model))) return rc;
+    if ((rc = create_cross(c, n_regions, regions, b.get(), &base, mapq, model))) return rc;
     if (b->n_pairs == 0) return 0;
     mgx_pairhmm_batch* raw = b.release();
     rc = mgx_pairhmm_batch_run(c, raw);
     if (!rc) {
-        uint8_t* pin = raw->slab.pin;
-        rc = [&]() -> int {
-            HIP_TRY(hipMemcpyAsync(pin + raw->o_out, raw->d_out, raw->result_bytes, hipMemcpyDeviceToHost, c->compute));
+        rc = [&]() -> int {       // values and keep flags in one copy, behind the kernels on their own stream
+            HIP_TRY(hipMemcpyAsync(raw->slab.pin + raw->o_out, raw->d_out, raw->result_bytes, hipMemcpyDeviceToHost, c->compute));
             HIP_TRY(hipStreamSynchronize(c->compute));
             return 0;
         }();
-        if (!rc) {
-            const double* all = (const double*)(pin + raw->o_out);
-            const uint8_t* keep = pin + raw->o_keep;
-            uint64_t r_at = 0;
-            for (uint32_t g = 0; g < n_regions; ++g) {
-                if (base[g + 1] > base[g]) memcpy(out_log10[g], all + base[g], (base[g + 1] - base[g]) * sizeof(double));
-                if (out_keep && out_keep[g] && regions[g].n_reads && regions[g].n_haps) memcpy(out_keep[g], keep + r_at, regions[g].n_reads);
-                r_at += regions[g].n_reads;
-            }
-        }
+        if (!rc) scatter_region_results(raw, base, regions, 0, n_regions, out_log10, out_keep);
     }
     mgx_pairhmm_batch_destroy(c, raw);
     return rc;
+}
+
+int mgx_pairhmm_region(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const uint8_t* mapq,
+                       const mgx_read_model_t* model, double* out_log10, uint8_t* out_keep) {
+    if (!c || !in || !mapq || !model || !out_log10) { set_error("NULL argument"); return -EINVAL; }
+    if (in->pair_read || in->pair_hap) { set_error("mgx_pairhmm_region takes the cross-product form (pair arrays NULL)"); return -EINVAL; }
+    int rc = validate(in);
+    if (rc) return rc;
+    if (in->n_reads == 0 || in->n_haps == 0) return 0;
+    return mgx_pairhmm_regions(c, 1, in, &mapq, model, &out_log10, out_keep ? &out_keep : nullptr);
 }
 
 int mgx_pairhmm_compute_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, double* const* out_log10) {
@@ -1312,28 +1302,14 @@ int mgx_pairhmm_compute_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_
         kChunkPairs = std::min<uint64_t>(6u << 16, std::max<uint64_t>(kChunkPairs, total / 6));
     }
     if (const char* e = getenv("MGX_PAIRHMM_REGION_CHUNK")) { const long long v = atoll(e); if (v > 0) kChunkPairs = (uint64_t)v; }      // A/B
-    std::vector<uint32_t> cut(1, 0);
-    {
-        uint64_t in_chunk = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            const uint64_t n = regions[g].n_reads * regions[g].n_haps;
-            if (in_chunk && in_chunk + n > kChunkPairs) { cut.push_back(g); in_chunk = 0; }
-            in_chunk += n;
-        }
-        cut.push_back(n_regions);
-    }
+    std::vector<uint32_t> cut;
+    cut_regions(regions, n_regions, kChunkPairs, &cut);
     struct InFlight { mgx_pairhmm_batch_t* b = nullptr; uint32_t g0 = 0, g1 = 0; std::vector<uint64_t> base; };
     InFlight fl[2];
     auto retire = [&](InFlight& f) -> int {
         if (!f.b) return 0;
-        int r = fetch_results(c, f.b, f.b->n_pairs * sizeof(double));
-        if (!r) {
-            const double* all = (const double*)(f.b->slab.pin + f.b->o_out);
-            for (uint32_t g = f.g0; g < f.g1; ++g) {
-                const uint64_t a = f.base[g - f.g0], e = f.base[g - f.g0 + 1];
-                if (e > a) memcpy(out_log10[g], all + a, (e - a) * sizeof(double));
-            }
-        }
+        const int r = fetch_results(c, f.b, f.b->n_pairs * sizeof(double));
+        if (!r) scatter_region_results(f.b, f.base, regions, f.g0, f.g1, out_log10, nullptr);
         mgx_pairhmm_batch_destroy(c, f.b);
         f.b = nullptr;
         return r;
@@ -1346,7 +1322,7 @@ int mgx_pairhmm_compute_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_
         BatchPtr b = new_batch();
         if (!b) { rc = -ENOMEM; break; }
         f.g0 = cut[k]; f.g1 = cut[k + 1];
-        if ((rc = create_cross_multi(c, f.g1 - f.g0, regions + f.g0, b.get(), &f.base))) break;
+        if ((rc = create_cross(c, f.g1 - f.g0, regions + f.g0, b.get(), &f.base))) break;
         if (b->n_pairs == 0) continue;
         f.b = b.release();
         rc = mgx_pairhmm_batch_run(c, f.b);
@@ -1416,13 +1392,7 @@ void queue_lane(mgx_pairhmm_queue* q, mgx_pairhmm_queue::Lane* ln, QueueRun* run
             int rc = 0;
             if (run->regions) {
                 rc = fetch_results(c, sl.b, sl.b->n_pairs * sizeof(double));
-                if (!rc) {
-                    const double* all = (const double*)(sl.b->slab.pin + sl.b->o_out);
-                    for (uint32_t g = sl.g0; g < sl.g1; ++g) {
-                        const uint64_t a = sl.base[g - sl.g0], e = sl.base[g - sl.g0 + 1];
-                        if (e > a) memcpy(run->region_out[g], all + a, (e - a) * sizeof(double));
-                    }
-                }
+                if (!rc) scatter_region_results(sl.b, sl.base, run->regions, sl.g0, sl.g1, run->region_out, nullptr);
                 ln->bytes_d2h += sl.b->n_pairs * 8;
             } else {
                 const uint64_t at = sl.lo - run->lo;
@@ -1447,7 +1417,7 @@ void queue_lane(mgx_pairhmm_queue* q, mgx_pairhmm_queue::Lane* ln, QueueRun* run
         int rc = b ? 0 : -ENOMEM;
         if (!rc && run->regions) {
             sl.g0 = run->chunk[k]; sl.g1 = run->chunk[k + 1];
-            rc = create_cross_multi(c, sl.g1 - sl.g0, run->regions + sl.g0, b.get(), &sl.base);
+            rc = create_cross(c, sl.g1 - sl.g0, run->regions + sl.g0, b.get(), &sl.base);
         } else if (!rc) {
             sl.lo = run->lo + k * q->batch_pairs;
             const uint64_t hi = std::min(run->hi, sl.lo + q->batch_pairs);
@@ -1543,19 +1513,16 @@ int mgx_pairhmm_queue_run_regions(mgx_pairhmm_queue_t* q, uint32_t n_regions, co
     q->stats.n_lanes = (uint32_t)q->lanes.size();
     QueueRun run;
     run.regions = regions; run.region_out = out_log10;
-    // batches are runs of whole regions holding about batch_pairs test cases
-    uint64_t total = 0, in_chunk = 0;
-    run.chunk.push_back(0);
+    uint64_t total = 0;
     for (uint32_t g = 0; g < n_regions; ++g) {
         int rc = validate(&regions[g]);
         if (rc) return rc;
         if (regions[g].pair_read || regions[g].pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
         const uint64_t n = regions[g].n_reads * regions[g].n_haps;
         if (n && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
-        if (in_chunk && in_chunk + n > q->batch_pairs) { run.chunk.push_back(g); in_chunk = 0; }
-        in_chunk += n; total += n;
+        total += n;
     }
-    if (n_regions) run.chunk.push_back(n_regions);
+    cut_regions(regions, n_regions, q->batch_pairs, &run.chunk);      // batches are runs of whole regions holding about batch_pairs test cases
     run.n_batches = run.chunk.size() - 1;
     if (total == 0) return 0;
     return queue_execute(q, run, total);

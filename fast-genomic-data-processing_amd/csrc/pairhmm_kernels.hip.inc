@@ -645,12 +645,6 @@ __global__ __launch_bounds__(256) void pairhmm_fwd_multi(MultiArgs m) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     pairhmm_multi_body<GSET>(m, smem);
 }
-// the same with the register budget of 4 wavefronts per SIMD enforced (the compiler spills what does not fit)
-template <int GSET>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void pairhmm_fwd_multi_occ4(MultiArgs m) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    pairhmm_multi_body<GSET>(m, smem);
-}
 
 // Cross-product batches (every read against every haplotype of a region, the shape
 // VectorLoglessPairHMM builds): job descriptors are generated on the device from two small tables
@@ -660,18 +654,10 @@ struct SeqRef {
     uint32_t len;
     uint32_t id;
 };
-__global__ __launch_bounds__(256) void pairhmm_make_jobs(const SeqRef* __restrict__ reads, const SeqRef* __restrict__ haps,
-                                                         uint32_t n_haps, uint32_t n_jobs, Job* __restrict__ jobs) {
-    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n_jobs) return;
-    const SeqRef r = reads[q / n_haps], h = haps[q % n_haps];   // neighbours: same read, haplotypes of similar length
-    Job j;
-    j.read_off = r.off; j.hap_off = h.off; j.R = r.len; j.H = h.len; j.pair = r.id * n_haps + h.id; j.pad_ = 0;
-    jobs[q] = j;
-}
 
-// Row F1 (SURVEY.md 8f): several active regions in ONE batch.  Every read is paired with the
-// haplotypes of its own region; job q belongs to the read whose prefix range holds q.
+// One or several active regions (row F1, SURVEY.md 8f) in ONE batch.  Every read is paired with the
+// haplotypes of its own region; job q belongs to the read whose prefix range holds q, so neighbouring jobs
+// are the same read against haplotypes of similar length.
 struct RegionRef {
     uint32_t hap_begin;    // first entry of the region's (length-sorted) haplotypes in the hap table
     uint32_t n_haps;
@@ -785,29 +771,8 @@ __global__ __launch_bounds__(128) void pairhmm_read_model(const SeqRef* __restri
 
 // one wavefront per read over its n_haps results: normalizeLikelihoods (AlleleLikelihoods.h:153-166,
 // 372-391) and the filterPoorlyModeledEvidence decision (:404-419, log10MinTrueLikelihood
-// PairHMMLikelihoodCalculationEngine.cpp:294-299)
-__global__ __launch_bounds__(256) void pairhmm_normalize_filter(double* __restrict__ out, const uint64_t* __restrict__ read_len,
-                                                                uint32_t n_reads, uint32_t n_haps, double log10_rate,
-                                                                double max_error_per_base, uint8_t* __restrict__ keep) {
-    const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= n_reads) return;
-    double* row = out + (size_t)r * n_haps;
-    double best = -__builtin_inf();
-    for (uint32_t h = lane; h < n_haps; h += 64) best = fmax(best, row[h]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) best = fmax(best, __shfl_xor(best, off, 64));
-    if (!__builtin_isinf(log10_rate) && n_haps > 1) {
-        const double cap = best + log10_rate;
-        for (uint32_t h = lane; h < n_haps; h += 64) if (row[h] < cap) row[h] = cap;
-    }
-    if (lane == 0) {
-        const double max_err = fmin(2.0, ceil((double)read_len[r] * max_error_per_base));
-        keep[r] = !(best < max_err * -4.0);
-    }
-}
-
-// the same over several regions in one batch: every read has its own row (start, width) in the output
+// PairHMMLikelihoodCalculationEngine.cpp:294-299).  Every read has its own row (start, width) in the output: the
+// reads of a batch may belong to different regions.
 __global__ __launch_bounds__(256) void pairhmm_normalize_filter_rows(double* __restrict__ out, const uint64_t* __restrict__ read_len,
                                                                      const uint32_t* __restrict__ row_off, const uint32_t* __restrict__ row_nh,
                                                                      uint32_t n_reads, double log10_rate, double max_error_per_base,

@@ -170,11 +170,11 @@ def test_one_context_per_worker_thread(pkg, synth):
     one region's data into the next."""
     import threading
     regions = [synth.gen_pairhmm_region(20 + 3 * k, 5 + k % 7, 100 + k, r_range=(30, 140), h_range=(60, 300)) for k in range(24)]
+    ref_eng = pkg.PairHMMEngine(0)
+    want = [ref_eng.compute(r) for r in regions]       # the explicit pair list: a builder of its own
+    ref_eng.close()
     for r in regions:
         r["pair_read"] = None; r["pair_hap"] = None
-    ref_eng = pkg.PairHMMEngine(0)
-    want = [ref_eng.compute(r) for r in regions]
-    ref_eng.close()
     got = [None] * len(regions)
     errors = []
 
@@ -210,14 +210,15 @@ def test_batches_in_flight(engine, oracle, synth):
 
 def test_many_regions_in_one_batch(engine, synth):
     """Row F1: coalescing active regions into one device batch returns, bit for bit, what one call per
-    region returns (regions of different sizes and read-length classes, one of them a single pair)."""
+    region returns (regions of different sizes and read-length classes, one of them a single pair).  The call per
+    region takes the explicit pair list, which is built by code of its own (the cross-product form of one region and
+    of many share a builder)."""
     shapes = [(24, 16, (20, 128), (64, 256)), (1, 1, (100, 100), (200, 200)), (40, 25, (90, 151), (150, 400)),
               (7, 3, (200, 400), (300, 600)), (60, 9, (30, 60), (40, 90)), (3, 40, (151, 151), (200, 300))]
     regions = [synth.gen_pairhmm_region(nr, nh, 100 + k, r_range=rr, h_range=hr) for k, (nr, nh, rr, hr) in enumerate(shapes)]
     got = engine.compute_regions(regions)
     for d, o in zip(regions, got):
-        dd = dict(d); dd["pair_read"] = None; dd["pair_hap"] = None
-        want = engine.compute(dd).reshape(o.shape)
+        want = engine.compute(d).reshape(o.shape)
         assert np.array_equal(o, want)
     # sub-views: a region whose offset tables do not start at zero
     d = regions[2]
@@ -226,6 +227,11 @@ def test_many_regions_in_one_batch(engine, synth):
     full = got[2]
     part = engine.compute_regions([sub])[0]
     assert np.array_equal(part, full[5:20, 3:11])
+    # the same sub-view through a plain compute in the cross-product form, and as an explicit pair list
+    cross = dict(sub, pair_read=None, pair_hap=None)
+    assert np.array_equal(engine.compute(cross).reshape(15, 8), full[5:20, 3:11])
+    pairs = dict(sub, pair_read=np.repeat(np.arange(15, dtype=np.uint32), 8), pair_hap=np.tile(np.arange(8, dtype=np.uint32), 15))
+    assert np.array_equal(engine.compute(pairs).reshape(15, 8), full[5:20, 3:11])
 
 
 def test_region_batch_with_empty_and_many_regions(engine, synth):
@@ -236,8 +242,7 @@ def test_region_batch_with_empty_and_many_regions(engine, synth):
     got = engine.compute_regions(regs)
     assert got[500].shape == (0, 4)
     for k in (0, 1, 499, 501, 777, 1000):
-        d = dict(regs[k]); d["pair_read"] = None; d["pair_hap"] = None
-        assert np.array_equal(got[k], engine.compute(d).reshape(got[k].shape))
+        assert np.array_equal(got[k], engine.compute(regs[k]).reshape(got[k].shape))      # explicit pair list
 
 
 @pytest.mark.parametrize("r_range,h_range,n,gcp", [((1025, 1100), (900, 1300), 40, 10), ((2049, 3300), (50, 700), 40, 10),

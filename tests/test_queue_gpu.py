@@ -90,9 +90,10 @@ def test_pair_count_without_pair_arrays_is_rejected(pkg, synth):
 
 
 def test_regions_through_the_queue(pkg, engine, synth):
-    """Row F1 through the queue: runs of whole regions pulled by the lanes; values identical to one call per region."""
+    """Row F1 through the queue: runs of whole regions pulled by the lanes; values identical to one call per region
+    (in the explicit pair-list form, which does not share the cross-product builder)."""
     regions = [synth.gen_pairhmm_region(5 + (g * 7) % 40, 1 + (g * 3) % 25, 100 + g, r_range=(20, 128), h_range=(64, 256)) for g in range(60)]
-    want = [engine.compute(dict(r, pair_read=None, pair_hap=None)).reshape(len(r["read_off"]) - 1, len(r["hap_off"]) - 1) for r in regions]
+    want = [engine.compute(r).reshape(len(r["read_off"]) - 1, len(r["hap_off"]) - 1) for r in regions]
     q = pkg.PairHMMQueue(devices=(0,), lanes_per_device=3, depth=2, batch_pairs=3000)
     got = q.run_regions(regions)
     st = q.stats()

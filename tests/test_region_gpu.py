@@ -44,6 +44,30 @@ def oracle_model(d, mapq, rate=3, thr=18, gcp=10):
     return m, olib
 
 
+def check_against_pair_list_and_oracle(engine, oracle, d, mapq, raw, got, keep, pcr_rate_factor=3, log10_rate=-4.5):
+    """One region's results against code that shares nothing with the cross-product builder: `raw` (normalisation
+    off) equals, bit for bit, the explicit pair list computed on the oracle-modified arrays; `got` / `keep` agree with
+    the oracle's normalisation and filter of the oracle's likelihoods."""
+    n_reads, n_haps = raw.shape
+    mod, olib = oracle_model(d, mapq, rate=pcr_rate_factor)
+    dm = dict(d); dm.update(mod)
+    assert dm["pair_read"] is not None and len(dm["pair_read"]) == n_reads * n_haps
+    assert np.array_equal(raw.ravel(), engine.compute(dm))
+    want, _ = oracle.batch(dm)
+    want = want.reshape(n_reads, n_haps).copy()
+    keep_want = np.zeros(n_reads, dtype=np.uint8)
+    ro = np.ascontiguousarray(d["read_off"], dtype=np.uint64)
+    olib.ph_oracle_normalize_filter(ctypes.c_int64(n_reads), ctypes.c_int64(n_haps), ro.ctypes.data_as(ctypes.c_void_p),
+                                    want.ctypes.data_as(ctypes.c_void_p), ctypes.c_double(log10_rate), ctypes.c_double(0.02),
+                                    keep_want.ctypes.data_as(ctypes.c_void_p))
+    assert_log10_close(got.ravel(), want.ravel())
+    best = got.max(axis=1)
+    R = np.diff(d["read_off"].astype(np.int64))
+    thr = np.minimum(2.0, np.ceil(R * 0.02)) * -4.0
+    sure = np.abs(best - thr) > 1e-4                   # away from the threshold the decision must agree
+    assert np.array_equal(keep[sure], keep_want[sure])
+
+
 @pytest.mark.parametrize("n_reads,n_haps,seed", [(60, 17, 1), (200, 40, 2), (5, 1, 3)])
 def test_region_matches_oracle_pipeline(engine, oracle, synth, n_reads, n_haps, seed):
     d, mapq = repeat_rich_region(synth, n_reads, n_haps, seed)
@@ -51,10 +75,10 @@ def test_region_matches_oracle_pipeline(engine, oracle, synth, n_reads, n_haps, 
     assert (mod["ins"] != d["ins"]).any() and (mod["qual"] != d["qual"]).any()      # the model did something
     dm = dict(d); dm.update(mod)
     # (1) the device's read model produces the oracle's bytes: with normalisation off, the region call
-    #     must equal the plain PairHMM on the oracle-modified arrays bit for bit
+    #     must equal the plain PairHMM on the oracle-modified arrays (as an explicit pair list: the builder that
+    #     the region call does not go through) bit for bit
     raw, _ = engine.region(d, mapq, log10_mismapping_rate=float("-inf"))
-    dm_cross = dict(dm); dm_cross["pair_read"] = None; dm_cross["pair_hap"] = None
-    assert np.array_equal(raw.ravel(), engine.compute(dm_cross))
+    assert np.array_equal(raw.ravel(), engine.compute(dm))
     # (2) the whole pipeline against the oracle's
     want, _ = oracle.batch(dm)
     want = want.reshape(n_reads, n_haps).copy()
@@ -83,17 +107,18 @@ def test_region_long_reads(engine, oracle, synth):
     assert np.diff(d["read_off"].astype(np.int64)).max() > 1024
     mod, olib = oracle_model(d, mapq)
     dm = dict(d); dm.update(mod)
-    dm_cross = dict(dm); dm_cross["pair_read"] = None; dm_cross["pair_hap"] = None
     raw, _ = engine.region(d, mapq, log10_mismapping_rate=float("-inf"))
-    assert np.array_equal(raw.ravel(), engine.compute(dm_cross))
+    assert np.array_equal(raw.ravel(), engine.compute(dm))          # dm carries the explicit pair list
     want, _ = oracle.batch(dm)
     assert_log10_close(raw.ravel(), want)
     # and in one batch with short-read regions
     d2, mapq2 = repeat_rich_region(synth, 40, 9, 22)
     got = engine.regions([d2, d, d2], [mapq2, mapq, mapq2])
-    for (o, k), (dd, mq) in zip(got, [(d2, mapq2), (d, mapq), (d2, mapq2)]):
+    raws = engine.regions([d2, d, d2], [mapq2, mapq, mapq2], log10_mismapping_rate=float("-inf"))
+    for (o, k), (rw, _), (dd, mq) in zip(got, raws, [(d2, mapq2), (d, mapq), (d2, mapq2)]):
         wo, wk = engine.region(dd, mq)
         assert np.array_equal(o, wo) and np.array_equal(k, wk)
+        check_against_pair_list_and_oracle(engine, oracle, dd, mq, rw, o, k)
 
 
 def test_region_model_off(engine, synth):
@@ -104,22 +129,28 @@ def test_region_model_off(engine, synth):
     p2 = dict(d2); p2["pair_read"] = None; p2["pair_hap"] = None
     got, keep = engine.region(d2, np.full(30, 255, dtype=np.uint8), pcr_rate_factor=0, constant_gcp=-1,
                               log10_mismapping_rate=float("-inf"))
-    assert np.array_equal(got.ravel(), engine.compute(p2))
+    assert np.array_equal(got.ravel(), engine.compute(d2))          # the explicit pair list
+    assert np.array_equal(got.ravel(), engine.compute(p2))          # and the cross-product form
 
 
-def test_several_regions_in_one_batch(engine, synth):
-    """rows F1 + F2: mgx_pairhmm_regions returns, per region, exactly what mgx_pairhmm_region returns"""
+def test_several_regions_in_one_batch(engine, oracle, synth):
+    """rows F1 + F2: mgx_pairhmm_regions returns, per region, exactly what mgx_pairhmm_region returns (the call with
+    one region), and what the explicit pair list and the oracle's normalisation / filter give"""
     shapes = [(60, 17, 11), (5, 1, 12), (200, 40, 13), (33, 7, 14)]
     regs, mqs = [], []
     for n_reads, n_haps, seed in shapes:
         d, mapq = repeat_rich_region(synth, n_reads, n_haps, seed)
         regs.append(d); mqs.append(mapq)
     got = engine.regions(regs, mqs)
-    for d, mq, (o, k) in zip(regs, mqs, got):
+    raws = engine.regions(regs, mqs, log10_mismapping_rate=float("-inf"))
+    for d, mq, (o, k), (rw, _) in zip(regs, mqs, got, raws):
         wo, wk = engine.region(d, mq)
         assert np.array_equal(o, wo) and np.array_equal(k, wk)
+        check_against_pair_list_and_oracle(engine, oracle, d, mq, rw, o, k)
     # a different model applies to all regions alike
     got2 = engine.regions(regs[:2], mqs[:2], pcr_rate_factor=1, log10_mismapping_rate=-3.0)
-    for d, mq, (o, k) in zip(regs[:2], mqs[:2], got2):
+    raws2 = engine.regions(regs[:2], mqs[:2], pcr_rate_factor=1, log10_mismapping_rate=float("-inf"))
+    for d, mq, (o, k), (rw, _) in zip(regs[:2], mqs[:2], got2, raws2):
         wo, wk = engine.region(d, mq, pcr_rate_factor=1, log10_mismapping_rate=-3.0)
         assert np.array_equal(o, wo) and np.array_equal(k, wk)
+        check_against_pair_list_and_oracle(engine, oracle, d, mq, rw, o, k, pcr_rate_factor=1, log10_rate=-3.0)

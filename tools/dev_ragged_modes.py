@@ -1,5 +1,5 @@
-"""Ragged sub-run 2b and region batches under the multi-class launch modes (development aid): run once per mode,
-MGX_PAIRHMM_MULTI is read at first use."""
+"""Ragged sub-run 2b and region batches with and without the multi-class launch (development aid): run once with
+MGX_PAIRHMM_MULTI=0 and once without it, the variable is read at first use."""
 import importlib, sys, os, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
