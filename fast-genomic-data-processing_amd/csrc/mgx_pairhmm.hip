@@ -57,7 +57,7 @@ struct Bin {
     uint32_t max_h = 0;
     uint64_t cells = 0, alg_bytes = 0;
     // launch geometry
-    uint32_t block = 256, lds_stride = 0, grid_f32 = 0, grid_f64 = 0, grid_f64_all = 0;
+    uint32_t block = 256, lds_stride = 0, grid_f32 = 0, grid_f64 = 0, grid_f64_all = 0, grid_nhap = 0;
     bool strip = false;              // reads longer than 1024 bases: the strip-mined kernel, one test case per workgroup
 };
 
@@ -105,6 +105,7 @@ struct mgx_pairhmm_batch {
     Job* d_jobs = nullptr;
     uint32_t* d_rerun_list = nullptr;
     uint32_t* d_rerun_count = nullptr;
+    uint32_t* d_nhap_list = nullptr;   // N-haplotype test cases of the four-code launches, every class at its job_begin
     double* d_out = nullptr;
     std::vector<Job> host_jobs;    // only kept for unstaged (very large) batches
     // whole-region form (mgx_pairhmm_regions): normalise / filter epilogue over every read's row of the output
@@ -168,10 +169,10 @@ inline void shape_of(uint32_t R, int* G, int* RPL) {
     else if (R <= (uint32_t)kMaxRowsStrip) { *G = 64; *RPL = kStripMarkRPL; }
     else { *G = 0; *RPL = 0; }
 }
-// dynamic LDS of one block: per-wavefront emission table (fp32 only) + per-group haplotype codes
-inline uint32_t lds_bytes(const Bin& bin, bool f32) {
+// dynamic LDS of one block: per-wavefront emission table (fp32 only, `codes` columns) + per-group haplotype codes
+inline uint32_t lds_bytes(const Bin& bin, bool f32, int codes = kMaxCodes) {
     const uint32_t waves = bin.block / 64u, groups = bin.block / (uint32_t)(f32 ? bin.G : bin.Gd);
-    const uint32_t etab = f32 ? (uint32_t)((bin.RPL + 1) / 2) * kNumCodes * 512u : 0u;
+    const uint32_t etab = f32 ? (uint32_t)((bin.RPL + 1) / 2) * (uint32_t)codes * 512u : 0u;
     return waves * etab + groups * bin.lds_stride;
 }
 // bins in order of (G, RPL): [G=4: 1..8][G=8: 1..8][G=16: 1..12][G=64: 4..16]
@@ -194,6 +195,10 @@ inline void bin_shape(int k, Bin* b) {
     else { b->Gd = b->G; b->RPLd = b->RPL; }
 }
 constexpr uint64_t kMergeBelow = 4096;
+// device counters of a batch: [0, kBins) every class's own fp64 re-run list, 62 the exact tier's list, 63 the narrow
+// classes' shared fp64 list, [kNhapCount, kNhapCount + kBins) every class's N-haplotype list
+constexpr int kNhapCount = 64, kCounters = 128;
+static_assert(kBins <= 62 && kNhapCount + kBins <= kCounters, "counter slots");
 
 // launch geometry of a bin once job_count and max_h are known
 int finalize_bin(Bin& bin, int n_cu) {
@@ -218,6 +223,7 @@ int finalize_bin(Bin& bin, int n_cu) {
     bin.grid_f32 = (bin.job_count + gpb - 1) / gpb;
     bin.grid_f64_all = (bin.job_count + gpbd - 1) / gpbd;
     bin.grid_f64 = std::min<uint32_t>(bin.grid_f64_all, (uint32_t)n_cu * 8u);
+    bin.grid_nhap = std::min<uint32_t>(bin.grid_f32, (uint32_t)n_cu * 8u);
     return 0;
 }
 // fold sparsely populated bins into the next larger row class of the same group width
@@ -401,7 +407,7 @@ struct SlabLayout {
     size_t rtab = 0, rreg = 0, rpre = 0, gtab = 0, htab = 0;      // cross-product form: what the jobs are enumerated from
     size_t jobs = 0, bases = 0, qual = 0, ins = 0, del = 0, gcp = 0, hap = 0;
     size_t mapq = 0, rlen = 0, roff = 0, rnh = 0;                 // with a read model: per read, for the model and the epilogue
-    size_t rlist = 0, rcount = 0;
+    size_t rlist = 0, nlist = 0, rcount = 0;
     size_t pin_bytes = 0;                                         // the pinned mirror covers the inputs and the results only
     bool staged = true;
 };
@@ -439,7 +445,8 @@ int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_b
     L->pin_bytes = off;
     if (L->cross) L->jobs = take(n * sizeof(Job));
     L->rlist = take(2 * n * sizeof(uint32_t));       // fp64 re-run lists | exact-tier list
-    L->rcount = take(64 * sizeof(uint32_t));
+    L->nlist = take(n * sizeof(uint32_t));           // N-haplotype lists of the four-code fp32 launches
+    L->rcount = take(kCounters * sizeof(uint32_t));
     L->staged = always_stage || L->pin_bytes <= kStageLimit;
     if (const int rc = acquire_slab(c, off, L->staged ? L->pin_bytes : 0, &b->slab)) return rc;
     uint8_t* dv = b->slab.dev;
@@ -448,6 +455,7 @@ int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_b
     b->d_gcp = dv + L->gcp; b->d_hap = dv + L->hap;
     b->d_out = (double*)(dv + b->o_out); b->d_used = dv + b->o_used;
     b->d_rerun_list = (uint32_t*)(dv + L->rlist); b->d_rerun_count = (uint32_t*)(dv + L->rcount);
+    b->d_nhap_list = (uint32_t*)(dv + L->nlist);
     if (L->model) {
         b->d_read_len = (uint64_t*)(dv + L->rlen); b->d_keep = dv + b->o_keep;
         b->d_row_off = (uint32_t*)(dv + L->roff); b->d_row_nh = (uint32_t*)(dv + L->rnh);
@@ -859,7 +867,7 @@ int pick_event_set(Run& r) {
 int begin_run(Run& r) {
     mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
     if (b->uploaded) HIP_TRY(hipStreamWaitEvent(r.s, b->uploaded, 0));
-    HIP_TRY(hipMemsetAsync(b->d_rerun_count, 0, 64 * sizeof(uint32_t), r.s));
+    HIP_TRY(hipMemsetAsync(b->d_rerun_count, 0, kCounters * sizeof(uint32_t), r.s));
     HIP_TRY(hipMemsetAsync(b->d_used, 0, b->n_pairs, r.s));
     r.n_str = (int)std::min<size_t>((size_t)c->n_streams, b->bins.size());
     if (r.n_str > 1) {
@@ -871,6 +879,7 @@ int begin_run(Run& r) {
     base.bases = b->d_bases; base.qual = b->d_qual; base.ins = b->d_ins; base.del = b->d_del;
     base.gcp = b->d_gcp; base.hap_bases = b->d_hap;
     base.out_log10 = b->d_out; base.used_f64 = b->d_used;
+    base.nhap_list = b->d_nhap_list; base.nhap_count = b->d_rerun_count + kNhapCount;
     base.log10_initial_f = c->log10_initial_f;
     base.log10_initial_d = c->log10_initial_d;
     return 0;
@@ -922,8 +931,8 @@ int launch_multi(Run& r, int gset, std::vector<size_t>& set) {
         const Bin& bn = b->bins[set[q]];
         m.block_first[q] = blocks; blocks += bn.grid_f32;
         m.job_first[q] = bn.job_begin; m.job_count[q] = bn.job_count; m.lds_stride[q] = bn.lds_stride;
-        m.G[q] = (uint8_t)bn.G; m.RPL[q] = (uint8_t)bn.RPL;
-        lds = std::max(lds, lds_bytes(bn, true));
+        m.G[q] = (uint8_t)bn.G; m.RPL[q] = (uint8_t)bn.RPL; m.bin[q] = (uint8_t)set[q];
+        lds = std::max(lds, lds_bytes(bn, true, 4));
         if (bn.cells > b->bins[book].cells) book = set[q];
         cells += bn.cells; bytes += bn.alg_bytes;
         r.in_multi[set[q]] = 1;
@@ -984,14 +993,27 @@ int launch_class(Run& r, size_t k, hipStream_t sk) {
     a.rerun_count = b->d_rerun_count + (shared ? kSharedCount : (int)k);
     a.lds_stride = bin.lds_stride;
     a.job_first = bin.job_begin;
-    if (!r.force_f64 && !r.in_multi[k]) {
-        a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count;
+    a.nhap_list = b->d_nhap_list + bin.job_begin;
+    a.nhap_count = b->d_rerun_count + kNhapCount + (int)k;
+    if (!r.force_f64) {
+        // four code columns first (the strip-mined class: five), then the class's N-haplotype list with five; both
+        // append their underflows to the same fp64 list.  A multi-class launch has done the first of the two.
         a.ph2pr = c->d_ph2pr_f; a.mm = c->d_mm_f; a.ph2pr_div3 = c->d_div3_f; a.gap_ratio = c->d_ratio_f;
-        KernelFn f = bin.strip ? (KernelFn)pairhmm_fwd_strip<float> : pick_kernel<float>(bin.G, bin.RPL);
-        if (!f) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
-        if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], sk));
-        hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true), sk, a);
-        if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 1], sk));
+        const bool first = !r.in_multi[k];
+        if (first) {
+            a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count;
+            KernelFn f = bin.strip ? (KernelFn)pairhmm_fwd_strip<float> : pick_kernel<float, 4>(bin.G, bin.RPL);
+            if (!f) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
+            if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], sk));
+            hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true, bin.strip ? kMaxCodes : 4), sk, a);
+        }
+        if (!bin.strip) {
+            KernelFn f5 = pick_kernel<float, kMaxCodes>(bin.G, bin.RPL);
+            if (!f5) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
+            a.job_list = a.nhap_list; a.n_dyn = a.nhap_count; a.n_static = 0;
+            hipLaunchKernelGGL(f5, dim3(bin.grid_nhap), dim3(bin.block), lds_bytes(bin, true, kMaxCodes), sk, a);
+        }
+        if (r.timing && first) HIP_TRY(hipEventRecord(ev[4 * k + 1], sk));
     }
     const bool books_shared = shared && k == r.first_narrow;      // the shared launch is booked on the first narrow class
     if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 2], sk));
@@ -1013,6 +1035,7 @@ int launch_classes(Run& r) {
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return b->bins[x].cells > b->bins[y].cells; });
     for (size_t at = 0; at < order.size(); ++at) {
         hipStream_t sk = (int)(at % (size_t)r.n_str) == 0 ? r.s : c->aux[at % (size_t)r.n_str - 1];
+        if (r.in_multi[order[at]]) sk = r.s;      // its five-code launch follows the multi-class launch, which ran there
         if (const int rc = launch_class(r, order[at], sk)) return rc;
     }
     for (int q = 0; q + 1 < r.n_str; ++q) {
@@ -1107,9 +1130,11 @@ int mgx_pairhmm_batch_stats(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, mgx_pairhm
     st.n_launches_f32 = force_f64 ? 0 : (uint32_t)b->bins.size();
     st.n_launches_f64 = (uint32_t)b->bins.size();
     st.n_rerun_f64 = 0;
+    st.n_nhap_f32 = 0;
     if (b->ran && b->n_pairs) {
-        std::vector<uint32_t> cnt(64);
-        HIP_TRY(hipMemcpy(cnt.data(), b->d_rerun_count, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> cnt(kCounters);
+        HIP_TRY(hipMemcpy(cnt.data(), b->d_rerun_count, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < b->bins.size(); ++k) st.n_nhap_f32 += cnt[kNhapCount + k];
         for (size_t k = 0; k < b->bins.size(); ++k) st.n_rerun_f64 += force_f64 ? b->bins[k].job_count : cnt[k];
         if (!force_f64) st.n_rerun_f64 += cnt[63];          // the narrow classes' shared list
         st.n_exact = cnt[62];

@@ -69,6 +69,8 @@ struct KernelArgs {
     uint8_t* used_f64;          // [n_pairs]
     uint32_t* rerun_list;       // fp32: jobs (indices into jobs) whose result underflowed -> re-run in fp64;
     uint32_t* rerun_count;      // fp64: jobs whose result is in reach of the flush-to-zero threshold -> exact re-run
+    uint32_t* nhap_list;        // fp32 with the four-code table: jobs whose haplotype holds an N -> the five-code fp32
+    uint32_t* nhap_count;       // launch of the same class (no result is written for them here)
     uint32_t lds_stride;        // bytes of LDS per group (>= max H of the bin + 2)
     void* strip_scratch;        // strip-mined class only: [workgroups][2][3][strip_stride] boundary rows (M, X, Y per column)
     uint32_t strip_stride;
@@ -153,14 +155,15 @@ template <> struct Prec<double> {
 // LDS emission table (fp32 kernels): etab[(s/2)][code][lane][s&1] holds e(row s of that lane,
 // haplotype code), so the per-cell compare+select becomes one conflict-free ds_read_b64 per
 // two rows (bank = lane) whose address is "code*512 + lane*8" plus an immediate offset.
-#ifndef MGX_PAIRHMM_CODES
-#define MGX_PAIRHMM_CODES 5
-#endif
-// 5: A C T G N  (PAD reads as N: harmless).  4 (A/B builds, tools/build_variant.sh -DMGX_PAIRHMM_CODES=4): no column for N -- 8 KB
-// instead of 10 KB per wavefront of eight rows per lane, 16 wavefronts per CU instead of 14 --, a test case whose haplotype holds an
-// N is left to the double-precision kernel (per test case, never per wavefront: a value does not depend on the batch it is in)
-constexpr int kNumCodes = MGX_PAIRHMM_CODES;
-template <int RPL> constexpr int etab_bytes_per_wave() { return ((RPL + 1) / 2) * kNumCodes * 64 * 8; }
+// CODES (a template parameter of the body) is the number of code columns.  5: A C T G N  (PAD reads as N: harmless).
+// 4: no column for N -- 8 KB instead of 10 KB per wavefront of eight rows per lane, so that the register budget and not
+// LDS decides how many wavefronts a CU holds (16 instead of 14).  The first fp32 launch of every class but the
+// strip-mined one has four columns; a test case whose haplotype holds an N gets no result from it and is appended to
+// the class's N-haplotype list, which the five-column fp32 instantiation of the same class then works through (per
+// test case, never per wavefront: a value does not depend on the batch it is in, nor on which launch computed it --
+// both read the same table entries for A C T G).  fp64 has no table; its CODES stays 5.
+constexpr int kMaxCodes = 5;
+template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return ((RPL + 1) / 2) * CODES * 64 * 8; }
 
 // The recurrence for the jobs of ONE class (G, RPL); `block` / `n_blocks` are the workgroup's index and count among
 // the workgroups working on this class (the whole grid for a single-class launch).
@@ -172,10 +175,13 @@ template <int RPL> constexpr int etab_bytes_per_wave() { return ((RPL + 1) / 2) 
 // on its own.  Flush-to-zero is on in the reference (IntelPairHmm.cc:230) and here, and a result within a few
 // hundred orders of magnitude of 2^-1022 depends on WHICH intermediate products were flushed: the fused
 // multiply-adds and the scaled form of the fast tiers flush at other points than the reference does.
-template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false>
+template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false, int CODES = kMaxCodes>
 __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem, const uint32_t block, const uint32_t n_blocks) {
     constexpr int GPW = 64 / G;                   // groups per wavefront
     constexpr bool kETab = (sizeof(T) == 4);      // fp32: emission table in LDS; fp64: compare+select
+    constexpr int kNumCodes = CODES;
+    static_assert(CODES == 4 || CODES == kMaxCodes, "four or five code columns");
+    static_assert(kETab || CODES == kMaxCodes, "fp64 has no table: the N code is compared");
     constexpr bool kSix = (sizeof(T) == 4) && !EXACT;   // fp32: the 6-operation cell; fp64: the scaled 7-operation cell (see sweep)
     constexpr int RP2 = (RPL + 1) / 2;
     constexpr int S = lane_stride<G>();           // lane stride of a group inside its DPP row
@@ -188,8 +194,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
     const int grp = wave * GPW + (G < 16 ? (lane >> 4) * S + (lane & 15) % S : lane / G);
     // LDS: [waves][etab] then [groups][hap codes]
     const int n_waves = (int)blockDim.x >> 6;
-    uint8_t* etab = smem + (kETab ? (size_t)wave * etab_bytes_per_wave<RPL>() : 0);
-    uint8_t* hapbuf = smem + (kETab ? (size_t)n_waves * etab_bytes_per_wave<RPL>() : 0) +
+    uint8_t* etab = smem + (kETab ? (size_t)wave * etab_bytes_per_wave<RPL, CODES>() : 0);
+    uint8_t* hapbuf = smem + (kETab ? (size_t)n_waves * etab_bytes_per_wave<RPL, CODES>() : 0) +
                       (size_t)grp * a.lds_stride;
     const T* __restrict__ ph2pr = (const T*)a.ph2pr;
     const T* __restrict__ mm = (const T*)a.mm;
@@ -322,8 +328,11 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         __syncthreads();                          // hapbuf / etab visible
 
         // ---- anti-diagonal sweep
-        const int nsteps_g = live ? (H + nl - 1) : 0;
-        int nmax = nsteps_g, nmin = live ? nsteps_g : 0x7fffffff;
+        // (a group that leaves its test case to the five-code launch takes no steps of its own: like a group without a job
+        // it follows its neighbours, and a wavefront made of such groups only skips the sweep)
+        const bool swept = live && !group_hap_n;
+        const int nsteps_g = swept ? (H + nl - 1) : 0;
+        int nmax = nsteps_g, nmin = swept ? nsteps_g : 0x7fffffff;
         if constexpr (GPW > 1) {
             // every lane of a group holds the group's value: combine across the groups interleaved in a row
             // (xor below S), then across rows / groups (xor from max(G, 16) up)
@@ -453,15 +462,20 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 // how many of its columns ran in which loop, i.e. on its wavefront neighbours.
                 T Mn[RPL], Xn[RPL], Yn[RPL];
                 if constexpr (SIX) {
-                    Mn[0] = fma_(k3[0], o2Y, fma_(o2M, k0[0], o2X)) * ec[0];
-                    Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
-                    Yn[0] = fma_(py[0], k4[0], pm[0]);
+                    // in place, bottom row first: a row's new M and y overwrite the old ones once the row below has
+                    // read them, so no value has to be moved out of the way; X follows top down from the new M
 #pragma unroll
-                    for (int s = 1; s < RPL; ++s) {
-                        Mn[s] = fma_(k3[s], py[s - 1], fma_(pm[s - 1], k0[s], px[s - 1])) * ec[s];
-                        Xn[s] = fma_(Xn[s - 1], k2[s], Mn[s - 1] * k1[s]);
-                        Yn[s] = fma_(py[s], k4[s], pm[s]);
+                    for (int s = RPL - 1; s >= 0; --s) {
+                        const T t = s ? fma_(k3[s], py[s - 1], fma_(pm[s - 1], k0[s], px[s - 1]))
+                                      : fma_(k3[0], o2Y, fma_(o2M, k0[0], o2X));
+                        py[s] = fma_(py[s], k4[s], pm[s]);
+                        pm[s] = t * ec[s];
                     }
+                    px[0] = fma_(o1X, k2[0], o1M * k1[0]);
+#pragma unroll
+                    for (int s = 1; s < RPL; ++s) px[s] = fma_(px[s - 1], k2[s], pm[s - 1] * k1[s]);
+#pragma unroll
+                    for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
                 } else if constexpr (SC) {
                     Mn[0] = (fma_(o2M, k0[0], o2X) + o2Y) * ec[0];
                     Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
@@ -551,7 +565,10 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         if (live && j == nl - 1) {
             const T res = sumM + sumX;
             if constexpr (sizeof(T) == 4) {
-                if (res < 1e-28f || group_hap_n) {
+                if (group_hap_n) {
+                    const uint32_t k = atomicAdd(a.nhap_count, 1u);
+                    a.nhap_list[k] = job_idx;
+                } else if (res < 1e-28f) {
                     const uint32_t k = atomicAdd(a.rerun_count, 1u);
                     a.rerun_list[k] = job_idx;
                 } else {
@@ -579,13 +596,13 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 // changes the allocator's choices and parks 16-18 values (236 MB of scratch writes per 1 M test cases; same duration).
 // (Holding 11 rows per lane -- 171 registers -- to the 168 of 3 wavefronts spills 19: not done.)  10 rows per lane (the
 // 151-base reads) need 169 with the 6-operation cell: held to the 168 of 3 wavefronts.
-template <typename T, int G, int RPL>
+template <typename T, int G, int RPL, int CODES = kMaxCodes>
 #ifndef MGX_HMM_MINWAVES_8
 #define MGX_HMM_MINWAVES_8 4
 #endif
 __global__ __launch_bounds__(256, (sizeof(T) == 4 && RPL == 7) ? MGX_HMM_MINWAVES_8 : (sizeof(T) == 4 && RPL == 10) ? 3 : 1) void pairhmm_fwd(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    pairhmm_body<T, G, RPL>(a, smem, blockIdx.x, gridDim.x);
+    pairhmm_body<T, G, RPL, false, false, CODES>(a, smem, blockIdx.x, gridDim.x);
 }
 
 // the strip-mined class: reads of more than 1024 bases, one test case per wavefront, 64 lanes x 16 rows per strip
@@ -614,6 +631,7 @@ struct MultiArgs {
     uint32_t block_first[kMultiBins + 1];      // first workgroup of every class
     uint32_t job_first[kMultiBins], job_count[kMultiBins], lds_stride[kMultiBins];
     uint8_t G[kMultiBins], RPL[kMultiBins];
+    uint8_t bin[kMultiBins];                   // the class's index in the batch: its N-haplotype counter
 };
 
 template <int GSET>
@@ -622,9 +640,10 @@ __device__ __forceinline__ void pairhmm_multi_body(const MultiArgs& m, uint8_t* 
     while (k + 1 < m.n_bins && blockIdx.x >= m.block_first[k + 1]) ++k;       // wave-uniform
     KernelArgs a = m.a;
     a.job_first = m.job_first[k]; a.n_static = m.job_count[k]; a.lds_stride = m.lds_stride[k];
+    a.nhap_list += m.job_first[k]; a.nhap_count += m.bin[k];          // every class keeps its own N-haplotype list
     const uint32_t blk = blockIdx.x - m.block_first[k], nblk = m.block_first[k + 1] - m.block_first[k];
     const int code = (int)m.G[k] * 16 + (int)m.RPL[k];
-#define MGX_MCASE(g, r) case (g) * 16 + (r): pairhmm_body<float, g, r>(a, smem, blk, nblk); break;
+#define MGX_MCASE(g, r) case (g) * 16 + (r): pairhmm_body<float, g, r, false, false, 4>(a, smem, blk, nblk); break;
     if constexpr (GSET == 0) {
         switch (code) {
             MGX_MCASE(16, 1) MGX_MCASE(16, 2) MGX_MCASE(16, 3) MGX_MCASE(16, 4) MGX_MCASE(16, 5) MGX_MCASE(16, 6) MGX_MCASE(16, 7) MGX_MCASE(16, 8)
@@ -798,9 +817,9 @@ __global__ __launch_bounds__(256) void pairhmm_normalize_filter_rows(double* __r
 
 using KernelFn = void (*)(KernelArgs);
 
-template <typename T>
+template <typename T, int CODES = kMaxCodes>
 KernelFn pick_kernel(int G, int RPL) {
-#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r>;
+#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r, CODES>;
     MGX_CASE(4, 1) MGX_CASE(4, 2) MGX_CASE(4, 3) MGX_CASE(4, 4) MGX_CASE(4, 5) MGX_CASE(4, 6) MGX_CASE(4, 7) MGX_CASE(4, 8)
     MGX_CASE(8, 1) MGX_CASE(8, 2) MGX_CASE(8, 3) MGX_CASE(8, 4) MGX_CASE(8, 5) MGX_CASE(8, 6) MGX_CASE(8, 7) MGX_CASE(8, 8)
     MGX_CASE(16, 1) MGX_CASE(16, 2) MGX_CASE(16, 3) MGX_CASE(16, 4)

@@ -103,6 +103,8 @@ typedef struct mgx_pairhmm_stats {
     char dominant_kernel[64];  /* its name as rocprofv3 prints it (prefix) */
     uint64_t n_exact;          /* test cases whose fp64 result was < 1e-280 (in reach of the flush-to-zero threshold) and
                                 * that were computed a third time in the reference's exact operation order (last run) */
+    uint64_t n_nhap_f32;       /* test cases whose haplotype holds an N: computed by the five-code fp32 launch of their class
+                                * (last run; the strip-mined class has five codes throughout and is not counted) */
 } mgx_pairhmm_stats_t;
 
 const char* mgx_last_error(void);

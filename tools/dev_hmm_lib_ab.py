@@ -1,6 +1,7 @@
 """In-process A/B of several builds of libmgx.so (tools/build_variant.sh) on resident PairHMM batches: the builds take
-turns on the same inputs and device; per-step wall time, median of the rounds.
-usage: dev_hmm_lib_ab.py A.so B.so ...   (first one is the reference for the output check)"""
+turns on the same inputs and device; per-step wall time, median of the rounds and their spread (max - min).
+usage: dev_hmm_lib_ab.py [--rounds N] [--hap-n-rate P] A.so B.so ...   (first one is the reference for the output check,
+values and fp64 flags)"""
 import ctypes as C, importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,13 +17,20 @@ def bind(path):
     return lib
 
 
-libs = {os.path.basename(p): bind(p) for p in sys.argv[1:]}
+argv = sys.argv[1:]
+rounds, hap_n_rate = 3, 0.0
+while argv and argv[0].startswith("--"):
+    if argv[0] == "--rounds": rounds = int(argv[1])
+    elif argv[0] == "--hap-n-rate": hap_n_rate = float(argv[1])
+    else: sys.exit(__doc__)
+    argv = argv[2:]
+libs = {os.path.basename(p): bind(p) for p in argv}
 shapes = [("2a 128x256", (128, 128), (256, 256)), ("R=100 H=200", (100, 100), (200, 200)), ("ragged", (32, 128), (64, 256)), ("R=151 H 200-400", (151, 151), (200, 400))]
 for name, rr, hr in shapes:
-    d = synth.gen_pairhmm_pairs_fast(1 << 20, 0x5EED0002, r_range=rr, h_range=hr)
+    d = synth.gen_pairhmm_pairs_fast(1 << 20, 0x5EED0002, r_range=rr, h_range=hr, hap_n_rate=hap_n_rate)
     inp, keep = ph.make_input(d)
     times = {k: [] for k in libs}; outs = {}
-    for rnd in range(3):
+    for rnd in range(rounds):
         for k, lib in libs.items():
             ctx = C.c_void_p(); assert lib.mgx_pairhmm_create(0, 0, C.byref(ctx)) == 0
             b = C.c_void_p(); assert lib.mgx_pairhmm_batch_create(ctx, C.byref(inp), C.byref(b)) == 0
@@ -35,8 +43,10 @@ for name, rr, hr in shapes:
             lib.mgx_pairhmm_sync(ctx)
             times[k].append((time.perf_counter() - t0) / 10)
             if rnd == 0:
-                o = np.empty(1 << 20); lib.mgx_pairhmm_batch_results(ctx, b, o.ctypes.data, None); outs[k] = o
+                o = np.empty(1 << 20); u = np.zeros(1 << 20, dtype=np.uint8)
+                lib.mgx_pairhmm_batch_results(ctx, b, o.ctypes.data, u.ctypes.data); outs[k] = (o, u)
             lib.mgx_pairhmm_batch_destroy(ctx, b); lib.mgx_pairhmm_destroy(ctx)
     ks = list(libs)
-    same = all(np.array_equal(outs[ks[0]], outs[k]) for k in ks[1:])
-    print(f"{name:18s} identical outputs: {same}; " + "; ".join(f"{k} {np.median(times[k]) * 1e3:.3f} ms = {d['cells'] / np.median(times[k]) / 1e9:.0f} GCUPS" for k in ks), flush=True)
+    same = all(outs[ks[0]][0].tobytes() == outs[k][0].tobytes() and np.array_equal(outs[ks[0]][1], outs[k][1]) for k in ks[1:])
+    print(f"{name:18s} identical outputs and flags: {same}; " + "; ".join(
+        f"{k} {np.median(times[k]) * 1e3:.3f} ms (spread {(max(times[k]) - min(times[k])) * 1e3:.3f}) = {d['cells'] / np.median(times[k]) / 1e9:.0f} GCUPS" for k in ks), flush=True)
