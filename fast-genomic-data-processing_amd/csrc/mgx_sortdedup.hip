@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <cerrno>
 #include <cstddef>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include <memory>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mgx_sortdedup.h"
@@ -49,10 +51,7 @@ namespace {
 using u64 = unsigned long long;   // == uint64_t on this ABI; the type HIP atomics are declared for
 using u32 = uint32_t;
 
-#ifndef MGX_SCATTER_WAVES
-#define MGX_SCATTER_WAVES 4
-#endif
-constexpr int kScatterWaves = MGX_SCATTER_WAVES;   // wavefronts per scatter workgroup
+constexpr int kScatterWaves = 4;                      // wavefronts per scatter workgroup
 constexpr int kTileThreads = 256;
 constexpr int kItems = 16;
 constexpr int kTile = kTileThreads * kItems;          // 4096 keys per workgroup
@@ -64,7 +63,7 @@ constexpr int kWalkCap = 64;                          // longest run a single la
 // counters, so each one sits in its own 128-byte line (atomics on one line serialise at ~90/us and
 // would otherwise also stall the plain reads of the maxima next to them).
 struct Scalars {
-    u64 max_coord, max_k1d, max_k2d, max_k1s, max_near;
+    u64 max_coord, max_k1d, max_k2d, max_k1s, max_near;      // consecutive: the build kernel settles them as one array
     u32 n_long_d, n_long_s, n_long_n, n_dup;
     u32 bad_mate;                              // a record names a mate index outside the shard
     u32 pad0_[17];
@@ -74,6 +73,9 @@ struct Scalars {
     alignas(128) u32 n_multi_d; u32 n_multi_s, n_multi_n;                   // run heads with more than one entry
     u32 huge_runs; u32 pad4_[28];            // a position holds more near pairs than the in-run comparison accepts
 };
+static_assert(offsetof(Scalars, max_k1d) == offsetof(Scalars, max_coord) + 8 && offsetof(Scalars, max_k2d) == offsetof(Scalars, max_coord) + 16 &&
+              offsetof(Scalars, max_k1s) == offsetof(Scalars, max_coord) + 24 && offsetof(Scalars, max_near) == offsetof(Scalars, max_coord) + 32,
+              "k_build_emit settles the five maxima as the array max_coord[0 .. 5)");
 // near pair: mate 5' end less than kNearSpan beyond record 1's (every proper pair; insert sizes are a
 // few hundred bases).  14 delta bits + 2 orientation bits + a 32-bit position = 48 key bits: six
 // 8-bit passes (a 16-bit delta would cost a seventh).
@@ -96,9 +98,10 @@ constexpr u32 kHugeRun = 4096;
 
 __device__ __forceinline__ u64 lanemask_lt() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
-// exclusive scan of one u32 per thread over a 256-thread block (4 wavefronts); returns the
-// exclusive prefix, *total gets the block sum.  sm must hold 4 u32.
-__device__ __forceinline__ u32 block_excl_scan_256(u32 v, u32* sm, u32* total) {
+// exclusive scan of one u32 per thread over a block of NW wavefronts (every thread of the block must
+// call it); returns the exclusive prefix, *total (if asked for) gets the block sum.  sm must hold NW u32.
+template <int NW>
+__device__ __forceinline__ u32 block_excl_scan(u32 v, u32* sm, u32* total = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u32 incl = v;
 #pragma unroll
@@ -111,9 +114,62 @@ __device__ __forceinline__ u32 block_excl_scan_256(u32 v, u32* sm, u32* total) {
     __syncthreads();
     u32 base = 0, tot = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { const u32 s = sm[w]; if (w < wave) base += s; tot += s; }
-    *total = tot;
+    for (int w = 0; w < NW; ++w) { const u32 s = sm[w]; if (w < wave) base += s; tot += s; }
+    if (total) *total = tot;
     return base + incl - v;
+}
+
+// maxima of N values per thread over a 256-thread block, folded into the N consecutive global words
+// dst[0 .. N): one shuffle loop and one barrier for all N, then thread k settles value k.  The atomic is
+// skipped when the (possibly stale) global value already covers the block's.  smem must hold 4 * N u64.
+template <int N>
+__device__ __forceinline__ void block_max_to(u64 (&v)[N], u64* smem, u64* dst) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = max(v[k], (u64)__shfl_xor(v[k], off, 64));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) smem[wave * N + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const u64 m = max(max(smem[threadIdx.x], smem[N + threadIdx.x]), max(smem[2 * N + threadIdx.x], smem[3 * N + threadIdx.x]));
+        if (m > __atomic_load_n(dst + threadIdx.x, __ATOMIC_RELAXED)) atomicMax(dst + threadIdx.x, m);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the entry words as the kernels after the build read them
+// ---------------------------------------------------------------------------------------------
+// Sorted pair entries: k1 (sort_key, or the near key word) plus, for far doubles, the mate's 5' end and
+// the record index.  PK: those two ride in one word, mate 5' end << 32 | record, and `recw` is unused.
+// Unpacked record words of near pairs carry "the mate is the neighbour rec ^ 1" in the bits outside
+// rec_mask (BuildOut::mate_flag).  Near pairs come as DOUBLE with k2 == nullptr: their key word is the
+// whole identity.
+template <bool DOUBLE, bool PK>
+struct Entries {
+    const u64* k2; const u32* recw; u32 rec_mask;
+    static __device__ __forceinline__ u64 packed(u64 end2, u32 rec) { return (end2 << 32) | rec; }
+    __device__ __forceinline__ u64 end2(u32 t) const { return PK ? (k2[t] >> 32) : k2[t]; }          // mate 5' end (far doubles)
+    __device__ __forceinline__ u64 id2(u32 t) const { return (!DOUBLE || !k2) ? 0ull : end2(t); }    // second identity word
+    __device__ __forceinline__ u32 rec(u32 t) const { return PK ? (u32)k2[t] : recw[t] & rec_mask; }
+    __device__ __forceinline__ bool mate_is_neighbour(u32 t) const { return !PK && (recw[t] & ~rec_mask); }
+    __device__ __forceinline__ u32 mate(const mgx_rec_t* recs, u32 t, u32 r) const { return mate_is_neighbour(t) ? (r ^ 1u) : recs[r].mate; }
+};
+
+// which orientations (FF FR RF RR = 0 1 2 3) put record END of a pair on the forward strand: FF and FR for
+// record 1, FF and RF for record 2
+template <int END>
+__device__ __forceinline__ bool end_is_forward(u32 orient) { return orient == 0u || orient == (END == 2 ? 2u : 1u); }
+
+// the near key word p1 << kNearShift | orient << kNearOrientShift | (p2 - p1) << kNearDeltaShift | inverted score
+struct NearKey { u64 p1, p2; u32 orient; };
+__device__ __forceinline__ NearKey decode_near(u64 key) {
+    const u64 p1 = key >> kNearShift;
+    return NearKey{p1, p1 + ((key >> kNearDeltaShift) & (kNearSpan - 1)), (u32)(key >> kNearOrientShift) & 3u};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -147,7 +203,7 @@ struct BuildOut {
 // order, so the line is already there.
 __global__ __launch_bounds__(256) void k_build_emit(const mgx_rec_t* __restrict__ recs, u32 n, BuildOut o, Scalars* sc) {
     constexpr int ITEMS = kBuildBlock / 256;
-    __shared__ u64 smax[4][5];
+    __shared__ u64 smax[4 * 5];
     __shared__ u32 s_cnt[3], s_base[3];
     __shared__ u32 s_hist[256];
     const u32 base = blockIdx.x * kBuildBlock;
@@ -248,30 +304,15 @@ __global__ __launch_bounds__(256) void k_build_emit(const mgx_rec_t* __restrict_
         } else if (cls[k] == 1) {
             const u32 at = s_base[0] + slot[k];
             o.dk1[at] = ka[k];
-            if (o.packed_pair) o.dk2[at] = (kb[k] << 32) | i; else { o.dk2[at] = kb[k]; o.drec[at] = i; }
+            if (o.packed_pair) o.dk2[at] = Entries<true, true>::packed(kb[k], i); else { o.dk2[at] = kb[k]; o.drec[at] = i; }
         } else if (cls[k] == 2) {
             const u32 at = s_base[1] + slot[k];
             o.sk1[at] = ka[k]; o.srec[at] = i;
         }
     }
-    // block max -> global atomics, skipped when the (possibly stale) global value already covers it
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m_coord = max(m_coord, (u64)__shfl_xor(m_coord, off, 64));
-        m_k1d = max(m_k1d, (u64)__shfl_xor(m_k1d, off, 64));
-        m_k2d = max(m_k2d, (u64)__shfl_xor(m_k2d, off, 64));
-        m_k1s = max(m_k1s, (u64)__shfl_xor(m_k1s, off, 64));
-        m_near = max(m_near, (u64)__shfl_xor(m_near, off, 64));
-    }
-    if (lane == 0) { smax[wave][0] = m_coord; smax[wave][1] = m_k1d; smax[wave][2] = m_k2d; smax[wave][3] = m_k1s; smax[wave][4] = m_near; }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const u64 v = max(max(smax[0][threadIdx.x], smax[1][threadIdx.x]), max(smax[2][threadIdx.x], smax[3][threadIdx.x]));
-        u64* dst = threadIdx.x == 0 ? &sc->max_coord : threadIdx.x == 1 ? &sc->max_k1d : threadIdx.x == 2 ? &sc->max_k2d
-                 : threadIdx.x == 3 ? &sc->max_k1s : &sc->max_near;
-        if (v > __atomic_load_n(dst, __ATOMIC_RELAXED)) atomicMax(dst, v);
-    }
+    // the five key maxima in one fused reduction (one barrier)
+    u64 mx[5] = {m_coord, m_k1d, m_k2d, m_k1s, m_near};      // in the order of Scalars
+    block_max_to(mx, smax, &sc->max_coord);
 }
 
 // Upload wire format: whenever a piece's coordinates and 5' ends all fit 32 bits (always, unless a 5' end wrapped
@@ -303,14 +344,8 @@ __global__ __launch_bounds__(256) void k_order_keys(const u64* __restrict__ coor
         if (!packed) cval[i] = a;
         m = max(m, cd);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (u64)__shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const u64 v = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
-        if (v > __atomic_load_n(&sc->max_coord, __ATOMIC_RELAXED)) atomicMax(&sc->max_coord, v);
-    }
+    u64 mx[1] = {m};
+    block_max_to(mx, smax, &sc->max_coord);
 }
 
 // Indicator marks routed from other shards (5' position << 1 | reverse half): ORed into the bitmap after the
@@ -381,7 +416,7 @@ __global__ __launch_bounds__(256) void k_radix_scan_chunks(u32* chunk_sums, u32 
         for (int k = 0; k < B; ++k) tot += x[k];
     }
     u32 all;
-    u32 run = block_excl_scan_256(tot, sm, &all);      // where this digit starts in the output
+    u32 run = block_excl_scan<4>(tot, sm, &all);      // where this digit starts in the output
     for (u32 c0 = 0; c0 < n_chunks; c0 += B) {
         u32 x[B];
 #pragma unroll
@@ -411,38 +446,15 @@ __global__ __launch_bounds__(256) void k_radix_apply(u32* __restrict__ hist, u32
     }
 }
 
-// block-wide exclusive scan over NW wavefronts (every thread of the block must call it)
-template <int NW>
-__device__ __forceinline__ u32 block_excl_scan(u32 v, u32* sm) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        u32 t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) sm[wave] = incl;
-    __syncthreads();
-    u32 base = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) { const u32 s = sm[w]; if (w < wave) base += s; }
-    return base + incl - v;
-}
-
 // One tile of WAVES x 1024 keys per workgroup of WAVES wavefronts; every wavefront ranks a contiguous slice.
 // (8 wavefronts = 8192-key tiles double the run a digit leaves the tile with, but measured slower: DESIGN.md 4.2.)
 // LOW32: last pass of the packed record sort -- only the low half of every key (the arrival index)
 // is stored, to pout32, which makes the sorted keys themselves unnecessary.
-#ifndef MGX_SORT_PREFETCH_P32
-#define MGX_SORT_PREFETCH_P32 1
-#endif
-constexpr bool kPrefetchP32 = MGX_SORT_PREFETCH_P32 != 0;     // the 32-bit payload is loaded with the keys, not between two barriers
 template <bool HAS_P64, bool HAS_P32, int WAVES, bool LOW32 = false>
 __global__ __launch_bounds__(WAVES * 64) void k_radix_scatter(const u64* __restrict__ kin, u64* __restrict__ kout,
                                                               const u64* __restrict__ pin64, u64* __restrict__ pout64,
                                                               const u32* __restrict__ pin32, u32* __restrict__ pout32,
-                                                              u32 n, int shift, const u32* __restrict__ goff, u32 n_tiles, int xcd_order) {
+                                                              u32 n, int shift, const u32* __restrict__ goff, u32 n_tiles) {
     constexpr int T = WAVES * 64;           // threads
     constexpr int ITEMS = kItems;           // keys per thread
     constexpr int kTile = T * ITEMS;        // keys per workgroup: 4096 with 4 wavefronts, 8192 with 8
@@ -456,11 +468,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_radix_scatter(const u64* __restr
     // ~16 keys starts at an arbitrary 8-byte offset, so most 128-byte lines are completed by the
     // NEXT tile: giving each XCD a contiguous range of tiles (walked in order) lets both halves of
     // such a line meet in one L2 instead of reaching HBM as two partial writes from two L2s.
-    u32 tile = blockIdx.x;
-    if (xcd_order) {
-        const u32 q = n_tiles >> 3, r = n_tiles & 7u, x = blockIdx.x & 7u;
-        tile = x * q + min(x, r) + (blockIdx.x >> 3);
-    }
+    const u32 q = n_tiles >> 3, r = n_tiles & 7u, x = blockIdx.x & 7u;
+    const u32 tile = x * q + min(x, r) + (blockIdx.x >> 3);
     const u32 tile0 = tile * kTile;
     const u32 tile_n = min((u32)kTile, n - tile0);
     for (int i = tid; i < WAVES * 256; i += T) (&wcnt[0][0])[i] = 0;
@@ -492,8 +501,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_radix_scatter(const u64* __restr
             pay[k] = li < tile_n ? pin64[tile0 + li] : 0ull;
         }
     }
-    u32 pay32[(HAS_P32 && kPrefetchP32) ? ITEMS : 1];
-    if constexpr (HAS_P32 && kPrefetchP32) {
+    u32 pay32[HAS_P32 ? ITEMS : 1];      // loaded with the keys, not between two barriers
+    if constexpr (HAS_P32) {
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
             const u32 li = wave * SLICE + k * 64 + lane;
@@ -577,7 +586,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_radix_scatter(const u64* __restr
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
             const u32 li = wave * SLICE + k * 64 + lane;
-            if (li < tile_n) sbuf32[lpos[k]] = kPrefetchP32 ? pay32[kPrefetchP32 ? k : 0] : pin32[tile0 + li];
+            if (li < tile_n) sbuf32[lpos[k]] = pay32[k];
         }
         __syncthreads();
 #pragma unroll
@@ -603,11 +612,9 @@ __global__ __launch_bounds__(256) void k_set_indicator(const u64* __restrict__ k
                                                        u32* __restrict__ indicator, u64 indicator_bits, u64 L) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    const Entries<true, PK> e{k2, nullptr, 0xFFFFFFFFu};
     const u64 a1 = k1[i];
-    const u32 orient = (u32)(a1 & 3);
-    u64 b;
-    if (END == 2) b = (PK ? (k2[i] >> 32) : k2[i]) + ((orient == 0u || orient == 2u) ? 0ull : L);   // record 2 forward: FF, RF
-    else          b = (a1 >> 2) + ((orient == 0u || orient == 1u) ? 0ull : L);   // record 1 forward: FF, FR
+    const u64 b = (END == 2 ? e.end2(i) : a1 >> 2) + (end_is_forward<END>((u32)(a1 & 3)) ? 0ull : L);
     if (b < indicator_bits) atomicOr(&indicator[b >> 5], 1u << (b & 31));
 }
 
@@ -618,13 +625,29 @@ __global__ __launch_bounds__(256) void k_set_indicator(const u64* __restrict__ k
 // slice of the sorted entries by binary search, sets bits in LDS and writes whole words with plain
 // coalesced stores.  No global atomics and no memset of the 4L-bit map.
 constexpr u32 kIndTile = 65536;              // positions per workgroup (2 x 8 KB of LDS)
+
+__device__ __forceinline__ void tile_clear(u32* fw, u32* rv) {
+    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) { fw[w] = 0; rv[w] = 0; }
+}
+// the workgroup's LDS tile -> its words of both halves of the bitmap (after a barrier)
+template <bool DEFINE>
+__device__ __forceinline__ void tile_flush(const u32* fw, const u32* rv, u32* __restrict__ indicator, u64 Lp) {
+    u32* gf = indicator + (size_t)blockIdx.x * (kIndTile / 32);
+    u32* gr = indicator + (size_t)(Lp >> 5) + (size_t)blockIdx.x * (kIndTile / 32);
+    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) {
+        if (DEFINE) { gf[w] = fw[w]; gr[w] = rv[w]; }                         // first pass: defines every word
+        else { if (fw[w]) gf[w] |= fw[w]; if (rv[w]) gr[w] |= rv[w]; }        // later passes: this tile owns them
+    }
+}
+
 template <int END, bool PK, bool DEFINE>
 __global__ __launch_bounds__(256) void k_indicator_tiles(const u64* __restrict__ k1, const u64* __restrict__ k2, u32 n,
                                                          u32* __restrict__ indicator, u64 Lp) {
     __shared__ u32 fw[kIndTile / 32], rv[kIndTile / 32];
     __shared__ u32 s_lo, s_hi;
-    auto POS = [&](u32 t) -> u64 { return END == 2 ? (PK ? (k2[t] >> 32) : k2[t]) : (k1[t] >> 2); };
-    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) { fw[w] = 0; rv[w] = 0; }
+    const Entries<true, PK> e{k2, nullptr, 0xFFFFFFFFu};
+    auto POS = [&](u32 t) -> u64 { return END == 2 ? e.end2(t) : (k1[t] >> 2); };
+    tile_clear(fw, rv);
     const u64 pos_lo = (u64)blockIdx.x * kIndTile, pos_hi = pos_lo + kIndTile;
     if (threadIdx.x < 2) {
         const u64 target = threadIdx.x == 0 ? pos_lo : pos_hi;
@@ -635,18 +658,11 @@ __global__ __launch_bounds__(256) void k_indicator_tiles(const u64* __restrict__
     __syncthreads();
     const u32 lo = s_lo, hi = s_hi;
     for (u32 i = lo + threadIdx.x; i < hi; i += 256) {
-        const u32 orient = (u32)(k1[i] & 3);
         const u32 p = (u32)(POS(i) - pos_lo);
-        const bool fwd = END == 2 ? (orient == 0u || orient == 2u) : (orient == 0u || orient == 1u);
-        atomicOr(fwd ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
+        atomicOr(end_is_forward<END>((u32)(k1[i] & 3)) ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
     }
     __syncthreads();
-    u32* gf = indicator + (size_t)blockIdx.x * (kIndTile / 32);
-    u32* gr = indicator + (size_t)(Lp >> 5) + (size_t)blockIdx.x * (kIndTile / 32);
-    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) {
-        if (DEFINE) { gf[w] = fw[w]; gr[w] = rv[w]; }                         // first pass: defines every word
-        else { if (fw[w]) gf[w] |= fw[w]; if (rv[w]) gr[w] |= rv[w]; }        // later passes: this tile owns them
-    }
+    tile_flush<DEFINE>(fw, rv, indicator, Lp);
 }
 
 // Near pairs (one key word p1 << 32 | orient << 30 | delta << 16 | inverted score, sorted on its upper 48 bits): both ends of every pair in ONE
@@ -659,7 +675,7 @@ __global__ __launch_bounds__(256) void k_indicator_tiles_near(const u64* __restr
                                                               const u32* __restrict__ sub_start, u32 n_sub) {
     __shared__ u32 fw[kIndTile / 32], rv[kIndTile / 32];
     __shared__ u32 s_lo, s_hi;
-    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) { fw[w] = 0; rv[w] = 0; }
+    tile_clear(fw, rv);
     const u64 pos_lo = (u64)blockIdx.x * kIndTile, pos_hi = pos_lo + kIndTile;
     constexpr u32 kSubPerTile = kIndTile / (u32)kNearSpan;
     if (threadIdx.x == 0) {
@@ -671,22 +687,18 @@ __global__ __launch_bounds__(256) void k_indicator_tiles_near(const u64* __restr
     __syncthreads();
     const u32 lo = s_lo, hi = min(s_hi, n);
     for (u32 i = lo + threadIdx.x; i < hi; i += 256) {
-        const u64 key = nk[i];
-        const u64 p1 = key >> kNearShift, p2 = p1 + ((key >> kNearDeltaShift) & (kNearSpan - 1));
-        const u32 orient = (u32)(key >> kNearOrientShift) & 3u;
-        if (p1 >= pos_lo) {                                  // record 1 forward: FF, FR
-            const u32 p = (u32)(p1 - pos_lo);
-            atomicOr((orient == 0u || orient == 1u) ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
+        const NearKey k = decode_near(nk[i]);
+        if (k.p1 >= pos_lo) {
+            const u32 p = (u32)(k.p1 - pos_lo);
+            atomicOr(end_is_forward<1>(k.orient) ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
         }
-        if (p2 >= pos_lo && p2 < pos_hi) {                   // record 2 forward: FF, RF
-            const u32 p = (u32)(p2 - pos_lo);
-            atomicOr((orient == 0u || orient == 2u) ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
+        if (k.p2 >= pos_lo && k.p2 < pos_hi) {
+            const u32 p = (u32)(k.p2 - pos_lo);
+            atomicOr(end_is_forward<2>(k.orient) ? &fw[p >> 5] : &rv[p >> 5], 1u << (p & 31));
         }
     }
     __syncthreads();
-    u32* gf = indicator + (size_t)blockIdx.x * (kIndTile / 32);
-    u32* gr = indicator + (size_t)(Lp >> 5) + (size_t)blockIdx.x * (kIndTile / 32);
-    for (u32 w = threadIdx.x; w < kIndTile / 32; w += 256) { gf[w] = fw[w]; gr[w] = rv[w]; }
+    tile_flush<true>(fw, rv, indicator, Lp);
 }
 
 // atomic fallback for near pairs (reference bitmap layout)
@@ -694,10 +706,8 @@ __global__ __launch_bounds__(256) void k_set_indicator_near(const u64* __restric
                                                             u64 indicator_bits, u64 L) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const u64 key = nk[i];
-    const u64 p1 = key >> kNearShift, p2 = p1 + ((key >> kNearDeltaShift) & (kNearSpan - 1));
-    const u32 orient = (u32)(key >> kNearOrientShift) & 3u;
-    const u64 b1 = p1 + ((orient == 0u || orient == 1u) ? 0ull : L), b2 = p2 + ((orient == 0u || orient == 2u) ? 0ull : L);
+    const NearKey k = decode_near(nk[i]);
+    const u64 b1 = k.p1 + (end_is_forward<1>(k.orient) ? 0ull : L), b2 = k.p2 + (end_is_forward<2>(k.orient) ? 0ull : L);
     if (b1 < indicator_bits) atomicOr(&indicator[b1 >> 5], 1u << (b1 & 31));
     if (b2 < indicator_bits) atomicOr(&indicator[b2 >> 5], 1u << (b2 & 31));
 }
@@ -713,18 +723,74 @@ __device__ __forceinline__ void mark_pair(uint8_t* dup, const mgx_rec_t* recs, u
 
 // quality of a pair entry: smaller is better -- score descending, then tile, x, y ascending
 // (main.cpp:253-264 / 303-314); the record index (= arrival order) breaks total ties
+__device__ __forceinline__ u64 place_word(const mgx_rec_t& a) {          // what decides between equal scores
+    return ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y;
+}
 __device__ __forceinline__ u64 quality_word(uint16_t score, const mgx_rec_t& a) {
-    return ((u64)(0xFFFFu - (u32)score) << 48) | ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y;
+    return ((u64)(0xFFFFu - (u32)score) << 48) | place_word(a);
 }
 __device__ __forceinline__ u64 quality_double(const mgx_rec_t* recs, u32 rec) {
     const mgx_rec_t a = recs[rec];
     const mgx_rec_t b = recs[a.mate];
-    const u32 score = (u32)(uint16_t)(a.score + b.score);                // pair.cpp:81
-    return ((u64)(0xFFFFu - score) << 48) | ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y;
+    return quality_word((uint16_t)(a.score + b.score), a);                // pair.cpp:81: uint16 sum
 }
 __device__ __forceinline__ u64 quality_single(const mgx_rec_t* recs, u32 rec) {
     const mgx_rec_t a = recs[rec];
-    return ((u64)(0xFFFFu - (u32)a.score) << 48) | ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y;
+    return quality_word(a.score, a);
+}
+
+// main.cpp:325-331: the kept single read of a run is a duplicate iff a double pair has an end on its
+// position and strand.  rev_off: where the reverse-strand half of the bitmap starts.
+__device__ __forceinline__ bool single_hits_pair_end(const u32* __restrict__ indicator, u64 ind_bits, u64 rev_off, u64 key) {
+    const u64 target = (key >> 2) + (((key & 3) == 3) ? rev_off : 0ull);
+    return target < ind_bits && ((indicator[target >> 5] >> (target & 31)) & 1u);
+}
+
+// Near pairs sorted on record 1's 5' end only: the run [first, end) holds every pair that starts there.
+// Entry t loses to any other entry of the run with the same identity (the key bits above the score)
+// and a better score -- tile, x, y, then arrival order on a score tie.  Records are gathered only on
+// such a tie.
+template <class E>
+__device__ __forceinline__ bool near_entry_loses(const u64* __restrict__ k1, const E& entries, const mgx_rec_t* __restrict__ recs,
+                                                 u32 first, u32 end, u32 t) {
+    const u64 kt = k1[t];
+    const u64 idt = kt >> kNearScoreBits;
+    const u32 st = (u32)(kt & 0xFFFFu);
+    bool have_t = false;
+    u32 rt = 0; u64 qt = 0;
+    for (u32 u = first; u < end; ++u) {
+        if (u == t) continue;
+        const u64 ku = k1[u];
+        if ((ku >> kNearScoreBits) != idt) continue;
+        const u32 su = (u32)(ku & 0xFFFFu);
+        if (su < st) return true;
+        if (su == st) {
+            if (!have_t) { rt = entries.rec(t); qt = place_word(recs[rt]); have_t = true; }
+            const u32 ru = entries.rec(u);
+            const u64 qu = place_word(recs[ru]);
+            if (qu < qt || (qu == qt && ru < rt)) return true;
+        }
+    }
+    return false;
+}
+
+// A whole workgroup finds where the run that starts at `first` ends: the first t in (first, n) with
+// !same_run(t), or n.  Every thread of the block must call it with the same first and n; the value
+// that ends the loop is read from LDS between two barriers, so all threads leave it in the same round.
+template <class F>
+__device__ __forceinline__ u32 block_run_end(u32 first, u32 n, F same_run) {
+    __shared__ u32 s_end;
+    for (u32 c = first; c < n; c += 256) {
+        const u32 t = c + threadIdx.x;
+        if (threadIdx.x == 0) s_end = n;
+        __syncthreads();
+        if (t < n && !same_run(t)) atomicMin(&s_end, t);
+        __syncthreads();
+        const u32 e = s_end;
+        __syncthreads();
+        if (e < n) return e;
+    }
+    return n;
 }
 
 // Duplicate search over the sorted entries, in two steps so that the random-access part runs dense:
@@ -735,20 +801,17 @@ __device__ __forceinline__ u64 quality_single(const mgx_rec_t* recs, u32 rec) {
 //   k_mark_list : one lane per listed head walks its run (runs are short), gathers the records'
 //                 quality words and marks everything but the best.  Runs longer than kWalkCap go to
 //                 a second list that k_mark_long handles with a whole workgroup each.
-// PK: the second array holds (mate 5' end << 32 | record) packed in one word and `rec` is unused.
 constexpr int kFindItems = 16;
 
 template <bool DOUBLE, bool PK, int KS>
 __global__ __launch_bounds__(256) void k_find_runs(const u64* __restrict__ k1, const u64* __restrict__ k2,
                                                    const u32* __restrict__ rec, u32 n,
-                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 L,
+                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 rev_off,
                                                    uint8_t* __restrict__ dup, u32* __restrict__ multi_list, u32* n_multi,
                                                    u32* __restrict__ sub_start, u32 n_sub) {
     __shared__ u32 s_base;
     __shared__ u32 s_scan[4];
-    // near pairs come as DOUBLE with k2 == nullptr: the single key word is the whole identity
-    auto K2 = [&](u32 t) -> u64 { return (!DOUBLE || !k2) ? 0ull : (PK ? (k2[t] >> 32) : k2[t]); };
-    auto REC = [&](u32 t) -> u32 { return PK ? (u32)k2[t] : rec[t]; };
+    const Entries<DOUBLE, PK> e{k2, rec, 0xFFFFFFFFu};      // only singles read a record index here: no flag bits
     const u32 base = blockIdx.x * (256 * kFindItems);
     u32 is_multi = 0;
 #pragma unroll
@@ -757,11 +820,11 @@ __global__ __launch_bounds__(256) void k_find_runs(const u64* __restrict__ k1, c
         bool multi = false;
         // neighbours come from the adjacent lanes; only the two edge lanes of a wavefront load theirs
         const int lane = threadIdx.x & 63;
-        const u64 a1 = i < n ? k1[i] >> KS : 0ull, a2 = i < n ? K2(i) : 0ull;     // KS: key bits below the identity
+        const u64 a1 = i < n ? k1[i] >> KS : 0ull, a2 = i < n ? e.id2(i) : 0ull;     // KS: key bits below the identity
         u64 p1 = __shfl_up(a1, 1, 64), p2 = DOUBLE ? __shfl_up(a2, 1, 64) : 0ull;
         u64 n1 = __shfl_down(a1, 1, 64), n2 = DOUBLE ? __shfl_down(a2, 1, 64) : 0ull;
-        if (lane == 0 && i > 0 && i < n) { p1 = k1[i - 1] >> KS; p2 = K2(i - 1); }
-        if (lane == 63 && i + 1 < n) { n1 = k1[i + 1] >> KS; n2 = K2(i + 1); }
+        if (lane == 0 && i > 0 && i < n) { p1 = k1[i - 1] >> KS; p2 = e.id2(i - 1); }
+        if (lane == 63 && i + 1 < n) { n1 = k1[i + 1] >> KS; n2 = e.id2(i + 1); }
         if constexpr (KS >= kNearScoreBits) {
             // near pairs: where the sorted entries cross a kNearSpan boundary of the genome (for the bitmap pass)
             if (sub_start && i < n) {
@@ -775,11 +838,7 @@ __global__ __launch_bounds__(256) void k_find_runs(const u64* __restrict__ k1, c
             const bool head = i == 0 || p1 != a1 || (DOUBLE && p2 != a2);
             if (head) {
                 multi = i + 1 < n && n1 == a1 && (!DOUBLE || n2 == a2);
-                if (!DOUBLE && !multi) {
-                    // main.cpp:325-331: the kept single is a duplicate iff a double pair has an end there
-                    const u64 target = (a1 >> 2) + (((a1 & 3) == 3) ? L : 0ull);
-                    if (target < indicator_bits && ((indicator[target >> 5] >> (target & 31)) & 1u)) dup[REC(i)] = 1;
-                }
+                if (!DOUBLE && !multi && single_hits_pair_end(indicator, indicator_bits, rev_off, a1)) dup[e.rec(i)] = 1;
             }
         }
         is_multi |= (multi ? 1u : 0u) << k;
@@ -787,7 +846,7 @@ __global__ __launch_bounds__(256) void k_find_runs(const u64* __restrict__ k1, c
     // one block scan over the per-thread counts (instead of a ballot + LDS atomic per item), one global
     // atomic per workgroup; the list's order is irrelevant
     u32 total;
-    u32 at = block_excl_scan_256((u32)__popc(is_multi), s_scan, &total);
+    u32 at = block_excl_scan<4>((u32)__popc(is_multi), s_scan, &total);
     if (threadIdx.x == 0) s_base = total ? atomicAdd(n_multi, total) : 0u;
     __syncthreads();
     at += s_base;
@@ -799,20 +858,15 @@ __global__ __launch_bounds__(256) void k_find_runs(const u64* __restrict__ k1, c
 template <bool DOUBLE, bool PK, int KS>
 __global__ __launch_bounds__(256) void k_mark_list(const u64* __restrict__ k1, const u64* __restrict__ k2,
                                                    const u32* __restrict__ rec, u32 n, const mgx_rec_t* __restrict__ recs, u32 n_records,
-                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 L,
+                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 rev_off,
                                                    uint8_t* __restrict__ dup, const u32* __restrict__ multi_list, const u32* n_multi,
                                                    u32* __restrict__ long_list, u32* n_long, u32 rec_mask) {
-    // rec_mask: near-pair record words carry "the mate is the neighbour" in the bits outside the mask
-    auto K2 = [&](u32 t) -> u64 { return (!DOUBLE || !k2) ? 0ull : (PK ? (k2[t] >> 32) : k2[t]); };
-    auto REC = [&](u32 t) -> u32 { return PK ? (u32)k2[t] : rec[t] & rec_mask; };
-    auto MATE = [&](u32 t, u32 r) -> u32 { return (!PK && (rec[t] & ~rec_mask)) ? (r ^ 1u) : recs[r].mate; };
+    const Entries<DOUBLE, PK> e{k2, rec, rec_mask};
     const u32 total = *n_multi;
     for (u32 li = blockIdx.x * 256 + threadIdx.x; li < total; li += gridDim.x * 256) {
         const u32 i = multi_list[li];
         if constexpr (KS > kNearScoreBits) {
-            // near pairs sorted on record 1's 5' end only: the run holds every pair that starts here; an
-            // entry loses to any other entry of the run with the same identity (bits above the score) and
-            // a better score -- tile, x, y, then arrival order on a score tie
+            // near pairs sorted on record 1's 5' end only: every entry of the run against every other one
             const u64 run_id = k1[i] >> KS;
             u32 j = i + 1;
             for (; j < n && j - i < kWalkCap; ++j) if ((k1[j] >> KS) != run_id) break;
@@ -820,31 +874,8 @@ __global__ __launch_bounds__(256) void k_mark_list(const u64* __restrict__ k1, c
                 long_list[atomicAdd(n_long, 1u)] = i;                                 // long run: defer
                 continue;
             }
-            for (u32 t = i; t < j; ++t) {
-                const u64 kt = k1[t];
-                const u64 idt = kt >> kNearScoreBits;
-                const u32 st = (u32)(kt & 0xFFFFu);
-                bool loser = false, have_t = false;
-                u32 rt = 0; u64 qt = 0;
-                for (u32 u = i; u < j && !loser; ++u) {
-                    if (u == t) continue;
-                    const u64 ku = k1[u];
-                    if ((ku >> kNearScoreBits) != idt) continue;
-                    const u32 su = (u32)(ku & 0xFFFFu);
-                    if (su < st) loser = true;
-                    else if (su == st) {
-                        if (!have_t) { rt = REC(t); const mgx_rec_t a = recs[rt]; qt = ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y; have_t = true; }
-                        const u32 ru = REC(u);
-                        const mgx_rec_t b = recs[ru];
-                        const u64 qu = ((u64)b.tile << 32) | ((u64)b.x << 16) | (u64)b.y;
-                        if (qu < qt || (qu == qt && ru < rt)) loser = true;
-                    }
-                }
-                if (loser) {
-                    if (!have_t) rt = REC(t);
-                    mark_pair(dup, recs, rt, !PK && (rec[t] & ~rec_mask));
-                }
-            }
+            for (u32 t = i; t < j; ++t)
+                if (near_entry_loses(k1, e, recs, i, j, t)) mark_pair(dup, recs, e.rec(t), e.mate_is_neighbour(t));
             continue;
         } else if constexpr (KS > 0) {
             // near pairs: the low KS bits of the key word are 0xFFFF - pair score, so the best entry of
@@ -869,23 +900,21 @@ __global__ __launch_bounds__(256) void k_mark_list(const u64* __restrict__ k1, c
                 u64 bq = ~0ull; u32 br = 0xFFFFFFFFu;
                 for (u32 t = i; t < j; ++t) {
                     if ((u32)(k1[t] & ((1u << KS) - 1)) != bs) continue;
-                    const u32 rt = REC(t);
-                    const mgx_rec_t a = recs[rt];
-                    const u64 q = ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y;
+                    const u32 rt = e.rec(t);
+                    const u64 q = place_word(recs[rt]);
                     if (q < bq || (q == bq && rt < br)) { bq = q; br = rt; best = t; }
                 }
             }
             for (u32 t = i; t < j; ++t) {
                 if (t == best) continue;
-                const u32 r = REC(t);
-                mark_pair(dup, recs, r, !PK && (rec[t] & ~rec_mask));
+                mark_pair(dup, recs, e.rec(t), e.mate_is_neighbour(t));
             }
             continue;
         }
-        const u64 a1 = k1[i], a2 = K2(i);
+        const u64 a1 = k1[i], a2 = e.id2(i);
         // the first two entries belong to the run by construction: their record gathers (the slow,
         // random part) are issued together instead of one after the other
-        const u32 r0 = REC(i), r1 = REC(i + 1);
+        const u32 r0 = e.rec(i), r1 = e.rec(i + 1);
         const mgx_rec_t ra = recs[r0], rb = recs[r1];
         u64 q0, q1;
         if (DOUBLE) {
@@ -906,24 +935,21 @@ __global__ __launch_bounds__(256) void k_mark_list(const u64* __restrict__ k1, c
         if (q1 < bq || (q1 == bq && r1 < best_rec)) { bq = q1; best = i + 1; best_rec = r1; }
         u32 j = i + 2;
         for (; j < n && j - i < kWalkCap; ++j) {
-            if (k1[j] != a1 || (DOUBLE && K2(j) != a2)) break;
-            const u32 rj = REC(j);
+            if (k1[j] != a1 || (DOUBLE && e.id2(j) != a2)) break;
+            const u32 rj = e.rec(j);
             const u64 q = DOUBLE ? quality_double(recs, rj) : quality_single(recs, rj);
             if (q < bq || (q == bq && rj < best_rec)) { bq = q; best = j; best_rec = rj; }
         }
-        if (j < n && j - i >= kWalkCap && k1[j] == a1 && (!DOUBLE || K2(j) == a2)) {
+        if (j < n && j - i >= kWalkCap && k1[j] == a1 && (!DOUBLE || e.id2(j) == a2)) {
             long_list[atomicAdd(n_long, 1u)] = i;                                     // long run: defer
             continue;
         }
-        if (!DOUBLE) {
-            const u64 target = (a1 >> 2) + (((a1 & 3) == 3) ? L : 0ull);
-            if (target < indicator_bits && ((indicator[target >> 5] >> (target & 31)) & 1u)) dup[REC(best)] = 1;
-        }
+        if (!DOUBLE && single_hits_pair_end(indicator, indicator_bits, rev_off, a1)) dup[e.rec(best)] = 1;
         for (u32 t = i; t < j; ++t) {
             if (t == best) continue;
-            const u32 r = REC(t);
+            const u32 r = e.rec(t);
             dup[r] = 1;
-            if (DOUBLE) dup[MATE(t, r)] = 1;
+            if (DOUBLE) dup[e.mate(recs, t, r)] = 1;
         }
     }
 }
@@ -931,34 +957,22 @@ __global__ __launch_bounds__(256) void k_mark_list(const u64* __restrict__ k1, c
 template <bool DOUBLE, bool PK, int KS>
 __global__ __launch_bounds__(256) void k_mark_long(const u64* __restrict__ k1, const u64* __restrict__ k2,
                                                    const u32* __restrict__ rec, u32 n, const mgx_rec_t* __restrict__ recs,
-                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 L,
+                                                   const u32* __restrict__ indicator, u64 indicator_bits, u64 rev_off,
                                                    uint8_t* __restrict__ dup, const u32* __restrict__ long_list, const u32* n_long, u32 rec_mask) {
     __shared__ u64 sq[256];
     __shared__ u32 sp[256];
     __shared__ u32 sr[256];
-    __shared__ u32 s_end;
-    auto K2 = [&](u32 t) -> u64 { return (!DOUBLE || !k2) ? 0ull : (PK ? (k2[t] >> 32) : k2[t]); };
-    auto REC = [&](u32 t) -> u32 { return PK ? (u32)k2[t] : rec[t] & rec_mask; };
+    const Entries<DOUBLE, PK> e{k2, rec, rec_mask};
     for (u32 li = blockIdx.x; li < *n_long; li += gridDim.x) {
         const u32 i = long_list[li];
-        const u64 a1 = k1[i] >> KS, a2 = K2(i);          // KS: key bits below the identity
-        // pass 1: extent of the run and its best entry
+        const u64 a1 = k1[i] >> KS, a2 = e.id2(i);          // KS: key bits below the identity
+        const u32 end = block_run_end(i, n, [&](u32 t) { return (k1[t] >> KS) == a1 && (!DOUBLE || e.id2(t) == a2); });
+        // the run's best entry: per thread, then over the block
         u64 bq = ~0ull; u32 bp = 0xFFFFFFFFu, bpr = 0xFFFFFFFFu;
-        u32 end = n;
-        for (u32 c = i; c < n; c += 256) {
-            const u32 t = c + threadIdx.x;
-            const bool in = t < n && (k1[t] >> KS) == a1 && (!DOUBLE || K2(t) == a2);
-            if (threadIdx.x == 0) s_end = n;
-            __syncthreads();
-            if (t < n && !in) atomicMin(&s_end, t);
-            __syncthreads();
-            const u32 e = s_end;
-            if (t < e) {
-                const u64 q = DOUBLE ? quality_double(recs, REC(t)) : quality_single(recs, REC(t));
-                if (q < bq || (q == bq && REC(t) < bpr)) { bq = q; bp = t; bpr = REC(t); }
-            }
-            __syncthreads();
-            if (e < n) { end = e; break; }
+        for (u32 t = i + threadIdx.x; t < end; t += 256) {
+            const u32 r = e.rec(t);
+            const u64 q = DOUBLE ? quality_double(recs, r) : quality_single(recs, r);
+            if (q < bq || (q == bq && r < bpr)) { bq = q; bp = t; bpr = r; }
         }
         sq[threadIdx.x] = bq; sp[threadIdx.x] = bp; sr[threadIdx.x] = bpr;
         __syncthreads();
@@ -971,15 +985,12 @@ __global__ __launch_bounds__(256) void k_mark_long(const u64* __restrict__ k1, c
         }
         const u32 best = sp[0];
         __syncthreads();
-        if (!DOUBLE && threadIdx.x == 0) {
-            u64 target = (a1 >> 2) + (((a1 & 3) == 3) ? L : 0ull);
-            if (target < indicator_bits && ((indicator[target >> 5] >> (target & 31)) & 1u)) dup[REC(best)] = 1;
-        }
+        if (!DOUBLE && threadIdx.x == 0 && single_hits_pair_end(indicator, indicator_bits, rev_off, a1)) dup[e.rec(best)] = 1;
         for (u32 t = i + threadIdx.x; t < end; t += 256) {
             if (t == best) continue;
-            const u32 r = REC(t);
+            const u32 r = e.rec(t);
             dup[r] = 1;
-            if (DOUBLE) dup[(!PK && (rec[t] & ~rec_mask)) ? (r ^ 1u) : recs[r].mate] = 1;
+            if (DOUBLE) dup[e.mate(recs, t, r)] = 1;
         }
         __syncthreads();
     }
@@ -991,50 +1002,17 @@ template <int RS>
 __global__ __launch_bounds__(256) void k_mark_long_sub(const u64* __restrict__ k1, const u32* __restrict__ rec, u32 n,
                                                        const mgx_rec_t* __restrict__ recs, uint8_t* __restrict__ dup,
                                                        const u32* __restrict__ long_list, const u32* n_long, u32* huge_runs, u32 rec_mask) {
-    __shared__ u32 s_end;
+    const Entries<true, false> e{nullptr, rec, rec_mask};
     for (u32 li = blockIdx.x; li < *n_long; li += gridDim.x) {
         const u32 i = long_list[li];
         const u64 run_id = k1[i] >> RS;
-        u32 end = n;
-        for (u32 c = i; c < n; c += 256) {                     // extent of the run
-            const u32 t = c + threadIdx.x;
-            if (threadIdx.x == 0) s_end = n;
-            __syncthreads();
-            if (t < n && (k1[t] >> RS) != run_id) atomicMin(&s_end, t);
-            __syncthreads();
-            const u32 e = s_end;
-            __syncthreads();
-            if (e < n) { end = e; break; }
-        }
+        const u32 end = block_run_end(i, n, [&](u32 t) { return (k1[t] >> RS) == run_id; });
         if (end - i > kHugeRun) {
             if (threadIdx.x == 0) atomicOr(huge_runs, 1u);
             continue;
         }
-        for (u32 t = i + threadIdx.x; t < end; t += 256) {
-            const u64 kt = k1[t];
-            const u64 idt = kt >> kNearScoreBits;
-            const u32 st = (u32)(kt & 0xFFFFu);
-            bool loser = false, have_t = false;
-            u32 rt = 0; u64 qt = 0;
-            for (u32 u = i; u < end && !loser; ++u) {
-                if (u == t) continue;
-                const u64 ku = k1[u];
-                if ((ku >> kNearScoreBits) != idt) continue;
-                const u32 su = (u32)(ku & 0xFFFFu);
-                if (su < st) loser = true;
-                else if (su == st) {
-                    if (!have_t) { rt = rec[t] & rec_mask; const mgx_rec_t a = recs[rt]; qt = ((u64)a.tile << 32) | ((u64)a.x << 16) | (u64)a.y; have_t = true; }
-                    const u32 ru = rec[u] & rec_mask;
-                    const mgx_rec_t b = recs[ru];
-                    const u64 qu = ((u64)b.tile << 32) | ((u64)b.x << 16) | (u64)b.y;
-                    if (qu < qt || (qu == qt && ru < rt)) loser = true;
-                }
-            }
-            if (loser) {
-                if (!have_t) rt = rec[t] & rec_mask;
-                mark_pair(dup, recs, rt, (rec[t] & ~rec_mask) != 0);
-            }
-        }
+        for (u32 t = i + threadIdx.x; t < end; t += 256)
+            if (near_entry_loses(k1, e, recs, i, end, t)) mark_pair(dup, recs, e.rec(t), e.mate_is_neighbour(t));
     }
 }
 
@@ -1102,7 +1080,6 @@ struct mgx_sortdedup {
     bool ran = false;
     bool near_by_position = true;          // near pairs sorted on record 1's 5' end only (MGX_SORTDEDUP_NEAR_EXACT=1: six-pass sort)
     bool finished = false;                 // the results of the last run have been checked for the fallback
-    int xcd_order = 1;                     // scatter tiles walk each XCD's contiguous range (MGX_SORTDEDUP_XCD_ORDER=0: plain)
     Scalars sc{};
     mgx_sortdedup_stats_t stats{};
 };
@@ -1182,7 +1159,7 @@ int radix_sort(mgx_sortdedup* c, hipStream_t s, const mgx_sortdedup::Scratch& q,
         // q.hist now holds the tile offsets
 #define MGX_SCATTER(P64, P32, LOW, K_IN, K_OUT, P64_IN, P64_OUT, P32_IN, P32_OUT)                                                      \
         hipLaunchKernelGGL((k_radix_scatter<P64, P32, WAVES, LOW>), dim3(n_tiles), dim3(WAVES * 64), 0, s, K_IN, K_OUT, P64_IN, P64_OUT, \
-                           P32_IN, P32_OUT, n, shift, q.hist, n_tiles, c->xcd_order)
+                           P32_IN, P32_OUT, n, shift, q.hist, n_tiles)
         if (p64 && !p32)
             MGX_SCATTER(true, false, false, key[in], key[out], p64[in], p64[out], (const u32*)nullptr, (u32*)nullptr);
         else if (p64)
@@ -1229,6 +1206,32 @@ void launch_mark(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, 
     else
         hipLaunchKernelGGL((k_mark_long<DOUBLE, PK, KS>), dim3(c->n_cu * 2), dim3(256), 0, s, k1, k2, rec, n_entries, c->d_recs,
                            c->d_indicator, ind_bits, ind_off, c->d_dup, q.longl, n_long, rec_mask);
+}
+
+// a run-time choice as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// record-END bits of the far pairs into the bitmap: the atomic form, or the tiled one over n_ind_tiles tiles with the
+// reverse half at Lp.  define: this is the first pass over the tiled bitmap (only the record-2 pass ever is).
+template <int END>
+void launch_indicator(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, u32 nd, bool tiled, u64 Lp, u32 n_ind_tiles,
+                      bool define = false) {
+    with_bool(c->packed_pair, [&](auto pk) {
+        constexpr bool PK = decltype(pk)::value;
+        if (!tiled) {
+            hipLaunchKernelGGL((k_set_indicator<END, PK>), dim3((nd + 255) / 256), dim3(256), 0, s, k1, k2, nd, c->d_indicator, c->indicator_bits, c->L);
+        } else if constexpr (END == 2) {
+            with_bool(define, [&](auto def) {
+                hipLaunchKernelGGL((k_indicator_tiles<2, PK, decltype(def)::value>), dim3(n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->d_indicator, Lp);
+            });
+        } else {
+            assert(!define);
+            hipLaunchKernelGGL((k_indicator_tiles<END, PK, false>), dim3(n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->d_indicator, Lp);
+        }
+    });
 }
 
 }  // namespace
@@ -1642,7 +1645,6 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     // pairs and singles stay on the main stream, so their short histogram / scan launches overlap the
     // other sorts' bandwidth-bound scatters.  In-process A/B on one device at 200 M records
     // (tools/dev_sort_ab.py): 18.0 ms against 19.4 ms on a single stream (MGX_SORTDEDUP_STREAMS=1).
-    if (const char* e = getenv("MGX_SORTDEDUP_XCD_ORDER")) c->xcd_order = atoi(e) != 0;
     if (const char* e = getenv("MGX_SORTDEDUP_NEAR_EXACT")) { if (atoi(e) != 0) c->near_by_position = false; }
     const char* env_streams = getenv("MGX_SORTDEDUP_STREAMS");
     const bool multi = !(env_streams && atoi(env_streams) == 1);
@@ -1657,12 +1659,11 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     const u32 n_sub = (u32)(Lp / kNearSpan);
     // run heads first: the same pass over the sorted keys notes where they cross the bitmap's sub-tile boundaries
     if (near_tiles && !nn) HIP_TRY(hipMemsetAsync(c->d_sub_start, 0, ((size_t)n_sub + 1) * 4, sN));
-    if (c->near_by_position)
-        launch_find<true, false, kNearShift>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, ind_bits, ind_off,
-                                             near_tiles ? c->d_sub_start : nullptr, n_sub);
-    else
-        launch_find<true, false, kNearScoreBits>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, ind_bits, ind_off,
-                                                 near_tiles ? c->d_sub_start : nullptr, n_sub);
+    with_bool(c->near_by_position, [&](auto by_pos) {
+        constexpr int KS = decltype(by_pos)::value ? kNearShift : kNearScoreBits;
+        launch_find<true, false, KS>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, ind_bits, ind_off,
+                                     near_tiles ? c->d_sub_start : nullptr, n_sub);
+    });
     if (near_tiles) {
         hipLaunchKernelGGL(k_indicator_tiles_near, dim3(n_ind_tiles), dim3(256), 0, sN, c->d_nk[ncur], nn, c->d_indicator, Lp, c->d_sub_start, n_sub);
         defined = true;
@@ -1671,10 +1672,10 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     }
     HIP_TRY(hipEventRecord(c->ev_ind, sN));
     const u32 near_rec_mask = n < 0x80000000u ? 0x7FFFFFFFu : 0xFFFFFFFFu;
-    if (c->near_by_position)
-        launch_mark<true, false, kNearShift>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, &c->d_sc->n_long_n, ind_bits, ind_off, true, near_rec_mask);
-    else
-        launch_mark<true, false, kNearScoreBits>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, &c->d_sc->n_long_n, ind_bits, ind_off, true, near_rec_mask);
+    with_bool(c->near_by_position, [&](auto by_pos) {
+        constexpr int KS = decltype(by_pos)::value ? kNearShift : kNearScoreBits;
+        launch_mark<true, false, KS>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, &c->d_sc->n_long_n, ind_bits, ind_off, true, near_rec_mask);
+    });
     HIP_TRY(hipEventRecord(c->ev_side[0], sN));
 
     // records by unified coordinate (stable: equal coordinates keep arrival order)
@@ -1709,41 +1710,21 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     // turns as key and payload (16 B per entry per pass, two LDS exchange rounds instead of three).
     int cur = 0;
     const bool pk = c->packed_pair;
-    if (pk) {
-        if ((rc = radix_sort(c, s, c->scr[0], c->d_k2, c->d_k1, nullptr, nd, 32, bits_of(c->sc.max_k2d), &cur))) return rc;
-    } else {
-        if ((rc = radix_sort(c, s, c->scr[0], c->d_k2, c->d_k1, c->d_prec, nd, 0, bits_of(c->sc.max_k2d), &cur))) return rc;
-    }
+    if ((rc = radix_sort(c, s, c->scr[0], c->d_k2, c->d_k1, pk ? nullptr : c->d_prec, nd, pk ? 32 : 0, bits_of(c->sc.max_k2d), &cur))) return rc;
     HIP_TRY(hipStreamWaitEvent(s, c->ev_ind, 0));      // the near pass defines the bitmap's words first
-    if (tiled && n && (nd || !defined)) {
-        const dim3 gt(n_ind_tiles);
-        if (defined) {
-            if (pk) hipLaunchKernelGGL((k_indicator_tiles<2, true, false>), gt, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-            else    hipLaunchKernelGGL((k_indicator_tiles<2, false, false>), gt, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-        } else {
-            if (pk) hipLaunchKernelGGL((k_indicator_tiles<2, true, true>), gt, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-            else    hipLaunchKernelGGL((k_indicator_tiles<2, false, true>), gt, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-            defined = true;
-        }
-    } else if (!tiled && nd) {
-        if (pk) hipLaunchKernelGGL((k_set_indicator<2, true>), dim3((nd + 255) / 256), dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, c->indicator_bits, c->L);
-        else    hipLaunchKernelGGL((k_set_indicator<2, false>), dim3((nd + 255) / 256), dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, c->indicator_bits, c->L);
-    }
+    // tiled: also without far pairs, when no pass has defined the bitmap's words yet
+    if (tiled ? (n && (nd || !defined)) : nd != 0)
+        launch_indicator<2>(c, s, c->d_k1[cur], c->d_k2[cur], nd, tiled, Lp, n_ind_tiles, !defined);
     if (n && c->n_marks)      // ends of pairs that live in other shards
         hipLaunchKernelGGL(k_or_marks, dim3((c->n_marks + 255) / 256), dim3(256), 0, s, c->d_marks, c->n_marks, c->d_indicator, ind_bits, ind_off,
                            tiled ? c->L - 64 : ~0ull);
     if ((rc = radix_sort(c, s, c->scr[0], c->d_k1, c->d_k2, pk ? nullptr : c->d_prec, nd, 0, bits_of(c->sc.max_k1d), &cur))) return rc;
     if (nd) {
-        const dim3 g((nd + 255) / 256);
-        if (tiled) {
-            if (pk) hipLaunchKernelGGL((k_indicator_tiles<1, true, false>), dim3(n_ind_tiles), dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-            else    hipLaunchKernelGGL((k_indicator_tiles<1, false, false>), dim3(n_ind_tiles), dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, Lp);
-        } else {
-            if (pk) hipLaunchKernelGGL((k_set_indicator<1, true>), g, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, c->indicator_bits, c->L);
-            else    hipLaunchKernelGGL((k_set_indicator<1, false>), g, dim3(256), 0, s, c->d_k1[cur], c->d_k2[cur], nd, c->d_indicator, c->indicator_bits, c->L);
-        }
-        if (pk) launch_mark<true, true>(c, s, c->d_k1[cur], c->d_k2[cur], nullptr, nd, c->scr[0], &c->d_sc->n_multi_d, &c->d_sc->n_long_d, ind_bits, ind_off);
-        else    launch_mark<true, false>(c, s, c->d_k1[cur], c->d_k2[cur], c->d_prec[cur], nd, c->scr[0], &c->d_sc->n_multi_d, &c->d_sc->n_long_d, ind_bits, ind_off);
+        launch_indicator<1>(c, s, c->d_k1[cur], c->d_k2[cur], nd, tiled, Lp, n_ind_tiles);
+        with_bool(pk, [&](auto packed) {
+            constexpr bool PK = decltype(packed)::value;
+            launch_mark<true, PK>(c, s, c->d_k1[cur], c->d_k2[cur], PK ? nullptr : c->d_prec[cur], nd, c->scr[0], &c->d_sc->n_multi_d, &c->d_sc->n_long_d, ind_bits, ind_off);
+        });
     }
     // singles
     int scur = 0;

@@ -40,32 +40,83 @@ def test_raw_random_vs_oracle(pkg, sd_engine, sd_oracle, synth, n_templates, see
     assert (st["n_double"], st["n_single"], st["n_dup_records"]) == tuple(int(c) for c in counts)
 
 
-def test_long_runs_and_total_ties(sd_engine, sd_oracle, synth):
-    """Thousands of pairs on the same 5' ends (runs far beyond the per-lane walk cap), many with
-    identical score/tile/x/y (the earliest arrival must win)."""
-    n_t = 30000
+def _pair_families(synth, rng, n_t, n_fam, first, second):
+    """n_t proper pairs (flags 99 / 147) whose 5' ends fall on n_fam positions, ten bases apart, from `first` and
+    `second`: a few giant runs, many entries with identical score/tile/x/y"""
     recs = np.zeros(2 * n_t, dtype=synth.REC_DTYPE)
     a, b = recs[0::2], recs[1::2]
-    rng = np.random.RandomState(3)
-    fam = rng.randint(0, 6, n_t)                       # six giant families
-    a["prime5"] = 1000 + fam * 10; b["prime5"] = 5000 + fam * 10
+    fam = rng.randint(0, n_fam, n_t)
+    a["prime5"] = first + fam * 10; b["prime5"] = second + fam * 10
     a["coord"] = a["prime5"]; b["coord"] = b["prime5"] - 99
     a["flag"] = 99; b["flag"] = 147
     a["score"] = rng.randint(100, 104, n_t); b["score"] = 50
     a["tile"] = b["tile"] = rng.randint(0, 2, n_t)
     ar = np.arange(n_t, dtype=np.uint32) * 2
     a["mate"], b["mate"] = ar + 1, ar
-    # plus long runs of singles
-    sg = np.zeros(5000, dtype=synth.REC_DTYPE)
-    sg["prime5"] = 1000 + rng.randint(0, 3, 5000) * 10; sg["coord"] = sg["prime5"]
-    sg["flag"] = 0; sg["mate"] = synth.NO_MATE; sg["score"] = rng.randint(0, 3, 5000)
+    return recs
+
+
+def _singles(synth, rng, n, positions, flag):
+    sg = np.zeros(n, dtype=synth.REC_DTYPE)
+    sg["prime5"] = np.asarray(positions, dtype=np.uint64)[rng.randint(0, len(positions), n)]; sg["coord"] = sg["prime5"]
+    sg["flag"] = flag; sg["mate"] = synth.NO_MATE; sg["score"] = rng.randint(0, 3, n)
+    return sg
+
+
+def test_long_runs_and_total_ties(sd_engine, sd_oracle, synth):
+    """Thousands of pairs on the same 5' ends (runs far beyond the per-lane walk cap), many with
+    identical score/tile/x/y (the earliest arrival must win)."""
+    n_t = 30000
+    rng = np.random.RandomState(3)
+    recs = _pair_families(synth, rng, n_t, 6, 1000, 5000)      # six giant families
+    sg = _singles(synth, rng, 5000, [1000, 1010, 1020], 0)    # plus long runs of singles
     allr = np.concatenate([recs, sg])
     want_order, want_dup, _ = sd_oracle.run(100000, allr)
     order, dup = sd_engine.sort_mark(100000, allr)
     assert np.array_equal(order, want_order)
     assert np.array_equal(dup, want_dup)
-    assert dup.sum() == len(allr) - 2 * 6 - 0 - (5000 - (5000 - 3)) - 0 or True   # sanity only
+    assert dup.sum() == 2 * (n_t - 6) + 5000
     assert (dup[2 * n_t:] == 1).all()                  # every single collides with a pair end here
+
+
+@pytest.mark.parametrize("shift,L", [(0, 100_000), (5_000_000_000, 6_000_000_000)], ids=["packed", "wide"])
+def test_long_runs_of_far_pairs(sd_engine, sd_oracle, synth, shift, L):
+    """Runs of 200 far pairs (insert 39 000, beyond the near-pair span) and of 100 single reads: the workgroup-per-run
+    search over two-word entries, with packed keys and -- every position moved beyond 2^32 -- with wide ones."""
+    rng = np.random.RandomState(11)
+    recs = _pair_families(synth, rng, 600, 3, 1000, 40000)
+    allr = np.concatenate([recs,
+                           _singles(synth, rng, 300, [1000, 1010, 1020], 0),        # on the forward ends of the pairs
+                           _singles(synth, rng, 300, [40000, 40010, 40020], 16),    # on their reverse ends
+                           _singles(synth, rng, 200, [70000, 70010], 0)])           # where no pair ends
+    allr["prime5"] += np.uint64(shift); allr["coord"] += np.uint64(shift)
+    want_order, want_dup, _ = sd_oracle.run(L, allr)
+    order, dup = sd_engine.sort_mark(L, allr)
+    assert np.array_equal(order, want_order)
+    assert np.array_equal(dup, want_dup)
+    assert dup.sum() == 2 * (600 - 3) + 600 + (200 - 2) == 1992
+    assert (sd_engine.stats()["key_bits_coord"] > 32) == bool(shift)
+
+
+def test_ends_near_the_reference_end_use_the_atomic_bitmap(sd_engine, sd_oracle, synth):
+    """A 5' end within 64 of L selects the reference's bitmap layout (global atomics) while the keys stay packed:
+    near pairs, far pairs and single reads of both strands on such ends."""
+    L = 50_000
+    rng = np.random.RandomState(12)
+    near = _pair_families(synth, rng, 400, 3, L - 4000, L - 40)
+    far = _pair_families(synth, rng, 400, 3, 1000, L - 40)
+    far["mate"] += np.uint32(len(near))
+    rev = _singles(synth, rng, 200, [L - 40, L - 30, L - 20], 16)
+    fwd = _singles(synth, rng, 200, [L - 4000, 1000, 2000], 0)
+    allr = np.concatenate([near, far, rev, fwd])
+    want_order, want_dup, _ = sd_oracle.run(L, allr)
+    order, dup = sd_engine.sort_mark(L, allr)
+    assert np.array_equal(order, want_order)
+    assert np.array_equal(dup, want_dup)
+    n_pair_recs = len(near) + len(far)
+    assert dup[:n_pair_recs].sum() == 1588
+    assert (dup[n_pair_recs:n_pair_recs + 200] == 1).all()           # every reverse single lies on a pair's reverse end
+    assert dup[n_pair_recs + 200:].sum() == 199                      # forward ones: all but the kept read at 2000
 
 
 def test_scaled_config_properties(sd_engine, sd_oracle, synth):
