@@ -27,6 +27,7 @@
 #include "mgx_common.h"
 #include "mgx_tables.h"
 #include "pairhmm_pack.h"
+#include "pairhmm_wire.h"
 #include "pairhmm_kernels.hip.inc"
 
 using mgx::set_error;
@@ -88,6 +89,7 @@ struct mgx_pairhmm {
     double* d_ph2pr_d = nullptr; double* d_mm_d = nullptr; double* d_div3_d = nullptr; double* d_ratio_d = nullptr;
     float log10_initial_f = 0; double log10_initial_d = 0;
     int n_cu = 256;
+    bool wire = false;           // MGX_PAIRHMM_WIRE, or its environment override: staged pair-list batches upload the wire form
     std::vector<Slab> free_slabs;
     void* d_strip = nullptr; size_t strip_cap = 0;      // boundary rows of the strip-mined class (one compute stream: launches do not overlap)
 };
@@ -97,9 +99,11 @@ struct mgx_pairhmm_batch {
     std::vector<Bin> bins;
     // everything lives in one slab: [jobs | bases | qual | ins | del | gcp | hap] is written once
     // (one H2D copy when staged through the pinned mirror), [out | used] is read back with one
-    // D2H copy, [rerun_list | rerun_count] is device scratch
+    // D2H copy, [rerun_list | rerun_count] is device scratch.  In the wire form the written prefix is
+    // [jobs | bases4 | qual | ins | del | gcp | hap4] and the six arrays are expanded into device scratch.
     Slab slab;
     size_t in_bytes = 0, o_out = 0, o_used = 0, result_bytes = 0;
+    uint64_t read_bytes = 0, hap_bytes = 0;      // lengths of the five read arrays and of the haplotype array
     uint8_t *d_bases = nullptr, *d_qual = nullptr, *d_ins = nullptr, *d_del = nullptr,
             *d_gcp = nullptr, *d_hap = nullptr, *d_used = nullptr;
     Job* d_jobs = nullptr;
@@ -236,7 +240,63 @@ void merge_small_bins(uint64_t (&count)[kBins], int (&remap)[kBins]) {
     for (int k = 0; k < kBins; ++k) { int t = k; while (remap[t] != t) t = remap[t]; remap[k] = t; }
 }
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+constexpr size_t kSlabAlign = 256;          // every array of a slab starts on a multiple of this and owns the bytes up to the next
+inline size_t align_up(size_t x, size_t a = kSlabAlign) { return (x + a - 1) / a * a; }
+
+// ---- the wire form's device side (pairhmm_wire.h): one launch on the copy stream, right behind the H2D copy, turns
+// [bases4 | qual | ins | del | gcp | hap4] back into the six byte arrays the PairHMM kernels read.  The grid is laid
+// over the concatenated work of the six arrays; which array a workgroup serves is uniform over it.  One thread
+// produces 8 output bytes with one 8-byte store: of a bit stream it reads the group's w bytes at byte offset w t, of
+// nibble codes 4 bytes, which two byte permutes map through "ACTGN".  No LDS, nothing shared between threads.
+constexpr uint32_t kExpandBlock = 256;
+// the last thread of an array stores its full 8 bytes, up to 7 past the array's length: they fall into the array's own
+// slab slot, which align_up rounds to a multiple of 8
+static_assert(kSlabAlign % 8 == 0, "pairhmm_expand_wire stores whole 8-byte groups into slab slots");
+struct ExpandWireArgs {
+    const uint8_t* src[6];       // bases4, qual, ins, del, gcp, hap4
+    uint8_t* dst[6];             // bases, qual, ins, del, gcp, hap
+    uint64_t n[6];               // positions = output bytes
+    uint32_t block_first[7];     // the first workgroup of every array; [6]: the grid
+    uint32_t w[6];               // 4: nibble codes; 6 / 7: bit stream; 0: every byte is `fill`
+    uint32_t fill;
+};
+__device__ __forceinline__ uint32_t nibbles_to_letters(uint32_t h) {      // four codes in 16 bits -> four ASCII bytes
+    h = (h | (h << 8)) & 0x00FF00FFu;
+    h = (h | (h << 4)) & 0x0F0F0F0Fu;
+    return __builtin_amdgcn_perm(0x0000004Eu, 0x47544341u, h & 0x07070707u);      // idx 0..7 -> A C T G N 0 0 0 (mgx::wire::kLetters)
+}
+__global__ __launch_bounds__(kExpandBlock) void pairhmm_expand_wire(const ExpandWireArgs a) {
+    const uint32_t blk = blockIdx.x;
+    const uint8_t* src = a.src[0];
+    uint8_t* dst = a.dst[0];
+    uint64_t n = a.n[0];
+    uint32_t first = 0, w = a.w[0];
+#pragma unroll
+    for (int k = 1; k < 6; ++k)
+        if (blk >= a.block_first[k]) { src = a.src[k]; dst = a.dst[k]; n = a.n[k]; first = a.block_first[k]; w = a.w[k]; }
+    const uint64_t t = (uint64_t)(blk - first) * kExpandBlock + threadIdx.x;      // this thread's group of eight positions
+    if (8 * t >= n) return;
+    uint64_t out;
+    if (w == 4) {
+        const uint64_t n_bytes = (n + 1) / 2;
+        const uint8_t* p = src + 4 * t;
+        uint32_t v = 0;
+        if (4 * t + 4 <= n_bytes) v = *reinterpret_cast<const uint32_t*>(p);
+        else for (uint64_t k = 0; 4 * t + k < n_bytes; ++k) v |= (uint32_t)p[k] << (8 * k);      // the array's last thread: nothing past ceil(n / 2) bytes
+        out = nibbles_to_letters(v & 0xFFFFu) | (uint64_t)nibbles_to_letters(v >> 16) << 32;
+    } else if (w == 0) {
+        out = (uint64_t)a.fill * 0x0101010101010101ull;
+    } else {
+        const uint8_t* p = src + (uint64_t)w * t;      // whole groups only: the packer zero-fills the last one
+        uint32_t lo;
+        uint16_t mid;
+        __builtin_memcpy(&lo, p, 4);
+        __builtin_memcpy(&mid, p + 4, 2);
+        const uint64_t v = lo | (uint64_t)mid << 32;
+        out = w == 7 ? mgx::wire::spread8<7>(v | (uint64_t)p[6] << 48) : mgx::wire::spread8<6>(v);
+    }
+    *reinterpret_cast<uint64_t*>(dst + 8 * t) = out;
+}
 
 int acquire_slab(mgx_pairhmm* c, size_t bytes, size_t pin_bytes, Slab* out) {
     int best = -1;
@@ -309,6 +369,8 @@ int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
     if (!c) return -ENOMEM;
     c->device = device;
     c->flags = flags;
+    c->wire = (flags & MGX_PAIRHMM_WIRE) != 0;
+    if (const char* e = getenv("MGX_PAIRHMM_WIRE")) { if (*e) c->wire = atoi(e) != 0; }      // A/B: read per context, not once per process
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     c->n_cu = prop.multiProcessorCount;
@@ -410,6 +472,11 @@ struct SlabLayout {
     size_t rlist = 0, nlist = 0, rcount = 0;
     size_t pin_bytes = 0;                                         // the pinned mirror covers the inputs and the results only
     bool staged = true;
+    // the wire form (pair-list batches of a context with MGX_PAIRHMM_WIRE): the uploaded prefix is [jobs | bases4 | qual |
+    // ins | del | gcp | hap4] at these offsets, and bases ... hap above lie in device scratch
+    bool wire = false;
+    mgx::wire::Widths ww;
+    size_t w_bases4 = 0, w_qual = 0, w_ins = 0, w_del = 0, w_gcp = 0, w_hap4 = 0;
 };
 
 // Decides the offsets, takes a slab of that size -- with a pinned mirror if always_stage or if inputs and results fit
@@ -427,12 +494,28 @@ int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_b
     } else {
         L->jobs = take(n * sizeof(Job));
     }
-    L->bases = take(L->read_bytes);
-    L->qual = take(L->read_bytes);
-    L->ins = take(L->read_bytes);
-    L->del = take(L->read_bytes);
-    L->gcp = take(L->read_bytes);
-    L->hap = take(L->hap_bytes);
+    auto take_expanded = [&] {
+        L->bases = take(L->read_bytes);
+        L->qual = take(L->read_bytes);
+        L->ins = take(L->read_bytes);
+        L->del = take(L->read_bytes);
+        L->gcp = take(L->read_bytes);
+        L->hap = take(L->hap_bytes);
+    };
+    // the wire form is for batches that go through the pinned mirror: those the plain form would stage
+    if (L->wire && (L->cross || (!always_stage && align_up(n * sizeof(Job)) + 5 * align_up(L->read_bytes) + align_up(L->hap_bytes) +
+                                                       align_up(n * sizeof(double)) + align_up(n) > kStageLimit))) L->wire = false;
+    if (L->wire) {
+        namespace W = mgx::wire;
+        L->w_bases4 = take(W::nibble_bytes(L->read_bytes));
+        L->w_qual = take(W::stream_bytes(L->read_bytes, L->ww.qual));
+        L->w_ins = take(W::stream_bytes(L->read_bytes, L->ww.ins));
+        L->w_del = take(W::stream_bytes(L->read_bytes, L->ww.del));
+        L->w_gcp = take(W::stream_bytes(L->read_bytes, L->ww.gcp));
+        L->w_hap4 = take(W::nibble_bytes(L->hap_bytes));
+    } else {
+        take_expanded();
+    }
     L->mapq = take(per_read);
     L->rlen = take(per_read * sizeof(uint64_t));
     L->roff = take(per_read * sizeof(uint32_t));
@@ -444,12 +527,14 @@ int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_b
     b->result_bytes = off - b->o_out;
     L->pin_bytes = off;
     if (L->cross) L->jobs = take(n * sizeof(Job));
+    if (L->wire) take_expanded();                    // what pairhmm_expand_wire writes
     L->rlist = take(2 * n * sizeof(uint32_t));       // fp64 re-run lists | exact-tier list
     L->nlist = take(n * sizeof(uint32_t));           // N-haplotype lists of the four-code fp32 launches
     L->rcount = take(kCounters * sizeof(uint32_t));
     L->staged = always_stage || L->pin_bytes <= kStageLimit;
     if (const int rc = acquire_slab(c, off, L->staged ? L->pin_bytes : 0, &b->slab)) return rc;
     uint8_t* dv = b->slab.dev;
+    b->read_bytes = L->read_bytes; b->hap_bytes = L->hap_bytes;
     b->d_jobs = (Job*)(dv + L->jobs);
     b->d_bases = dv + L->bases; b->d_qual = dv + L->qual; b->d_ins = dv + L->ins; b->d_del = dv + L->del;
     b->d_gcp = dv + L->gcp; b->d_hap = dv + L->hap;
@@ -664,13 +749,58 @@ int create_cross(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t
     return 0;
 }
 
+// The six arrays of a pair-list batch in the wire form, straight from the caller's arrays into the pinned mirror
+// (the gather and the bit-packing are one pass; the widths come from create_pairs' pre-pass).
+void stage_wire(const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, const SlabLayout& L, uint8_t* pin) {
+    namespace W = mgx::wire;
+    if (plan || L.read_bytes + L.hap_bytes < (32u << 20)) {
+        W::pack_arrays(in, plan, L.ww, pin + L.w_bases4, pin + L.w_qual, pin + L.w_ins, pin + L.w_del, pin + L.w_gcp, pin + L.w_hap4);
+        return;
+    }
+    // a large one-shot batch: one thread per array, as the plain form stages it
+    std::thread th[6];
+    th[0] = std::thread([=] { W::pack_nibbles(in, plan, true, pin + L.w_bases4); });
+    th[1] = std::thread([=] { W::pack_stream(in, plan, in->qual, L.ww.qual, pin + L.w_qual); });
+    th[2] = std::thread([=] { W::pack_stream(in, plan, in->ins, L.ww.ins, pin + L.w_ins); });
+    th[3] = std::thread([=] { W::pack_stream(in, plan, in->del, L.ww.del, pin + L.w_del); });
+    th[4] = std::thread([=] { if (L.ww.gcp) W::pack_stream(in, plan, in->gcp, L.ww.gcp, pin + L.w_gcp); });
+    th[5] = std::thread([=] { W::pack_nibbles(in, plan, false, pin + L.w_hap4); });
+    for (auto& t : th) t.join();
+}
+
+// pairhmm_expand_wire behind the copy, on the same stream: d_bases ... d_hap are whole before `uploaded` is recorded
+int launch_expand_wire(hipStream_t s, const SlabLayout& L, mgx_pairhmm_batch* b) {
+    ExpandWireArgs a{};
+    const size_t src[6] = {L.w_bases4, L.w_qual, L.w_ins, L.w_del, L.w_gcp, L.w_hap4};
+    uint8_t* const dst[6] = {b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, b->d_hap};
+    const uint32_t w[6] = {4, L.ww.qual, L.ww.ins, L.ww.del, L.ww.gcp, 4};
+    uint64_t blocks = 0;
+    for (int k = 0; k < 6; ++k) {
+        a.src[k] = b->slab.dev + src[k]; a.dst[k] = dst[k]; a.w[k] = w[k];
+        a.n[k] = k == 5 ? L.hap_bytes : L.read_bytes;
+        a.block_first[k] = (uint32_t)blocks;
+        blocks += ((a.n[k] + 7) / 8 + kExpandBlock - 1) / kExpandBlock;
+        if (blocks > 0x7FFFFFFFull) { set_error("batch too large for one expansion launch"); return -E2BIG; }
+    }
+    a.block_first[6] = (uint32_t)blocks;
+    a.fill = L.ww.gcp_const;
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(pairhmm_expand_wire, dim3((uint32_t)blocks), dim3(kExpandBlock), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Upload of a pair-list batch: one copy out of the pinned mirror, or (very large batches) one per array.
 int upload_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, const SlabLayout& L, const Job* jobs,
                  mgx_pairhmm_batch* b) {
     const uint64_t read_bytes = L.read_bytes, hap_bytes = L.hap_bytes;
     uint8_t* dv = b->slab.dev;
     hipStream_t s = c->copy;
-    if (L.staged) {
+    if (L.wire) {
+        stage_wire(in, plan, L, b->slab.pin);
+        HIP_TRY(hipMemcpyAsync(dv, b->slab.pin, b->in_bytes, hipMemcpyHostToDevice, s));
+        if (const int rc = launch_expand_wire(s, L, b)) return rc;
+    } else if (L.staged) {
         uint8_t* pin = b->slab.pin;
         if (plan) {
             mgx::pack_copy(in, *plan, pin + L.bases, pin + L.qual, pin + L.ins, pin + L.del, pin + L.gcp, pin + L.hap);
@@ -751,6 +881,7 @@ int create_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::Pac
     //      built directly in the pinned mirror
     SlabLayout L;
     L.n = n; L.n_reads = n_reads; L.n_haps = n_haps; L.read_bytes = roff[n_reads]; L.hap_bytes = hoff[n_haps];
+    if (c->wire) { L.wire = true; L.ww = mgx::wire::scan_widths(in, plan); }      // the widths decide the layout
     if ((rc = lay_out_slab(c, plan != nullptr, &L, b))) return rc;
     if (!L.staged) b->host_jobs.resize(n);
     Job* jobs = L.staged ? (Job*)(b->slab.pin + L.jobs) : b->host_jobs.data();
@@ -1111,6 +1242,22 @@ int mgx_pairhmm_batch_run(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
     if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(b->done, r.s));
     b->ran = true;
+    return 0;
+}
+
+int mgx_pairhmm_batch_read_inputs(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, uint8_t* bases, uint8_t* qual, uint8_t* ins,
+                                  uint8_t* del, uint8_t* gcp, uint8_t* hap) {
+    if (!c || !b) { set_error("ctx/batch is NULL"); return -EINVAL; }
+    if ((b->read_bytes && (!bases || !qual || !ins || !del || !gcp)) || (b->hap_bytes && !hap)) { set_error("NULL argument"); return -EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    if (b->n_pairs == 0) return 0;
+    if (b->uploaded) HIP_TRY(hipEventSynchronize(b->uploaded));      // the copy and, in the wire form, the expansion behind it
+    uint8_t* const host[6] = {bases, qual, ins, del, gcp, hap};
+    const uint8_t* const dev[6] = {b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, b->d_hap};
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t len = k == 5 ? b->hap_bytes : b->read_bytes;
+        if (len) HIP_TRY(hipMemcpy(host[k], dev[k], len, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -1,9 +1,11 @@
-// pairhmm_pack_batch.cpp -- mgx_pairhmm_pack_batch (include/mgx_pairhmm.h): the work queue's packer as a host-only
-// entry point.  No HIP in this translation unit: it is also what tests/test_host_sanitizers.py builds with
+// pairhmm_pack_batch.cpp -- mgx_pairhmm_pack_batch, mgx_pairhmm_pack_batch_wire and mgx_pairhmm_wire_expand_host
+// (include/mgx_pairhmm.h): the work queue's packer, plain and in the wire form, as host-only entry points.
+// No HIP in this translation unit: it is also what tests/test_host_sanitizers.py builds with
 // -fsanitize=address,undefined / thread.
 #include <cstring>
 
 #include "pairhmm_pack.h"
+#include "pairhmm_wire.h"
 
 using mgx::set_error;
 
@@ -47,6 +49,40 @@ int mgx_pairhmm_pack_batch(const mgx_pairhmm_input_t* in, uint64_t pair_begin, u
     o.n_haps = nh; o.hap_off = (const uint64_t*)(p + o_hoff); o.hap_bases = p + o_h;
     o.n_pairs = n; o.pair_read = (const uint32_t*)(p + o_pr); o.pair_hap = (const uint32_t*)(p + o_ph);
     *out = o;
+    return 0;
+}
+
+// Host-only: the same batch in the wire form (pairhmm_wire.h).
+int mgx_pairhmm_pack_batch_wire(const mgx_pairhmm_input_t* in, uint64_t pair_begin, uint64_t pair_end, void* buf, size_t buf_bytes,
+                                mgx_pairhmm_wire_t* out, size_t* need) {
+    int rc = validate(in);
+    if (rc) return rc;
+    if (!out || !need) { set_error("NULL argument"); return -EINVAL; }
+    *need = 0;
+    if (pair_begin > pair_end || pair_end > mgx::pack_n_pairs(in)) { set_error("test-case range outside the stream"); return -EINVAL; }
+    mgx::PackPlan plan;
+    const uint64_t bad = mgx::pack_plan(in, pair_begin, pair_end, &plan);
+    if (bad) { set_error("test case %llu: index out of range", (unsigned long long)(pair_begin + bad - 1)); return -EINVAL; }
+    const mgx::wire::Widths w = mgx::wire::scan_widths(in, &plan);
+    const mgx::wire::BufferLayout L = mgx::wire::buffer_layout(plan.lread.size(), plan.lhap.size(), pair_end - pair_begin,
+                                                               plan.roff.back(), plan.hoff.back(), w);
+    *need = L.need;
+    if (!buf || buf_bytes < L.need) { set_error("buffer of %zu bytes needed", L.need); return -ENOSPC; }
+    if ((uintptr_t)buf & 7u) { set_error("buffer is not 8-byte aligned"); return -EINVAL; }
+    mgx::wire::pack_batch(in, plan, w, L, (uint8_t*)buf, out);
+    return 0;
+}
+
+int mgx_pairhmm_wire_expand_host(const mgx_pairhmm_wire_t* wire, uint8_t* bases, uint8_t* qual, uint8_t* ins, uint8_t* del,
+                                 uint8_t* gcp, uint8_t* hap) {
+    if (!wire || !wire->read_off || !wire->hap_off) { set_error("NULL argument"); return -EINVAL; }
+    const uint64_t rb = wire->read_off[wire->n_reads], hb = wire->hap_off[wire->n_haps];
+    if ((rb && (!bases || !qual || !ins || !del || !gcp || !wire->bases4 || !wire->qual || !wire->ins || !wire->del || (wire->w_gcp && !wire->gcp))) ||
+        (hb && (!hap || !wire->hap4))) { set_error("NULL argument"); return -EINVAL; }
+    const uint8_t ws[3] = {wire->w_qual, wire->w_ins, wire->w_del};
+    for (uint8_t w : ws) if (w != 6 && w != 7) { set_error("field width %u is neither 6 nor 7", w); return -EINVAL; }
+    if (wire->w_gcp != 0 && wire->w_gcp != 6 && wire->w_gcp != 7) { set_error("gcp width %u is none of 0, 6, 7", wire->w_gcp); return -EINVAL; }
+    mgx::wire::expand(wire, bases, qual, ins, del, gcp, hap);
     return 0;
 }
 

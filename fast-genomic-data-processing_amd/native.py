@@ -23,6 +23,17 @@ class PairHMMInput(C.Structure):
     ]
 
 
+class PairHMMWire(C.Structure):
+    _fields_ = [
+        ("n_reads", C.c_uint64), ("n_haps", C.c_uint64), ("n_pairs", C.c_uint64),
+        ("read_off", C.c_void_p), ("hap_off", C.c_void_p), ("pair_read", C.c_void_p), ("pair_hap", C.c_void_p),
+        ("w_qual", C.c_uint8), ("w_ins", C.c_uint8), ("w_del", C.c_uint8), ("w_gcp", C.c_uint8), ("gcp_const", C.c_uint8),
+        ("pad_", C.c_uint8 * 3),
+        ("bases4", C.c_void_p), ("qual", C.c_void_p), ("ins", C.c_void_p), ("del_", C.c_void_p), ("gcp", C.c_void_p),
+        ("hap4", C.c_void_p),
+    ]
+
+
 class PairHMMStats(C.Structure):
     _fields_ = [
         ("n_pairs", C.c_uint64), ("cells", C.c_uint64), ("alg_bytes", C.c_uint64),
@@ -75,6 +86,10 @@ PAIRHMM_SYMBOLS = {
     "mgx_pairhmm_queue_stats": (C.c_int, [C.c_void_p, C.POINTER(QueueStats)]),
     "mgx_pairhmm_pack_batch": (C.c_int, [C.POINTER(PairHMMInput), C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t,
                                          C.POINTER(PairHMMInput), C.POINTER(C.c_size_t)]),
+    "mgx_pairhmm_pack_batch_wire": (C.c_int, [C.POINTER(PairHMMInput), C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t,
+                                              C.POINTER(PairHMMWire), C.POINTER(C.c_size_t)]),
+    "mgx_pairhmm_wire_expand_host": (C.c_int, [C.POINTER(PairHMMWire)] + [C.c_void_p] * 6),
+    "mgx_pairhmm_batch_read_inputs": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "mgx_pairhmm_table_f32": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "mgx_pairhmm_table_f64": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
 }

@@ -12,6 +12,7 @@ from . import native
 
 FORCE_DOUBLE = 1
 TIMING = 2
+WIRE = 8             # staged pair-list batches cross PCIe bit-packed and are expanded on the device (include/mgx_pairhmm.h)
 PACKED_FP32 = 4      # accepted and ignored: the packed fp32 kernel it selected was removed (include/mgx_pairhmm.h)
 
 
@@ -88,6 +89,81 @@ def pack_batch(d, lo, hi):
                 pair_read=view(out.pair_read, n, np.uint32), pair_hap=view(out.pair_hap, n, np.uint32))
 
 
+_WIRE_ARRAYS = ("bases4", "qual", "ins", "dele", "gcp", "hap4")
+
+
+def wire_lengths(w):
+    """Bytes of the six packed arrays of a wire batch, in the order of _WIRE_ARRAYS."""
+    rb, hb = int(w["read_off"][-1]), int(w["hap_off"][-1])
+    groups = (rb + 7) // 8
+    return [(rb + 1) // 2, groups * w["w_qual"], groups * w["w_ins"], groups * w["w_del"], groups * w["w_gcp"], (hb + 1) // 2]
+
+
+def wire_need(w):
+    """The documented size of mgx_pairhmm_pack_batch_wire's buffer (nothing is padded)."""
+    return 8 * (w["n_reads"] + 1) + 8 * (w["n_haps"] + 1) + 8 * w["n_pairs"] + sum(wire_lengths(w))
+
+
+def wire_upload_bytes(w):
+    """What a batch in the wire form uploads: [jobs | bases4 | qual | ins | del | gcp | hap4], every part rounded up to 256."""
+    return sum((x + 255) // 256 * 256 for x in [32 * w["n_pairs"]] + wire_lengths(w))
+
+
+def plain_upload_bytes(d):
+    """... and the plain form of the same packed batch: [jobs | bases | qual | ins | del | gcp | hap]."""
+    rb, hb = int(d["read_off"][-1]), int(d["hap_off"][-1])
+    return sum((x + 255) // 256 * 256 for x in [32 * d["n_pairs"]] + [rb] * 5 + [hb])
+
+
+def pack_batch_wire(d, lo, hi):
+    """pack_batch with the six byte arrays in the bit-packed wire form (host only): the offsets and pair arrays of
+    pack_batch, the widths w_qual / w_ins / w_del / w_gcp, gcp_const, the packed arrays, and `need`."""
+    lib = native.load()
+    inp, keep = make_input(d)
+    out = native.PairHMMWire()
+    need = C.c_size_t()
+    rc = lib.mgx_pairhmm_pack_batch_wire(C.byref(inp), lo, hi, None, 0, C.byref(out), C.byref(need))
+    if rc != -28:          # -ENOSPC is the sizing answer
+        native.check(rc)
+    buf = np.zeros(max(int(need.value), 8) // 8 + 1, dtype=np.uint64).view(np.uint8)[:max(int(need.value), 1)]      # 8-byte aligned
+    native.check(lib.mgx_pairhmm_pack_batch_wire(C.byref(inp), lo, hi, _ptr(buf), int(need.value), C.byref(out), C.byref(need)))
+    base = buf.ctypes.data
+
+    def view(ptr, count, dt):
+        o = int(ptr or base) - base
+        return buf[o:o + count * np.dtype(dt).itemsize].view(dt).copy()
+    nr, nh, n = int(out.n_reads), int(out.n_haps), int(out.n_pairs)
+    w = dict(n_reads=nr, n_haps=nh, n_pairs=n, read_off=view(out.read_off, nr + 1, np.uint64), hap_off=view(out.hap_off, nh + 1, np.uint64),
+             pair_read=view(out.pair_read, n, np.uint32), pair_hap=view(out.pair_hap, n, np.uint32),
+             w_qual=int(out.w_qual), w_ins=int(out.w_ins), w_del=int(out.w_del), w_gcp=int(out.w_gcp), gcp_const=int(out.gcp_const),
+             need=int(need.value))
+    ptrs = (out.bases4, out.qual, out.ins, out.del_, out.gcp, out.hap4)
+    for k, ptr, ln in zip(_WIRE_ARRAYS, ptrs, wire_lengths(w)):
+        w[k] = view(ptr, ln, np.uint8)
+    return w
+
+
+def wire_expand(w):
+    """The reference expander (host): a wire batch back to pack_batch's dict, with canonical arrays -- qualities
+    masked with 127, bases folded to A C T G N."""
+    lib = native.load()
+    keep = {k: _as(w[k], np.uint8) for k in _WIRE_ARRAYS}
+    keep.update(read_off=_as(w["read_off"], np.uint64), hap_off=_as(w["hap_off"], np.uint64),
+                pair_read=_as(w["pair_read"], np.uint32), pair_hap=_as(w["pair_hap"], np.uint32))
+    wire = native.PairHMMWire(
+        n_reads=w["n_reads"], n_haps=w["n_haps"], n_pairs=w["n_pairs"], read_off=_ptr(keep["read_off"]), hap_off=_ptr(keep["hap_off"]),
+        pair_read=_ptr(keep["pair_read"]), pair_hap=_ptr(keep["pair_hap"]), w_qual=w["w_qual"], w_ins=w["w_ins"], w_del=w["w_del"],
+        w_gcp=w["w_gcp"], gcp_const=w["gcp_const"], bases4=_ptr(keep["bases4"]), qual=_ptr(keep["qual"]), ins=_ptr(keep["ins"]),
+        del_=_ptr(keep["dele"]), gcp=_ptr(keep["gcp"]), hap4=_ptr(keep["hap4"]))
+    rb, hb = int(keep["read_off"][-1]), int(keep["hap_off"][-1])
+    out = {k: np.zeros(rb, dtype=np.uint8) for k in ("bases", "qual", "ins", "dele", "gcp")}
+    out["hap_bases"] = np.zeros(hb, dtype=np.uint8)
+    native.check(lib.mgx_pairhmm_wire_expand_host(C.byref(wire), *[_ptr(out[k]) for k in ("bases", "qual", "ins", "dele", "gcp", "hap_bases")]))
+    out.update(n_reads=w["n_reads"], n_haps=w["n_haps"], n_pairs=w["n_pairs"], read_off=keep["read_off"].copy(), hap_off=keep["hap_off"].copy(),
+               pair_read=keep["pair_read"].copy(), pair_hap=keep["pair_hap"].copy())
+    return out
+
+
 class PairHMMQueue:
     """Host work queue over one or more devices (include/mgx_pairhmm.h, mgx_pairhmm_queue_*):
     BASELINE.json configs[2], the reference's worker threads pulling regions off an atomic index."""
@@ -142,6 +218,7 @@ class PairHMMBatch:
         self.engine = engine
         inp, keep = make_input(d)
         self.n_pairs = int(inp.n_pairs)
+        self.read_bytes, self.hap_bytes = int(keep["read_off"][-1]), int(keep["hap_off"][-1])
         h = C.c_void_p()
         native.check(engine.lib.mgx_pairhmm_batch_create(engine.ctx, C.byref(inp), C.byref(h)))
         self.h = h
@@ -154,6 +231,14 @@ class PairHMMBatch:
         used = np.zeros(self.n_pairs, dtype=np.uint8)
         native.check(self.engine.lib.mgx_pairhmm_batch_results(self.engine.ctx, self.h, _ptr(out), _ptr(used)))
         return (out, used) if with_flags else out
+
+    def read_inputs(self):
+        """The batch's six device-resident input arrays, copied back (for tests): dict of bases, qual, ins, dele, gcp,
+        hap_bases.  On a WIRE context these are what the device expanded."""
+        keys = ("bases", "qual", "ins", "dele", "gcp", "hap_bases")
+        out = {k: np.zeros(self.hap_bytes if k == "hap_bases" else self.read_bytes, dtype=np.uint8) for k in keys}
+        native.check(self.engine.lib.mgx_pairhmm_batch_read_inputs(self.engine.ctx, self.h, *[_ptr(out[k]) for k in keys]))
+        return out
 
     def stats(self):
         st = native.PairHMMStats()

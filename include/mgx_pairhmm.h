@@ -55,6 +55,12 @@ typedef struct mgx_pairhmm_batch mgx_pairhmm_batch_t;
                                      * runs the default kernels.  One visible difference: a test case whose gap-continuation
                                      * byte is 0 used to go to the fp64 list under this flag; it now takes the default fp32
                                      * kernel's plain form and returns the default path's result. */
+#define MGX_PAIRHMM_WIRE         8u /* pair-list batches staged through the pinned mirror -- every batch a queue packs, and
+                                     * mgx_pairhmm_batch_create / mgx_pairhmm_compute in pair-list form -- cross PCIe in the
+                                     * bit-packed wire form (mgx_pairhmm_wire_t below) and are expanded on the device behind
+                                     * the copy.  Results and used_f64 flags keep their bits.  Cross-product, region and
+                                     * unstaged batches are uploaded as without the flag.  Default off; the environment
+                                     * variable MGX_PAIRHMM_WIRE=1 / 0, read when a context is created, overrides the flag. */
 /* bits 8..15 (both mgx_pairhmm_create and mgx_sortdedup_create): optional CU partition, an 8-bit
  * pattern repeated over the CU index; 0 or 0xFF = all CUs.  MGX_CU_PATTERN(0x3F) keeps 6 CUs of 8. */
 #define MGX_CU_PATTERN(p) (((unsigned)(p) & 0xFFu) << 8)
@@ -220,6 +226,42 @@ int mgx_pairhmm_queue_stats(mgx_pairhmm_queue_t* q, mgx_pairhmm_queue_stats_t* o
  * first-use order.  *need receives the bytes required; -ENOSPC if buf_bytes is smaller (buf may be NULL). */
 int mgx_pairhmm_pack_batch(const mgx_pairhmm_input_t* in, uint64_t pair_begin, uint64_t pair_end, void* buf, size_t buf_bytes,
                            mgx_pairhmm_input_t* out, size_t* need);
+
+/* ---- The wire form: a packed batch with its six byte arrays bit-packed (csrc/pairhmm_wire.h has the layout and the
+ * argument why no result changes).  bases4 / hap4: 4-bit codes A 0, C 1, T 2, G 3, N 4, any other byte 0; two positions
+ * per byte, the even one in the low nibble.  qual / ins / del / gcp: the values byte & 127 as a little-endian stream of
+ * w-bit fields over the concatenated reads (position p in bits [p w, p w + w), bit b = bit b % 8 of byte b / 8), w = 6
+ * when every masked value of that array in the batch is at most 63, else 7; w_gcp = 0 when every masked gcp byte of the
+ * batch is the one value gcp_const, and gcp then holds nothing.  Offsets and pair arrays are those of
+ * mgx_pairhmm_pack_batch.  With rb = read_off[n_reads] and hb = hap_off[n_haps] the packed arrays hold
+ * ceil(rb / 2), ceil(rb / 8) * w (four times) and ceil(hb / 2) bytes; the last partial group is zero-filled. */
+typedef struct mgx_pairhmm_wire {
+    uint64_t n_reads, n_haps, n_pairs;
+    const uint64_t* read_off;  /* [n_reads + 1] */
+    const uint64_t* hap_off;   /* [n_haps + 1] */
+    const uint32_t* pair_read; /* [n_pairs] */
+    const uint32_t* pair_hap;  /* [n_pairs] */
+    uint8_t w_qual, w_ins, w_del, w_gcp, gcp_const, pad_[3];
+    const uint8_t* bases4;
+    const uint8_t* qual;
+    const uint8_t* ins;
+    const uint8_t* del;
+    const uint8_t* gcp;
+    const uint8_t* hap4;
+} mgx_pairhmm_wire_t;
+/* Host only: mgx_pairhmm_pack_batch with the wire form as its result.  *need is always written and is
+ *   8 (n_reads + 1) + 8 (n_haps + 1) + 8 n_pairs + ceil(rb / 2) + ceil(rb / 8) (w_qual + w_ins + w_del + w_gcp) + ceil(hb / 2)
+ * (nothing is padded); -ENOSPC if buf_bytes is smaller (buf may then be NULL).  buf must be 8-byte aligned. */
+int mgx_pairhmm_pack_batch_wire(const mgx_pairhmm_input_t* in, uint64_t pair_begin, uint64_t pair_end, void* buf, size_t buf_bytes,
+                                mgx_pairhmm_wire_t* out, size_t* need);
+/* Host only: the reference expander (the device kernel is tested against it).  Writes rb bytes to each of bases, qual,
+ * ins, del, gcp and hb bytes to hap: canonical arrays -- qualities masked with 127, bases one of A C T G N. */
+int mgx_pairhmm_wire_expand_host(const mgx_pairhmm_wire_t* wire, uint8_t* bases, uint8_t* qual, uint8_t* ins, uint8_t* del,
+                                 uint8_t* gcp, uint8_t* hap);
+/* For tests: waits for the batch's upload and copies its six device-resident input arrays back (as many bytes as the
+ * batch was created with: read_off[n_reads] each, hap_off[n_haps] for hap). */
+int mgx_pairhmm_batch_read_inputs(mgx_pairhmm_t* ctx, mgx_pairhmm_batch_t* batch, uint8_t* bases, uint8_t* qual, uint8_t* ins,
+                                  uint8_t* del, uint8_t* gcp, uint8_t* hap);
 
 /* The two probability tables as built by the product (for table-parity tests):
  * which = 0: ph2pr[128]; which = 1: matchToMatchProb[32640].  Returns the element count. */
