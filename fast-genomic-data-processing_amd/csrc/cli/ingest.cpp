@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "mgx_bam.h"
 #include "mgx_pairhmm.h"       // mgx_last_error
 
 using slicecut::Slice;
@@ -119,6 +120,67 @@ static void parse_slice(const char* data, size_t size, const samtext::Header& h,
     std::vector<uint64_t>().swap(c->cigar_off); std::vector<uint64_t>().swap(c->qname_off);
 }
 
+// ---- one slice of BAM records (-b): keys -> the same Chunk -------------------------------------------------------------------
+// The records are whole and valid (the index walked them); their keys come from the device, or, for an owned slice, from
+// the host functions here.  The record bytes go on unchanged, without their block_size field.
+// A record that the host key functions refuse (its CIGAR is in a CG tag): the library names its offset in `data`; name it in
+// the uncompressed stream, where data[0] is at `base`.  The refused record is the first whose key is still marked redo.
+static std::string refused_record(const uint64_t* off, const std::vector<mgx_bam_key_t>& keys, uint64_t base) {
+    const std::string why = mgx_last_error();
+    const size_t colon = why.find(": ");
+    uint64_t i = 0;
+    while (i < keys.size() && !keys[i].redo) ++i;
+    if (i == keys.size() || colon == std::string::npos) return why;
+    return "BAM record at offset " + std::to_string(base + off[i]) + " of the uncompressed stream: " + why.substr(colon + 2);
+}
+
+static void parse_bam_slice(const Slice& sl, const samtext::Header& h, Chunk* c) {
+    const uint8_t* data = sl.bam_data;
+    const uint64_t* off = sl.rec_off;
+    uint64_t n = sl.n_rec;
+    std::vector<uint64_t> own_off;
+    std::vector<mgx_bam_key_t> keys;
+    if (!data) {                                             // owned bytes: what straddled two batches
+        data = (const uint8_t*)sl.text.data();
+        uint64_t next = 0;
+        int rc = mgx_bam_walk_host(data, sl.text.size(), 0, 0, nullptr, &n, &next);
+        if (!rc) { own_off.resize(n); rc = mgx_bam_walk_host(data, sl.text.size(), 0, n, own_off.data(), &n, &next); }
+        if (rc == -EBADMSG) {                                 // the message names the offset inside the slice: name it in the stream
+            const std::string why = mgx_last_error();
+            const size_t colon = why.find(": ");
+            c->err = "corrupt BAM record at offset " + std::to_string(sl.bam_at + next) + " of the uncompressed stream: " + (colon == std::string::npos ? why : why.substr(colon + 2));
+            return;
+        }
+        if (rc || next != sl.text.size()) { c->err = rc ? mgx_last_error() : "a slice of records does not end with a record"; return; }
+        off = own_off.data();
+        keys.resize(n);
+        if (mgx_bam_keys_host(data, off, n, keys.data())) { c->err = refused_record(off, keys, sl.bam_at); return; }
+    } else {
+        const mgx_bam_key_t* k = static_cast<const mgx_bam_key_t*>(sl.keys);
+        keys.assign(k, k + n);
+        // what the device rules declined (tokens that need strtol, the long-CIGAR placeholder) is derived here
+        if (mgx_bam_keys_redo(data, off, n, keys.data())) { c->err = refused_record(off, keys, sl.bam_at - off[0]); return; }       // bam_at: where the slice's first record is
+    }
+    c->flag.resize(n); c->tid.resize(n); c->pos.resize(n); c->end.resize(n); c->blob_off.resize(n + 1);
+    uint64_t bytes = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        int32_t bs;
+        memcpy(&bs, data + off[i], 4);
+        c->blob_off[i] = bytes; bytes += (uint32_t)bs;
+    }
+    c->blob_off[n] = bytes;
+    c->blob.resize(bytes);
+    for (uint64_t i = 0; i < n; ++i) {
+        const mgx_bam_key_t& k = keys[i];
+        c->flag[i] = k.flag; c->tid[i] = k.tid; c->pos[i] = k.pos; c->end[i] = k.end;
+        memcpy(c->blob.data() + c->blob_off[i], data + off[i] + 4, c->blob_off[i + 1] - c->blob_off[i]);
+    }
+    c->recs.resize(n); c->input_index.resize(n);
+    uint64_t L = 0;
+    if (mgx_bam_pack_keys(n, keys.data(), (uint32_t)h.ref_len.size(), h.ref_len.data(), c->recs.data(), c->input_index.data(), &L))
+        c->err = std::string("pack: ") + mgx_last_error() + " (records of the slice at offset " + std::to_string(sl.bam_at) + " of the uncompressed stream)";
+}
+
 // ---- Ingest ------------------------------------------------------------------------------------------------------------
 Ingest::Ingest(const samtext::Header& hdr, GpuBringUp& gpu, int threads, const char* in_base, int in_fd, slicecut::PieceSource* src)
     : hdr_(hdr), gpu_(gpu), in_base_(in_base), in_fd_(in_fd), src_(src), queue_cap_((size_t)threads * 2) {
@@ -215,6 +277,11 @@ bool Ingest::finish_chunk(std::unique_ptr<Chunk> ch, uint64_t seq) {
 // Parses one slice where its text is: in the mapping of the input file, in this thread's buffer after a pread, in a piece's
 // buffer, or in the slice itself.  False after fail().
 bool Ingest::parse(const Slice& sl, std::vector<char>* text_buf, Chunk* ch) {
+    if (sl.bam) {
+        parse_bam_slice(sl, hdr_, ch);
+        if (!ch->err.empty()) { fail("BAM input: " + ch->err); return false; }
+        return true;
+    }
     if (sl.from_file && in_base_) {
 #ifdef MADV_POPULATE_READ
         const uintptr_t a0 = (uintptr_t)(in_base_ + sl.file_off) & ~(uintptr_t)4095, a1 = ((uintptr_t)(in_base_ + sl.file_off + sl.file_len) + 4095) & ~(uintptr_t)4095;

@@ -18,6 +18,11 @@ namespace slicecut {
 struct Slice {                       // owned text, a range of the input file, or text inside a piece's buffer
     uint64_t seq = 0; std::string text; uint64_t file_off = 0; size_t file_len = 0; bool from_file = false;
     const char* ext = nullptr; size_t ext_len = 0; std::shared_ptr<void> hold;      // a piece's text: parsed in place
+    // BAM input (gz_source.h): whole alignment records instead of lines.  Owned bytes in `text` (keyed by the parser), or
+    // n_rec records inside a batch's buffer, record i at bam_data + rec_off[i] with the device-made key keys[i]
+    // (mgx_bam_key_t); bam_at: where the slice's bytes start in the uncompressed stream (for messages).
+    bool bam = false; const uint8_t* bam_data = nullptr; const uint64_t* rec_off = nullptr; const void* keys = nullptr; size_t n_rec = 0;
+    uint64_t bam_at = 0;
 };
 
 // A piece of text; `hold` keeps its buffer alive (the slices cut from it are parsed in place, and the buffer goes back to

@@ -1,12 +1,17 @@
 // sortmardup_main.cpp -- `sortmardup`: coordinate sort + mark duplicates, SAM text in, BAM + BAI out.
 //
 // Same command line and outputs as the reference tool (sortmardup/main.cpp:47-78):
-//     sortmardup [-I input.sam] [-t threads] -O output.bam
+//     sortmardup [-I input.sam] [-t threads] [-b] -O output.bam
 // text SAM from a file or stdin; output.bam is replaced if it exists; output.bam.bai is written
 // next to it; stage timings go to stdout (time_stamp(), main.cpp:597-607).
 // Input formats: plain SAM text; BGZF-compressed SAM (inflated on the device in batches, the text parsed in place from
 // the pinned buffers: gz_source.cpp); plain gzip, one member or several (zlib on the reader thread: serial).
-// The gzip magic in the first two bytes decides; BAM input is refused.
+// The gzip magic in the first two bytes decides; BAM input is refused unless -b says that the input is BAM.
+// -b (extension): the input is BGZF BAM, from a file or stdin.  The same inflate batches; the header is parsed on the host,
+// and where the records start and their sort / duplicate keys are found on the device behind each batch's inflate
+// (mgx_bam.h); the parsers only re-derive what the device rules declined, pair the records
+// (mgx_bam_pack_keys) and hand the record bytes on unchanged.  Anything else given with -b is refused.  MGX_CLI_BAM=host
+// walks and keys the records on the host instead (A/B, debugging).
 //
 // Ingest is a pipeline over bounded slices of the text, the shape of the reference's reader thread feeding its
 // shuffle threads through a bounded queue of line blocks (main.cpp:505-562, 129-192):
@@ -71,13 +76,14 @@ struct Options {
     int device = 0, level = 6;
     OutMode out_mode = kOutDevice;
     size_t slice_bytes = 8u << 20;     // 8 MB: 20 M records parse in 1.2 s (32 MB slices: 2.1 s -- fewer, longer tasks per thread)
+    bool bam = false;                  // -b: the input is BGZF BAM
 };
 
 // False (after the usage line) when the command line is not one the tool takes.
 bool parse_options(int argc, char** argv, Options* o) {
-    auto usage = [&]() { fprintf(stderr, "usage: %s [-I input.sam] [-t num] -O output.bam\n", argv[0]); return false; };
+    auto usage = [&]() { fprintf(stderr, "usage: %s [-I input.sam] [-t num] [-b] -O output.bam\n", argv[0]); return false; };
     int c;
-    while ((c = getopt(argc, argv, "I:O:t:d:l:s:z:")) >= 0) {
+    while ((c = getopt(argc, argv, "I:O:t:d:l:s:z:b")) >= 0) {
         switch (c) {
             case 'I': o->in_path = optarg; break;
             case 'O': o->out_path = optarg; break;
@@ -91,6 +97,7 @@ bool parse_options(int argc, char** argv, Options* o) {
                 o->out_mode = !strcmp(optarg, "zlib") ? kOutZlib : !strcmp(optarg, "pinned") ? kOutPinned : kOutDevice;
                 break;
             case 's': o->slice_bytes = (size_t)atoll(optarg); break;   // extension: bytes of SAM text per slice
+            case 'b': o->bam = true; break;                  // extension: the input is BGZF BAM
             default: return usage();
         }
     }
@@ -260,7 +267,13 @@ int main(int argc, char** argv) {
     std::unique_ptr<slicecut::PieceSource> src;              // everything else
     GzSource* gzs = nullptr;
     slicecut::PieceHead head; std::string carry;             // text of the pieces read so far that is not in a slice yet
-    if (in.fd >= 0) {
+    if (opt.bam) {
+        if (!in.gz) { fprintf(stderr, "%s is not BAM: -b reads BGZF-compressed BAM, and this is not compressed\n", in.name()); return 1; }
+        const char* e = getenv("MGX_CLI_INFLATE"); const char* eb = getenv("MGX_CLI_BAM");
+        src.reset(gzs = new GzSource(in.f, in.first_bytes, in.name(), opt.device, opt.threads, e && !strcmp(e, "host"),
+                                     eb && !strcmp(eb, "host") ? GzSource::kBamHost : GzSource::kBamDevice));
+        if (!gzs->read_bam_header(&hdr)) { fprintf(stderr, "%s\n", gzs->err().c_str()); return 1; }
+    } else if (in.fd >= 0) {
         if (!in.read_file_header(&hdr, &body_pos)) { fprintf(stderr, "cannot read %s\n", in.path); return 1; }
     } else {
         const char* e = getenv("MGX_CLI_INFLATE");
@@ -273,14 +286,17 @@ int main(int argc, char** argv) {
     uint64_t L = 0;
     for (uint64_t x : hdr.ref_len) L += x;
     // bytes of SAM text, for the sizes of the device buffers: of compressed input, the file's size times the ratio of what is inflated so far
-    const uint64_t text_bytes = gzs ? (uint64_t)((double)in.file_bytes * gzs->ratio()) : in.file_bytes;
+    // (the sizes are stated in SAM text, of which BAM bytes are about 0.6)
+    const uint64_t text_bytes = gzs ? (uint64_t)((double)in.file_bytes * gzs->ratio() * (opt.bam ? 5.0 / 3.0 : 1.0)) : in.file_bytes;
 
     GpuBringUp gpu(opt.device, opt.out_mode, text_bytes, gzs ? gzs->hbm_bytes_to_come() : 0, L);
 
     // ---- ingest: the reader (this thread) cuts slices, the parsers take them from the queue
     Ingest ingest(hdr, gpu, opt.threads, in.base, in.fd, src.get());
     const slicecut::Push push = [&](slicecut::Slice sl) { return ingest.push(std::move(sl)); };
-    if (in.fd >= 0) {
+    if (opt.bam) {
+        if (!gzs->cut_bam(opt.slice_bytes, push, [&] { return ingest.failed(); })) ingest.fail(gzs->err());
+    } else if (in.fd >= 0) {
         const int fd = in.fd;
         if (!slicecut::cut_file_ranges([fd](char* dst, size_t n, uint64_t at) { return pread_all(fd, dst, n, at); }, body_pos, in.file_bytes,
                                        opt.slice_bytes, push))

@@ -1,5 +1,6 @@
-// mgx_bgzf_ctx.h -- the BGZF context (include/mgx_bgzf.h) as its two translation units see it: the compressor
-// (mgx_bgzf.hip) and the inflater (mgx_bgzf_inflate.hip) share its device and streams.
+// mgx_bgzf_ctx.h -- the BGZF context (include/mgx_bgzf.h) as its translation units see it: the compressor
+// (mgx_bgzf.hip), the inflater (mgx_bgzf_inflate.hip) and BAM input (mgx_bam.hip) share its device and streams, and BAM
+// input reads an inflate batch's output where the inflate kernel left it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,4 +24,18 @@ struct mgx_bgzf {
     std::mutex inf_mu;
     uint64_t inf_blocks = 0, inf_bytes_in = 0, inf_bytes_out = 0;
     float inf_ms_kernel = 0;
+    // BAM input (mgx_bam.hip): the last batch waited for
+    std::mutex bam_mu;
+    uint64_t bam_tiles = 0, bam_rewalked = 0, bam_redo = 0;
+    uint32_t bam_rounds = 0;
+    float bam_ms_index = 0, bam_ms_keys = 0;
+};
+
+struct mgx_bgzf_inflate {
+    uint64_t in_cap = 0, out_cap = 0; uint32_t max_blocks = 0;
+    uint8_t* h_in = nullptr; uint64_t* h_off = nullptr; uint8_t* h_out = nullptr; uint32_t* h_status = nullptr;      // pinned
+    uint8_t* d_in = nullptr; uint64_t* d_off = nullptr; uint8_t* d_out = nullptr; uint32_t* d_status = nullptr;
+    hipEvent_t ev_in = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr;
+    uint32_t n_blocks = 0; uint64_t n_in = 0, n_out = 0;
+    bool submitted = false;
 };

@@ -186,15 +186,6 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(InflateArgs a) {
 
 }  // namespace
 
-struct mgx_bgzf_inflate {
-    u64 in_cap = 0, out_cap = 0; u32 max_blocks = 0;
-    u8* h_in = nullptr; u64* h_off = nullptr; u8* h_out = nullptr; u32* h_status = nullptr;      // pinned
-    u8* d_in = nullptr; u64* d_off = nullptr; u8* d_out = nullptr; u32* d_status = nullptr;
-    hipEvent_t ev_in = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr;
-    u32 n_blocks = 0; u64 n_in = 0, n_out = 0;
-    bool submitted = false;
-};
-
 extern "C" {
 
 void mgx_bgzf_inflate_batch_destroy(mgx_bgzf_t* c, mgx_bgzf_inflate_t* b) {

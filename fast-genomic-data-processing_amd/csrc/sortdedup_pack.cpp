@@ -20,8 +20,10 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/mgx_bam.h"
 #include "../../include/mgx_sortdedup.h"
 #include "mgx_common.h"
+#include "sortdedup_pack.h"
 
 extern "C" const char* mgx_last_error(void);
 
@@ -85,7 +87,66 @@ void tile_x_y(const char* q, uint64_t len, uint16_t out[3]) {
     for (int k = 0; k < 3; ++k) out[k] = token_to_u16(tok[first + k], tl[first + k]);
 }
 
+// The pairing loop of mgx_sortdedup_pack, for any holder of records: flag(i), same(i, q) = whether records i < q have
+// equal qnames (asked only while every record between them has i's qname too), emit(k, r, mate) = arrival slot k is
+// input record r.
+// The queue logic only ever looks ahead inside one run of equal qnames, so the input can be cut
+// at qname changes and the pieces packed independently by several threads: the number of records
+// a piece emits equals the number it consumes, hence arrival slot == input slot of the piece's
+// first record, and mate indices are piece-local offsets plus that base.
+template <class Flag, class Same, class Emit>
+int pack_paired(uint64_t n, Flag flag, Same same_qname, Emit emit) {
+    auto pack_range = [&](uint64_t lo, uint64_t hi) -> int {
+        std::vector<uint8_t> taken(hi - lo, 0);
+        uint64_t k = lo;
+        for (uint64_t i = lo; i < hi; ++i) {
+            if (taken[i - lo]) continue;
+            taken[i - lo] = 1;
+            uint64_t mate = hi;
+            if (!(flag(i) & kIgnorable)) {
+                for (uint64_t q = i + 1; q < hi && (taken[q - lo] || same_qname(i, q)); ++q) {
+                    if (taken[q - lo]) continue;
+                    if (!(flag(q) & kIgnorable)) { mate = q; break; }
+                }
+            }
+            int rc;
+            if (mate == hi) {
+                if ((rc = emit(k, i, MGX_NO_MATE))) return rc;
+                k += 1;
+            } else {
+                taken[mate - lo] = 1;
+                if ((rc = emit(k, i, (uint32_t)(k + 1)))) return rc;
+                if ((rc = emit(k + 1, mate, (uint32_t)k))) return rc;
+                k += 2;
+            }
+        }
+        return 0;
+    };
+    unsigned T = std::thread::hardware_concurrency();
+    if (const char* e = getenv("MGX_PACK_THREADS")) T = (unsigned)atoi(e);
+    if (T < 1) T = 1;
+    if (T > 64) T = 64;
+    if (n < 200000 || T == 1) return pack_range(0, n);
+    std::vector<uint64_t> cut(T + 1, n);
+    cut[0] = 0;
+    for (unsigned t = 1; t < T; ++t) {
+        uint64_t p = n * t / T;
+        while (p < n && p > 0 && same_qname(p - 1, p)) ++p;       // never split a qname group
+        cut[t] = std::max(p, cut[t - 1]);
+    }
+    std::vector<int> rcs(T, 0);
+    std::vector<std::string> errs(T);
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < T; ++t)
+        pool.emplace_back([&, t]() { rcs[t] = pack_range(cut[t], cut[t + 1]); if (rcs[t]) errs[t] = mgx_last_error(); });
+    for (auto& th : pool) th.join();
+    for (unsigned t = 0; t < T; ++t) if (rcs[t]) { mgx::set_error("%s", errs[t].c_str()); return rcs[t]; }
+    return 0;
+}
+
 }  // namespace
+
+void mgx::qname_tile_x_y(const char* q, uint64_t len, uint16_t out[3]) { tile_x_y(q, len, out); }
 
 extern "C" int mgx_sortdedup_pack(const mgx_raw_records_t* raw, mgx_rec_t* out, uint32_t* out_input_index,
                                   uint64_t* out_L) {
@@ -133,54 +194,32 @@ extern "C" int mgx_sortdedup_pack_scored(const mgx_raw_records_t* raw, const uin
         return 0;
     };
 
-    // The queue logic only ever looks ahead inside one run of equal qnames, so the input can be cut
-    // at qname changes and the pieces packed independently by several threads: the number of records
-    // a piece emits equals the number it consumes, hence arrival slot == input slot of the piece's
-    // first record, and mate indices are piece-local offsets plus that base.
-    auto pack_range = [&](uint64_t lo, uint64_t hi) -> int {
-        std::vector<uint8_t> taken(hi - lo, 0);
-        uint64_t k = lo;
-        for (uint64_t i = lo; i < hi; ++i) {
-            if (taken[i - lo]) continue;
-            taken[i - lo] = 1;
-            uint64_t mate = hi;
-            if (!(raw->flag[i] & kIgnorable)) {
-                for (uint64_t q = i + 1; q < hi && (taken[q - lo] || same_qname(i, q)); ++q) {
-                    if (taken[q - lo]) continue;
-                    if (!(raw->flag[q] & kIgnorable)) { mate = q; break; }
-                }
-            }
-            int rc;
-            if (mate == hi) {
-                if ((rc = emit(k, i, MGX_NO_MATE))) return rc;
-                k += 1;
-            } else {
-                taken[mate - lo] = 1;
-                if ((rc = emit(k, i, (uint32_t)(k + 1)))) return rc;
-                if ((rc = emit(k + 1, mate, (uint32_t)k))) return rc;
-                k += 2;
-            }
-        }
+    return pack_paired(n, [&](uint64_t i) { return raw->flag[i]; }, same_qname, emit);
+}
+
+extern "C" int mgx_bam_pack_keys(uint64_t n, const mgx_bam_key_t* keys, uint32_t n_targets, const uint64_t* target_len, mgx_rec_t* out,
+                                 uint32_t* out_input_index, uint64_t* out_L) {
+    if (!out_L || (n && (!keys || !out || !out_input_index)) || (n_targets && !target_len)) { mgx::set_error("NULL argument"); return -EINVAL; }
+    if (n >= 0xFFFFFFFFull) { mgx::set_error("more than 2^32-1 records"); return -E2BIG; }
+    std::vector<uint64_t> ktable(n_targets + 1);
+    uint64_t acc = 0;
+    for (uint32_t t = 0; t < n_targets; ++t) { ktable[t] = acc; acc += target_len[t]; }
+    ktable[n_targets] = acc;
+    *out_L = acc;
+    auto emit = [&](uint64_t k, uint64_t r, uint32_t mate) -> int {
+        const mgx_bam_key_t& key = keys[r];
+        if (key.tid >= (int32_t)n_targets) { mgx::set_error("record %llu: tid %d out of range", (unsigned long long)r, key.tid); return -EINVAL; }
+        if (key.redo) { mgx::set_error("record %llu: its key is marked redo (mgx_bam_keys_redo completes it)", (unsigned long long)r); return -EINVAL; }
+        mgx_rec_t& o = out[k];
+        memset(&o, 0, sizeof o);
+        o.coord = key.tid < 0 ? acc : ktable[key.tid] + (uint64_t)(int64_t)key.pos;
+        o.prime5 = o.coord + (uint64_t)key.d5;
+        o.flag = key.flag; o.score = key.score;
+        o.tile = key.tile; o.x = key.x; o.y = key.y;
+        o.mate = mate;
+        out_input_index[k] = (uint32_t)r;
         return 0;
     };
-    unsigned T = std::thread::hardware_concurrency();
-    if (const char* e = getenv("MGX_PACK_THREADS")) T = (unsigned)atoi(e);
-    if (T < 1) T = 1;
-    if (T > 64) T = 64;
-    if (n < 200000 || T == 1) return pack_range(0, n);
-    std::vector<uint64_t> cut(T + 1, n);
-    cut[0] = 0;
-    for (unsigned t = 1; t < T; ++t) {
-        uint64_t p = n * t / T;
-        while (p < n && p > 0 && same_qname(p - 1, p)) ++p;       // never split a qname group
-        cut[t] = std::max(p, cut[t - 1]);
-    }
-    std::vector<int> rcs(T, 0);
-    std::vector<std::string> errs(T);
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < T; ++t)
-        pool.emplace_back([&, t]() { rcs[t] = pack_range(cut[t], cut[t + 1]); if (rcs[t]) errs[t] = mgx_last_error(); });
-    for (auto& th : pool) th.join();
-    for (unsigned t = 0; t < T; ++t) if (rcs[t]) { mgx::set_error("%s", errs[t].c_str()); return rcs[t]; }
-    return 0;
+    // same(i, q) is asked while every record between i and q has i's qname: the chained bit of q decides
+    return pack_paired(n, [&](uint64_t i) { return keys[i].flag; }, [&](uint64_t, uint64_t q) { return keys[q].same_qname != 0; }, emit);
 }

@@ -247,3 +247,37 @@ BGZF_SYMBOLS.update({
 })
 BGZF_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p)
 SYMBOLS.update(BGZF_SYMBOLS)
+
+
+# ---- include/mgx_bam.h ----------------------------------------------------------------------------
+class BamKey(C.Structure):
+    _fields_ = [("d5", C.c_int64), ("tid", C.c_int32), ("pos", C.c_int32), ("end", C.c_int32), ("flag", C.c_uint16), ("score", C.c_uint16),
+                ("tile", C.c_uint16), ("x", C.c_uint16), ("y", C.c_uint16), ("same_qname", C.c_uint8), ("redo", C.c_uint8)]
+
+
+class BamHeader(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("text_off", C.c_uint64), ("text_len", C.c_uint64), ("n_ref", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class BamStats(C.Structure):
+    _fields_ = [("n_tiles", C.c_uint64), ("n_tiles_rewalked", C.c_uint64), ("n_redo", C.c_uint64), ("n_rounds", C.c_uint32),
+                ("ms_index", C.c_float), ("ms_keys", C.c_float)]
+
+
+BAM_SYMBOLS = {
+    "mgx_bam_parse_header": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(BamHeader), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_bam_walk_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_bam_keys_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mgx_bam_keys_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mgx_bam_keys_redo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mgx_bam_pack_keys": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgx_bam_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mgx_bam_batch_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "mgx_bam_batch_input": (C.c_void_p, [C.c_void_p]),
+    "mgx_bam_batch_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mgx_bam_batch_wait": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_bam_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_bam_stats": (C.c_int, [C.c_void_p, C.POINTER(BamStats)]),
+}
+SYMBOLS.update(BAM_SYMBOLS)
