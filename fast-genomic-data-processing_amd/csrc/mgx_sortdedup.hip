@@ -1594,6 +1594,7 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     c->ev_used = 0; c->scatter_bytes = 0;
     HIP_TRY(hipEventRecord(c->ev_start, s));
     for (int attempt = 0; attempt < 2; ++attempt) {
+        c->stats.n_builds = (uint32_t)attempt + 1;
         HIP_TRY(hipMemsetAsync(c->d_sc, 0, sizeof(Scalars), s));
         if (n) {
             HIP_TRY(hipMemsetAsync(c->d_dup, 0, n, s));
@@ -1631,6 +1632,8 @@ int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     // is safely below L; otherwise the reference's exact layout with global atomics
     const uint64_t maxpos = std::max<uint64_t>(c->sc.max_k2d, std::max<uint64_t>(c->sc.max_k1d >> 2, c->sc.max_k1s >> 2));
     const bool tiled = c->L > 64 && maxpos < c->L - 64;
+    c->stats.bitmap_tiled = tiled ? 1 : 0;
+    c->stats.n_pipeline_runs = 1;
     const uint64_t Lp = (c->L + kIndTile - 1) / kIndTile * kIndTile;
     const uint64_t ind_off = tiled ? Lp : c->L;                 // offset of the reverse-strand half
     const uint64_t ind_bits = tiled ? 2 * Lp : c->indicator_bits;
@@ -1751,6 +1754,7 @@ static int finish_run(mgx_sortdedup_t* c) {
         c->near_by_position = false;
         const int rc = mgx_sortdedup_run(c);
         if (rc) return rc;
+        c->stats.n_pipeline_runs = 2;
         HIP_TRY(hipStreamSynchronize(c->compute));
         HIP_TRY(hipMemcpy(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost));
     }
@@ -1778,6 +1782,11 @@ int mgx_sortdedup_stats(mgx_sortdedup_t* c, mgx_sortdedup_stats_t* out) {
     { const int rc = finish_run(c); if (rc) return rc; }
     mgx_sortdedup_stats_t st = c->stats;
     st.n_dup_records = c->sc.n_dup;
+    st.n_near = c->sc.n_near;
+    st.n_multi_far = c->sc.n_multi_d; st.n_multi_single = c->sc.n_multi_s; st.n_multi_near = c->sc.n_multi_n;
+    st.n_long_far = c->sc.n_long_d; st.n_long_single = c->sc.n_long_s; st.n_long_near = c->sc.n_long_n;
+    st.packed_coord = c->packed_coord ? 1 : 0; st.packed_pair = c->packed_pair ? 1 : 0;
+    st.near_by_position = c->near_by_position ? 1 : 0;
     HIP_TRY(hipEventElapsedTime(&st.ms_total, c->ev_start, c->ev_stop));
     st.ms_radix_scatter = 0;
     for (size_t k = 0; k + 1 < c->ev_used + 1 && k + 1 < c->ev_scatter.size() + 1 && k < c->ev_used; k += 2) {

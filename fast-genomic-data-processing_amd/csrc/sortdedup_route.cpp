@@ -13,6 +13,11 @@
 //   * marking half    the templates keyed in the shard's range, as records with shard-local mate indices
 //   * marks           for every pair, each 5' end that lies in ANOTHER shard's range is sent to that shard as
 //                     (position, strand half): the only data that crosses shards, 8 bytes per straddling end
+//                     The reference's map is one array of bits, pos (+ L on the reverse strand), so an end at or
+//                     beyond L is also read by the other half: a forward end at L + d is the reverse strand's bit of
+//                     position d, and a reverse end at d is the forward strand's bit of L + d.  Such an end is sent
+//                     to the shard of the read that would consult it as well (the second kind only when the input
+//                     holds a forward fragment at or beyond L at all, so ordinary inputs exchange nothing more).
 // Concatenating the shards' orders in shard order is the global order; duplicate flags come back per
 // marking record and are scattered to arrival indices by mgx_sortdedup_merge.
 #include <algorithm>
@@ -43,7 +48,7 @@ struct ShardData {
 };
 
 // per chunk and shard: how many ordering records / marking records / marks the chunk contributes
-struct Counts { uint64_t order = 0, mark = 0, marks = 0; };
+struct Counts { uint64_t order = 0, mark = 0, marks = 0, marks_beyond = 0; };
 
 }  // namespace
 
@@ -75,8 +80,19 @@ inline PairEnds pair_ends(const mgx_rec_t& a, const mgx_rec_t& b) {
 
 // One walk over records [a, b): `emit` decides what happens with each routed item, so that the counting pass
 // and the writing pass cannot disagree.
+// on_mark(shard, mark, beyond): beyond = the mark is a reverse end seen from the forward half (position + L).
 template <class OnOrder, class OnTemplate, class OnMark>
 int walk(const mgx_sortdedup_routed& R, const mgx_rec_t* recs, uint64_t a, uint64_t b, OnOrder on_order, OnTemplate on_template, OnMark on_mark) {
+    const uint32_t last = R.n_shards - 1;
+    auto end_marks = [&](uint32_t home, uint64_t p, bool rev) {
+        const uint32_t sp = shard_of(R, p);
+        if (sp != home) on_mark(sp, (p << 1) | (rev ? 1u : 0u), false);
+        if (!rev && p >= R.L && p < 4 * R.L) {                    // bit p is the reverse strand's bit of position p - L
+            const uint32_t sq = shard_of(R, p - R.L);
+            if (sq != home) on_mark(sq, ((p - R.L) << 1) | 1u, false);
+        }
+        if (rev && p < 3 * R.L && last != home) on_mark(last, (p + R.L) << 1, true);   // bit p + L: a forward read at p + L >= L
+    };
     for (uint64_t i = a; i < b; ++i) {
         const mgx_rec_t& r = recs[i];
         on_order(shard_of(R, r.coord), i);
@@ -88,9 +104,8 @@ int walk(const mgx_sortdedup_routed& R, const mgx_rec_t* recs, uint64_t a, uint6
         const PairEnds e = pair_ends(r, m);
         const uint32_t s = shard_of(R, e.p1);
         on_template(s, i, (uint64_t)r.mate);
-        const uint32_t s1 = shard_of(R, e.p1), s2 = shard_of(R, e.p2);   // s1 == s by construction
-        if (s1 != s) on_mark(s1, (e.p1 << 1) | (e.rev1 ? 1u : 0u));
-        if (s2 != s) on_mark(s2, (e.p2 << 1) | (e.rev2 ? 1u : 0u));
+        end_marks(s, e.p1, e.rev1);
+        end_marks(s, e.p2, e.rev2);
     }
     return 0;
 }
@@ -120,6 +135,7 @@ int mgx_sortdedup_route(uint64_t L, uint64_t n_records, const mgx_rec_t* recs, u
     const uint64_t per = (n_records + n_chunks - 1) / n_chunks;
     std::vector<std::vector<Counts>> cnt(n_chunks, std::vector<Counts>(n_shards));
     std::vector<int> rcs(n_chunks, 0);
+    std::vector<char> fwd_beyond(n_chunks, 0);       // the chunk holds a forward fragment with its 5' end at or beyond L
     auto run_chunks = [&](auto body) {
         std::vector<std::thread> th;
         for (uint64_t c = 1; c < n_chunks; ++c) th.emplace_back(body, c);
@@ -132,10 +148,16 @@ int mgx_sortdedup_route(uint64_t L, uint64_t n_records, const mgx_rec_t* recs, u
         std::vector<Counts>& k = cnt[c];
         rcs[c] = walk(*R, recs, a, b,
                       [&](uint32_t s, uint64_t) { k[s].order++; },
-                      [&](uint32_t s, uint64_t, uint64_t m) { k[s].mark += m == MGX_NO_MATE ? 1 : 2; },
-                      [&](uint32_t s, uint64_t) { k[s].marks++; });
+                      [&](uint32_t s, uint64_t i, uint64_t m) {
+                          k[s].mark += m == MGX_NO_MATE ? 1 : 2;
+                          if (m == MGX_NO_MATE && recs[i].prime5 >= L && !(recs[i].flag & 0x10)) fwd_beyond[c] = 1;
+                      },
+                      [&](uint32_t s, uint64_t, bool beyond) { if (beyond) k[s].marks_beyond++; else k[s].marks++; });
     });
     for (int rc : rcs) if (rc) { delete R; set_error("a record's mate index is outside the record set"); return rc; }
+    const bool send_beyond = std::any_of(fwd_beyond.begin(), fwd_beyond.end(), [](char f) { return f != 0; });
+    if (send_beyond)
+        for (auto& k : cnt) for (Counts& x : k) x.marks += x.marks_beyond;
     // chunk-major prefix inside every shard keeps arrival order
     std::vector<std::vector<Counts>> base(n_chunks, std::vector<Counts>(n_shards));
     for (uint32_t s = 0; s < n_shards; ++s) {
@@ -173,7 +195,8 @@ int mgx_sortdedup_route(uint64_t L, uint64_t n_records, const mgx_rec_t* recs, u
                  d.mark_recs[k].mate = (uint32_t)(k + 1);
                  d.mark_recs[k + 1] = recs[m]; d.mark_recs[k + 1].mate = (uint32_t)k; d.mark_arrival[k + 1] = (uint32_t)m;
              },
-             [&](uint32_t s, uint64_t mark) {
+             [&](uint32_t s, uint64_t mark, bool beyond) {
+                 if (beyond && !send_beyond) return;
                  ShardData& d = R->shards[s];
                  const uint64_t k = at[s].marks++;
                  if (d.kept) d.marks[k] = mark;

@@ -144,6 +144,11 @@ class SortDedupStats(C.Structure):
         ("radix_scatter_bytes", C.c_uint64), ("alg_bytes", C.c_uint64),
         ("ms_scatter_records", C.c_float), ("n_scatter_records", C.c_uint32), ("scatter_records_bytes", C.c_uint64),
         ("n_key_hist_launches", C.c_uint32), ("pad_", C.c_uint32),
+        # which paths the returned pipeline pass took
+        ("n_near", C.c_uint32), ("n_multi_far", C.c_uint32), ("n_multi_single", C.c_uint32), ("n_multi_near", C.c_uint32),
+        ("n_long_far", C.c_uint32), ("n_long_single", C.c_uint32), ("n_long_near", C.c_uint32),
+        ("n_builds", C.c_uint32), ("n_pipeline_runs", C.c_uint32), ("bitmap_tiled", C.c_uint32),
+        ("packed_coord", C.c_uint32), ("packed_pair", C.c_uint32), ("near_by_position", C.c_uint32), ("pad2_", C.c_uint32),
     ]
 
 

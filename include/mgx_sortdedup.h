@@ -81,6 +81,21 @@ typedef struct mgx_sortdedup_stats {
     uint32_t n_key_hist_launches;   /* histogram passes of the last run that re-read the keys (k_radix_hist); the others (the
                                      * first pass of the record sort) merge the histograms the build kernel left (k_hist_merge) */
     uint32_t pad_;
+    /* Which paths the pipeline pass took whose results are returned (after the huge-run fallback: the second pass). */
+    uint32_t n_near;                /* double pairs keyed in the one-word near form; n_double - n_near took the two-word form */
+    uint32_t n_multi_far;           /* runs of two or more two-word (far) pair entries */
+    uint32_t n_multi_single;        /* runs of two or more single-read entries */
+    uint32_t n_multi_near;          /* runs of two or more near entries: per start position, or per identity in the exact mode */
+    uint32_t n_long_far;            /* far runs beyond the per-lane walk, handed to a whole workgroup */
+    uint32_t n_long_single;         /* single-read runs handed to a whole workgroup */
+    uint32_t n_long_near;           /* near runs handed to a whole workgroup */
+    uint32_t n_builds;              /* 1, or 2 when a device maximum >= 2^32 made the build kernel run again with wide keys */
+    uint32_t n_pipeline_runs;       /* 1, or 2 after the huge-run fallback */
+    uint32_t bitmap_tiled;          /* 1: tiled bitmap (plain stores, reverse half at a tile boundary); 0: reference layout, atomics */
+    uint32_t packed_coord;          /* 1: record sort on coord << 32 | arrival index words */
+    uint32_t packed_pair;           /* 1: far entries carry mate end << 32 | record in one word (and near pairs exist at all) */
+    uint32_t near_by_position;      /* 1: near pairs sorted on record 1's 5' end only; 0: six-pass sort on the whole identity */
+    uint32_t pad2_;
 } mgx_sortdedup_stats_t;
 
 /* Host side (B3-B7): pair records by adjacent equal qname exactly as BamParser does, derive the

@@ -77,6 +77,8 @@ def test_long_runs_and_total_ties(sd_engine, sd_oracle, synth):
     assert np.array_equal(dup, want_dup)
     assert dup.sum() == 2 * (n_t - 6) + 5000
     assert (dup[2 * n_t:] == 1).all()                  # every single collides with a pair end here
+    st = sd_engine.stats()
+    assert st["n_long_near"] + st["n_long_far"] >= 6 and st["n_long_single"] >= 3      # whole workgroups took those runs
 
 
 @pytest.mark.parametrize("shift,L", [(0, 100_000), (5_000_000_000, 6_000_000_000)], ids=["packed", "wide"])
@@ -117,6 +119,7 @@ def test_ends_near_the_reference_end_use_the_atomic_bitmap(sd_engine, sd_oracle,
     assert dup[:n_pair_recs].sum() == 1588
     assert (dup[n_pair_recs:n_pair_recs + 200] == 1).all()           # every reverse single lies on a pair's reverse end
     assert dup[n_pair_recs + 200:].sum() == 199                      # forward ones: all but the kept read at 2000
+    assert sd_engine.stats()["bitmap_tiled"] == 0
 
 
 def test_scaled_config_properties(sd_engine, sd_oracle, synth):
@@ -203,6 +206,7 @@ def test_near_sort_modes_agree(pkg, sd_oracle, synth, monkeypatch):
         eng.close()
         assert np.array_equal(order, want_order) and np.array_equal(dup, want_dup)
         assert st["n_radix_passes"] > 0
+        assert st["near_by_position"] == (1 if exact == "0" else 0) and st["n_pipeline_runs"] == 1
     monkeypatch.delenv("MGX_SORTDEDUP_NEAR_EXACT")
     # 6000 pairs starting at one position with three different inserts: beyond the in-run limit
     n_t = 6000
@@ -221,6 +225,8 @@ def test_near_sort_modes_agree(pkg, sd_oracle, synth, monkeypatch):
     order, dup = eng.sort_mark(50000, big)
     assert np.array_equal(order, want_order) and np.array_equal(dup, want_dup)
     assert dup.sum() == 2 * (n_t - 3)
+    st = eng.stats()
+    assert st["n_pipeline_runs"] == 2 and st["near_by_position"] == 0
     # the fallback is also taken when the statistics are asked for before the results
     eng.upload(50000, big); eng.run()
     assert eng.stats()["n_dup_records"] == 2 * (n_t - 3)
@@ -242,7 +248,8 @@ def test_wide_keys_take_the_unpacked_path(sd_engine, sd_oracle, synth):
     want_order, want_dup, _ = sd_oracle.run(L, recs)
     order, dup = sd_engine.sort_mark(L, recs)
     assert np.array_equal(order, want_order) and np.array_equal(dup, want_dup)
-    assert sd_engine.stats()["key_bits_coord"] > 32
+    st = sd_engine.stats()
+    assert st["key_bits_coord"] > 32 and st["packed_coord"] == 0 and st["n_near"] == 0
 
 
 def test_wrapped_five_prime_forces_the_fallback(sd_engine, sd_oracle, synth):
@@ -256,6 +263,8 @@ def test_wrapped_five_prime_forces_the_fallback(sd_engine, sd_oracle, synth):
     want_order, want_dup, _ = sd_oracle.run(L, recs)
     order, dup = sd_engine.sort_mark(L, recs)
     assert np.array_equal(order, want_order) and np.array_equal(dup, want_dup)
+    st = sd_engine.stats()
+    assert st["n_builds"] == 2 and st["packed_pair"] == 0
 
 
 def test_out_of_range_mate_is_an_error_not_a_fault(pkg, sd_engine, synth):
