@@ -12,7 +12,7 @@
 //              asc), the rest are duplicates (main.cpp:269-280, 319-340); singles additionally
 //              test the indicator bitmap
 //
-// No collective and no host round trip inside the pipeline except one 64-byte read-back of the
+// No collective and no host round trip inside the pipeline except one 640-byte read-back of the
 // entry counts and key maxima (they size the sorts and pick the number of digit passes).
 #include <hip/hip_runtime.h>
 
@@ -33,6 +33,7 @@
 
 #include "../../include/mgx_sortdedup.h"
 #include "mgx_common.h"
+#include "sortdedup_stage.h"
 
 using mgx::set_error;
 
@@ -1036,6 +1037,19 @@ inline int bits_of(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b
 }  // namespace
 
 struct mgx_sortdedup {
+    // a device array that only grows; growing discards the contents.  A plain pair, no destructor: ensure_recs assigns one over another
+    template <typename T>
+    struct Grow {
+        T* p = nullptr; size_t cap = 0;
+        void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+        int grow(size_t count) {
+            if (count <= cap) return 0;
+            release();
+            HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
+            cap = count;
+            return 0;
+        }
+    };
     int device = 0;
     unsigned flags = 0;
     hipStream_t compute = nullptr, copy = nullptr;
@@ -1044,10 +1058,10 @@ struct mgx_sortdedup {
     u32 n = 0;                             // records the duplicate search works on (the marking half of a shard)
     u32 n_order = 0;                       // records the coordinate sort orders (== n unless the input is a shard)
     bool sharded = false;
-    u64* d_ocoord = nullptr; u32* d_oarr = nullptr; size_t order_cap = 0;   // a shard's ordering half as uploaded
-    u64* d_marks = nullptr; size_t marks_cap = 0; u32 n_marks = 0;          // indicator marks routed from other shards
+    Grow<u64> ocoord; Grow<u32> oarr;      // a shard's ordering half as uploaded
+    Grow<u64> marks; u32 n_marks = 0;      // indicator marks routed from other shards
     size_t cap = 0;                        // record capacity of the work buffers below
-    mgx_rec_t* d_recs = nullptr; size_t recs_cap = 0;      // the uploaded records (grown on demand by a streamed upload)
+    Grow<mgx_rec_t> recs;                  // the uploaded records (a streamed upload grows it by hand: ensure_recs keeps the contents)
     void* d_wire[2] = {nullptr, nullptr};  // device side of the staging buffers: compact 24-byte records before expansion
     uint64_t up_L = 0, up_high = 0;        // streamed upload in progress: reference length, highest record index seen + 1
     bool uploading = false;
@@ -1060,8 +1074,8 @@ struct mgx_sortdedup {
     struct Scratch { u32 *hist = nullptr, *chunk = nullptr, *longl = nullptr, *multi = nullptr; } scr[3];
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_ind = nullptr, ev_side[2] = {nullptr, nullptr};
-    u32* d_indicator = nullptr; uint64_t indicator_bits = 0; size_t indicator_cap_words = 0;
-    u32* d_sub_start = nullptr; size_t sub_cap = 0;      // first near entry per kNearSpan positions (bitmap pass)
+    Grow<u32> indicator; uint64_t indicator_bits = 0;    // the bitmap, in 32-bit words
+    Grow<u32> sub_start;                                 // first near entry per kNearSpan positions (bitmap pass)
     uint8_t* d_dup = nullptr;
     u32* d_half_hist = nullptr;            // [ceil(n / kBuildBlock)][256], written by the build kernel
     Scalars* d_sc = nullptr;
@@ -1072,8 +1086,7 @@ struct mgx_sortdedup {
     std::vector<hipEvent_t> ev_scatter;    // pairs (start, stop) per scatter launch
     size_t ev_used = 0;
     size_t ev_rec_begin = 0, ev_rec_end = 0;   // event range of the record sort's scatter launches
-    uint64_t rec_scatter_bytes = 0;
-    uint64_t scatter_bytes = 0;
+    uint64_t rec_scatter_bytes = 0, scatter_bytes = 0;
     int order_buf = 0;                     // which d_cval holds the final order
     bool packed_coord = false;             // L < 2^32: coordinate sort on packed (coord, index) words
     bool packed_pair = false;              // every 5' end < 2^32: (mate end, record) ride in one word
@@ -1088,17 +1101,16 @@ namespace {
 
 constexpr size_t kPinnedChunk = 64u << 20;
 
+template <typename T>
+void dfree(T*& p) { (void)hipFree(p); p = nullptr; }
+
 void free_buffers(mgx_sortdedup* c) {
     for (int i = 0; i < 2; ++i) {
-        (void)hipFree(c->d_ckey[i]); (void)hipFree(c->d_cval[i]); (void)hipFree(c->d_k1[i]); (void)hipFree(c->d_k2[i]);
-        (void)hipFree(c->d_prec[i]); (void)hipFree(c->d_sk1[i]); (void)hipFree(c->d_srec[i]);
-        (void)hipFree(c->d_nk[i]); (void)hipFree(c->d_nrec[i]); c->d_nk[i] = nullptr; c->d_nrec[i] = nullptr;
-        c->d_ckey[i] = c->d_k1[i] = c->d_k2[i] = c->d_sk1[i] = nullptr;
-        c->d_cval[i] = c->d_prec[i] = c->d_srec[i] = nullptr;
+        dfree(c->d_ckey[i]); dfree(c->d_cval[i]); dfree(c->d_k1[i]); dfree(c->d_k2[i]); dfree(c->d_prec[i]);
+        dfree(c->d_sk1[i]); dfree(c->d_srec[i]); dfree(c->d_nk[i]); dfree(c->d_nrec[i]);
     }
-    for (auto& q : c->scr) { (void)hipFree(q.hist); (void)hipFree(q.chunk); (void)hipFree(q.longl); (void)hipFree(q.multi); q.hist = q.chunk = q.longl = q.multi = nullptr; }
-    (void)hipFree(c->d_dup); c->d_dup = nullptr;
-    (void)hipFree(c->d_half_hist); c->d_half_hist = nullptr;
+    for (auto& q : c->scr) { dfree(q.hist); dfree(q.chunk); dfree(q.longl); dfree(q.multi); }
+    dfree(c->d_dup); dfree(c->d_half_hist);
     c->cap = 0;
 }
 
@@ -1182,30 +1194,40 @@ int radix_sort(mgx_sortdedup* c, hipStream_t s, const mgx_sortdedup::Scratch& q,
     return 0;
 }
 
+inline u64 tile_aligned(u64 L) { return (L + kIndTile - 1) / kIndTile * kIndTile; }   // where the tiled bitmap's reverse-strand half starts
+
+// Layout of the indicator bitmap for one run: tiled (plain stores, reverse half at a tile-aligned offset) whenever every
+// 5' end is safely below L; otherwise the reference's exact layout with global atomics.
+struct BitmapPlan {
+    bool tiled;
+    u64 Lp, ind_off, ind_bits;   // tile_aligned(L); offset of the reverse-strand half; bits of both halves
+    u32 n_ind_tiles, n_sub;      // bitmap tiles, entries of the near pass's sub-tile table
+};
+
 // duplicate search over one sorted entry array: run heads -> dense list -> marks (+ long runs)
 template <bool DOUBLE, bool PK, int KS = 0>
 void launch_find(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, const u32* rec, u32 n_entries,
-                 const mgx_sortdedup::Scratch& q, u32* n_multi, u64 ind_bits, u64 ind_off, u32* sub_start = nullptr, u32 n_sub = 0) {
+                 const mgx_sortdedup::Scratch& q, u32* n_multi, const BitmapPlan& bp, u32* sub_start = nullptr, u32 n_sub = 0) {
     if (!n_entries) return;
     const u32 per = 256 * kFindItems;
     hipLaunchKernelGGL((k_find_runs<DOUBLE, PK, KS>), dim3((n_entries + per - 1) / per), dim3(256), 0, s, k1, k2, rec, n_entries,
-                       c->d_indicator, ind_bits, ind_off, c->d_dup, q.multi, n_multi, sub_start, n_sub);
+                       c->indicator.p, bp.ind_bits, bp.ind_off, c->d_dup, q.multi, n_multi, sub_start, n_sub);
 }
 
 template <bool DOUBLE, bool PK, int KS = 0>
 void launch_mark(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, const u32* rec, u32 n_entries,
-                 const mgx_sortdedup::Scratch& q, u32* n_multi, u32* n_long, u64 ind_bits, u64 ind_off, bool find_done = false,
+                 const mgx_sortdedup::Scratch& q, u32* n_multi, u32* n_long, const BitmapPlan& bp, bool find_done = false,
                  u32 rec_mask = 0xFFFFFFFFu) {
     if (!n_entries) return;
-    if (!find_done) launch_find<DOUBLE, PK, KS>(c, s, k1, k2, rec, n_entries, q, n_multi, ind_bits, ind_off);
-    hipLaunchKernelGGL((k_mark_list<DOUBLE, PK, KS>), dim3(c->n_cu * 16), dim3(256), 0, s, k1, k2, rec, n_entries, c->d_recs, c->n,
-                       c->d_indicator, ind_bits, ind_off, c->d_dup, q.multi, n_multi, q.longl, n_long, rec_mask);
+    if (!find_done) launch_find<DOUBLE, PK, KS>(c, s, k1, k2, rec, n_entries, q, n_multi, bp);
+    hipLaunchKernelGGL((k_mark_list<DOUBLE, PK, KS>), dim3(c->n_cu * 16), dim3(256), 0, s, k1, k2, rec, n_entries, c->recs.p, c->n,
+                       c->indicator.p, bp.ind_bits, bp.ind_off, c->d_dup, q.multi, n_multi, q.longl, n_long, rec_mask);
     if constexpr (KS > kNearScoreBits)
-        hipLaunchKernelGGL((k_mark_long_sub<KS>), dim3(c->n_cu * 2), dim3(256), 0, s, k1, rec, n_entries, c->d_recs, c->d_dup, q.longl, n_long,
+        hipLaunchKernelGGL((k_mark_long_sub<KS>), dim3(c->n_cu * 2), dim3(256), 0, s, k1, rec, n_entries, c->recs.p, c->d_dup, q.longl, n_long,
                            &c->d_sc->huge_runs, rec_mask);
     else
-        hipLaunchKernelGGL((k_mark_long<DOUBLE, PK, KS>), dim3(c->n_cu * 2), dim3(256), 0, s, k1, k2, rec, n_entries, c->d_recs,
-                           c->d_indicator, ind_bits, ind_off, c->d_dup, q.longl, n_long, rec_mask);
+        hipLaunchKernelGGL((k_mark_long<DOUBLE, PK, KS>), dim3(c->n_cu * 2), dim3(256), 0, s, k1, k2, rec, n_entries, c->recs.p,
+                           c->indicator.p, bp.ind_bits, bp.ind_off, c->d_dup, q.longl, n_long, rec_mask);
 }
 
 // a run-time choice as a template argument: f(std::true_type{}) or f(std::false_type{})
@@ -1214,22 +1236,21 @@ void with_bool(bool b, F&& f) {
     if (b) f(std::true_type{}); else f(std::false_type{});
 }
 
-// record-END bits of the far pairs into the bitmap: the atomic form, or the tiled one over n_ind_tiles tiles with the
-// reverse half at Lp.  define: this is the first pass over the tiled bitmap (only the record-2 pass ever is).
+// record-END bits of the far pairs into the bitmap: the atomic form, or the tiled one over its tiles with the reverse
+// half at Lp.  define: this is the first pass over the tiled bitmap (only the record-2 pass ever is).
 template <int END>
-void launch_indicator(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, u32 nd, bool tiled, u64 Lp, u32 n_ind_tiles,
-                      bool define = false) {
+void launch_indicator(mgx_sortdedup* c, hipStream_t s, const u64* k1, const u64* k2, u32 nd, const BitmapPlan& bp, bool define = false) {
     with_bool(c->packed_pair, [&](auto pk) {
         constexpr bool PK = decltype(pk)::value;
-        if (!tiled) {
-            hipLaunchKernelGGL((k_set_indicator<END, PK>), dim3((nd + 255) / 256), dim3(256), 0, s, k1, k2, nd, c->d_indicator, c->indicator_bits, c->L);
+        if (!bp.tiled) {
+            hipLaunchKernelGGL((k_set_indicator<END, PK>), dim3((nd + 255) / 256), dim3(256), 0, s, k1, k2, nd, c->indicator.p, c->indicator_bits, c->L);
         } else if constexpr (END == 2) {
             with_bool(define, [&](auto def) {
-                hipLaunchKernelGGL((k_indicator_tiles<2, PK, decltype(def)::value>), dim3(n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->d_indicator, Lp);
+                hipLaunchKernelGGL((k_indicator_tiles<2, PK, decltype(def)::value>), dim3(bp.n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->indicator.p, bp.Lp);
             });
         } else {
             assert(!define);
-            hipLaunchKernelGGL((k_indicator_tiles<END, PK, false>), dim3(n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->d_indicator, Lp);
+            hipLaunchKernelGGL((k_indicator_tiles<END, PK, false>), dim3(bp.n_ind_tiles), dim3(256), 0, s, k1, k2, nd, c->indicator.p, bp.Lp);
         }
     });
 }
@@ -1298,9 +1319,8 @@ void mgx_sortdedup_destroy(mgx_sortdedup_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     free_buffers(c);
-    (void)hipFree(c->d_recs); (void)hipFree(c->d_wire[0]); (void)hipFree(c->d_wire[1]);
-    (void)hipFree(c->d_indicator); (void)hipFree(c->d_sub_start); (void)hipFree(c->d_sc);
-    (void)hipFree(c->d_ocoord); (void)hipFree(c->d_oarr); (void)hipFree(c->d_marks);
+    c->recs.release(); c->indicator.release(); c->sub_start.release(); c->ocoord.release(); c->oarr.release(); c->marks.release();
+    (void)hipFree(c->d_wire[0]); (void)hipFree(c->d_wire[1]); (void)hipFree(c->d_sc);
     for (int i = 0; i < 2; ++i) { if (c->pinned[i]) (void)hipHostFree(c->pinned[i]); if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]); }
     for (auto e : c->ev_scatter) (void)hipEventDestroy(e);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
@@ -1312,23 +1332,21 @@ void mgx_sortdedup_destroy(mgx_sortdedup_t* c) {
     delete c;
 }
 
+}  // extern "C"
+
 namespace {
 
 // device room for `n` records; the first `keep` records already uploaded survive a growth
 int ensure_recs(mgx_sortdedup_t* c, size_t n, size_t keep) {
-    if (n <= c->recs_cap) return 0;
-    size_t cap = std::max<size_t>(n, keep ? c->recs_cap + c->recs_cap / 2 : 0);
-    mgx_rec_t* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, std::max<size_t>(cap, 1) * sizeof(mgx_rec_t)) != hipSuccess) {
-        set_error("out of device memory for %zu records", cap);
-        return -ENOMEM;
-    }
-    if (keep && c->d_recs) {
-        HIP_TRY(hipMemcpyAsync(fresh, c->d_recs, keep * sizeof(mgx_rec_t), hipMemcpyDeviceToDevice, c->copy));
+    if (n <= c->recs.cap) return 0;
+    const size_t cap = std::max<size_t>(n, keep ? c->recs.cap + c->recs.cap / 2 : 0);
+    mgx_sortdedup::Grow<mgx_rec_t> fresh;
+    if (fresh.grow(cap)) { set_error("out of device memory for %zu records", cap); return -ENOMEM; }
+    if (keep && c->recs.p) {
+        HIP_TRY(hipMemcpyAsync(fresh.p, c->recs.p, keep * sizeof(mgx_rec_t), hipMemcpyDeviceToDevice, c->copy));
         HIP_TRY(hipStreamSynchronize(c->copy));
     }
-    (void)hipFree(c->d_recs);
-    c->d_recs = fresh; c->recs_cap = cap;
+    c->recs.release(); c->recs = fresh;
     return 0;
 }
 
@@ -1336,25 +1354,12 @@ int ensure_recs(mgx_sortdedup_t* c, size_t n, size_t keep) {
 int prepare_input(mgx_sortdedup_t* c, uint64_t L, size_t capacity) {
     int rc = ensure_capacity(c, capacity);
     if (rc) { set_error("out of device memory for %zu records", capacity); return rc; }
-    // double_pair_indicator: 4L bits like the reference (main.cpp:115)
-    const uint64_t Lp = (L + kIndTile - 1) / kIndTile * kIndTile;          // tile-aligned reverse offset
+    // double_pair_indicator: 4L bits like the reference (main.cpp:115), or the two tile-aligned halves
+    const uint64_t Lp = tile_aligned(L);
     const uint64_t bits = std::max<uint64_t>(4 * L + 64, 2 * Lp + 2 * (uint64_t)kIndTile);
-    const size_t words = (size_t)((bits + 31) / 32);
-    if (words > c->indicator_cap_words) {
-        (void)hipFree(c->d_indicator); c->d_indicator = nullptr; c->indicator_cap_words = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_indicator, words * 4));
-        c->indicator_cap_words = words;
-    }
-    {
-        const size_t n_sub = (size_t)(Lp / kNearSpan) + 2;
-        if (n_sub > c->sub_cap) {
-            (void)hipFree(c->d_sub_start); c->d_sub_start = nullptr; c->sub_cap = 0;
-            HIP_TRY(hipMalloc((void**)&c->d_sub_start, n_sub * 4));
-            c->sub_cap = n_sub;
-        }
-    }
-    c->indicator_bits = 4 * L;
-    c->L = L; c->ran = false;
+    if ((rc = c->indicator.grow((size_t)((bits + 31) / 32)))) return rc;
+    if ((rc = c->sub_start.grow((size_t)(Lp / kNearSpan) + 2))) return rc;
+    c->indicator_bits = 4 * L; c->L = L; c->ran = false;
     c->near_by_position = true;             // decided again for every input (see finish_run)
     c->packed_coord = L < 0xFFFFFFFFull;     // coord <= L (bam_record.cpp:18-24)
     c->packed_pair = L < 0xF0000000ull;      // 5' ends <= L + clip; verified against the device maximum
@@ -1364,11 +1369,7 @@ int prepare_input(mgx_sortdedup_t* c, uint64_t L, size_t capacity) {
 int ensure_staging(mgx_sortdedup_t* c, size_t chunk) {
     if (chunk <= c->pinned_cap) return 0;
     HIP_TRY(hipStreamSynchronize(c->copy));
-    for (int i = 0; i < 2; ++i) {
-        if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
-        (void)hipFree(c->d_wire[i]);
-        c->pinned[i] = nullptr; c->d_wire[i] = nullptr;
-    }
+    for (int i = 0; i < 2; ++i) { if (c->pinned[i]) (void)hipHostFree(c->pinned[i]); c->pinned[i] = nullptr; dfree(c->d_wire[i]); }
     c->pinned_cap = 0;
     for (int i = 0; i < 2; ++i) {
         HIP_TRY(hipHostMalloc(&c->pinned[i], chunk, hipHostMallocDefault));
@@ -1378,135 +1379,216 @@ int ensure_staging(mgx_sortdedup_t* c, size_t chunk) {
     return 0;
 }
 
-int upload_threads() {
+// Host memory -> HBM through the two pinned staging buffers on the copy stream (asynchronous; the caller syncs), in pieces
+// of as many whole items as a buffer holds; the buffers take turns and one is refilled only after what was last enqueued
+// from it has left it (pin_ev).  records: a piece travels in the 24-byte wire form and is expanded on the device whenever
+// its values allow it, raw otherwise (MGX_SORTDEDUP_WIRE=32 keeps every piece raw).
+int staged_upload(mgx_sortdedup_t* c, void* dst_, const void* src_, size_t n_items, size_t item_bytes, bool records = false) {
     // one core moves ~12 GB/s into the staging buffer, less than a quarter of what the link takes: every piece is
     // split over a gang of threads (MGX_UPLOAD_THREADS, default 4).  Measured on the GPU box, 200 M records, 24-byte
     // wire form (profiles/r02_upload_threads.txt): 4 threads 89.6 ms, 8: 95.9, 12: 97.4, 16: 113.4 -- beyond four the
     // threads only compete for memory bandwidth; raw 32-byte records with 8 threads: 114.9 ms.
-    static const int n_thr = [] {
-        const char* e = getenv("MGX_UPLOAD_THREADS");
-        const int v = e ? atoi(e) : 4;
-        return v < 1 ? 1 : (v > 16 ? 16 : v);
-    }();
-    return n_thr;
-}
-
-extern "C++" {
-// A gang of helper threads that lives for one upload: every staging piece (~1 ms of copying) is split over the
-// gang without creating threads per piece (eight std::thread starts cost a quarter of a piece's copy time).
-class Gang {
-public:
-    explicit Gang(int n) : n_(n < 1 ? 1 : n) {
-        for (int t = 1; t < n_; ++t) th_.emplace_back([this, t] { loop(t); });
-    }
-    ~Gang() {
-        stop_.store(true);
-        gen_.fetch_add(1);
-        for (auto& t : th_) t.join();
-    }
-    // body(first, last) over [0, n_items) in n contiguous shares; returns when all shares are done
-    template <class F>
-    void run(size_t n_items, size_t min_per_thread, F body) {
-        if (n_ == 1 || n_items < 2 * min_per_thread) { body((size_t)0, n_items); return; }
-        const size_t part = (n_items + (size_t)n_ - 1) / (size_t)n_;
-        fn_ = [&, part, n_items](int t) { const size_t a = std::min(n_items, (size_t)t * part), b = std::min(n_items, a + part); if (a < b) body(a, b); };
-        done_.store(0);
-        gen_.fetch_add(1);
-        fn_(0);
-        while (done_.load() != n_ - 1) std::this_thread::yield();
-    }
-private:
-    void loop(int t) {
-        uint64_t seen = 0;
-        for (;;) {
-            while (gen_.load() == seen) std::this_thread::yield();
-            seen = gen_.load();
-            if (stop_.load()) return;
-            fn_(t);
-            done_.fetch_add(1);
-        }
-    }
-    int n_;
-    std::vector<std::thread> th_;
-    std::function<void(int)> fn_;
-    std::atomic<uint64_t> gen_{0};
-    std::atomic<int> done_{0};
-    std::atomic<bool> stop_{false};
-};
-}  // extern "C++"
-
-// host memory -> HBM through two pinned staging buffers on the copy stream (asynchronous; the caller syncs)
-int stream_up(mgx_sortdedup_t* c, void* dst, const void* src_, size_t total) {
-    if (!total) return 0;
+    static const int n_thr = [] { const char* e = getenv("MGX_UPLOAD_THREADS"); return std::min(16, std::max(1, e ? atoi(e) : 4)); }();
+    static const bool compact_ok = [] { const char* e = getenv("MGX_SORTDEDUP_WIRE"); return !(e && atoi(e) == 32); }();
+    const bool wire = records && compact_ok;
+    if (!n_items) return 0;
+    const size_t total = n_items * item_bytes;
     int rc = ensure_staging(c, std::min(kPinnedChunk, std::max<size_t>((total + 1) / 2, 1u << 20)));
     if (rc) return rc;
-    size_t off = 0;
+    const size_t piece = c->pinned_cap / item_bytes;
+    mgx_stage::Gang gang(total >= (32u << 20) ? n_thr : 1);
     int buf = 0;
-    Gang gang(total >= (32u << 20) ? upload_threads() : 1);
-    while (off < total) {
-        const size_t len = std::min(c->pinned_cap, total - off);
+    for (size_t off = 0; off < n_items; off += piece, buf ^= 1) {
+        const size_t m = std::min(piece, n_items - off), len = m * item_bytes;
+        const char* src = static_cast<const char*>(src_) + off * item_bytes;
+        char *dst = static_cast<char*>(dst_) + off * item_bytes, *stage = static_cast<char*>(c->pinned[buf]);
         HIP_TRY(hipEventSynchronize(c->pin_ev[buf]));
-        const char* src = reinterpret_cast<const char*>(src_) + off;
-        char* stage = static_cast<char*>(c->pinned[buf]);
-        gang.run(len, 4u << 20, [=](size_t a, size_t b) { memcpy(stage + a, src + a, b - a); });
-        HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(dst) + off, c->pinned[buf], len, hipMemcpyHostToDevice, c->copy));
+        if (wire && !mgx_stage::pack24(gang, reinterpret_cast<const mgx_rec_t*>(src), m, stage)) {
+            HIP_TRY(hipMemcpyAsync(c->d_wire[buf], stage, m * sizeof(Wire24), hipMemcpyHostToDevice, c->copy));
+            hipLaunchKernelGGL(k_expand24, dim3((u32)((m + 255) / 256)), dim3(256), 0, c->copy, (const Wire24*)c->d_wire[buf], (mgx_rec_t*)dst, (u32)m);
+        } else {
+            gang.run(len, 4u << 20, [=](size_t a, size_t b) { memcpy(stage + a, src + a, b - a); });
+            HIP_TRY(hipMemcpyAsync(dst, stage, len, hipMemcpyHostToDevice, c->copy));
+        }
         HIP_TRY(hipEventRecord(c->pin_ev[buf], c->copy));
-        off += len; buf ^= 1;
     }
     return 0;
 }
 
-// records -> d_recs[first ...): 24-byte wire form whenever the piece allows it (MGX_SORTDEDUP_WIRE=32 keeps the raw form)
-int stream_up_recs(mgx_sortdedup_t* c, uint64_t first, uint64_t n, const mgx_rec_t* recs) {
-    if (!n) return 0;
-    static const bool compact_ok = [] { const char* e = getenv("MGX_SORTDEDUP_WIRE"); return !(e && atoi(e) == 32); }();
-    const size_t total = (size_t)n * sizeof(mgx_rec_t);
-    int rc = ensure_staging(c, std::min(kPinnedChunk, std::max<size_t>((total + 1) / 2, 1u << 20)));
-    if (rc) return rc;
-    const size_t piece = c->pinned_cap / sizeof(mgx_rec_t);
-    int buf = 0;
-    Gang gang(total >= (32u << 20) ? upload_threads() : 1);
-    for (uint64_t off = 0; off < n; off += piece, buf ^= 1) {
-        const size_t m = (size_t)std::min<uint64_t>(piece, n - off);
-        HIP_TRY(hipEventSynchronize(c->pin_ev[buf]));
-        const mgx_rec_t* src = recs + off;
-        mgx_rec_t* dst = c->d_recs + first + off;
-        bool compact = compact_ok;
-        if (compact) {
-            // a wire record is the low halves of the two 64-bit fields followed by the record's second 16 bytes as
-            // they are: four 8-byte loads and three 8-byte stores per record, as cheap as the plain copy
-            uint64_t* w = static_cast<uint64_t*>(c->pinned[buf]);
-            const uint64_t* s64 = reinterpret_cast<const uint64_t*>(src);
-            static_assert(sizeof(mgx_rec_t) == 32 && offsetof(mgx_rec_t, prime5) == 8 && offsetof(mgx_rec_t, mate) == 16, "record layout");
-            std::atomic<uint64_t> high{0};
-            gang.run(m, 65536, [&, w, s64](size_t a, size_t b) {
-                uint64_t hi = 0;
-                for (size_t i = a; i < b; ++i) {
-                    const uint64_t c0 = s64[4 * i], p0 = s64[4 * i + 1];
-                    hi |= c0 | p0;
-                    w[3 * i] = (c0 & 0xFFFFFFFFull) | (p0 << 32);
-                    w[3 * i + 1] = s64[4 * i + 2];
-                    w[3 * i + 2] = s64[4 * i + 3];
-                }
-                if (hi >> 32) high.fetch_or(1);
-            });
-            compact = high.load() == 0;
+// ---- the stages of mgx_sortdedup_run, in the order it calls them; DESIGN.md 4.2 has the overview ----
+// The only host round trip of a run: entry counts and key maxima size the sorts.  A maximum >= 2^32 (a coordinate beyond
+// L, a 5' end wrapped below zero) does not fit the packed words: one rebuild, in the wide form of whatever did not fit.
+int build_entries(mgx_sortdedup_t* c) {
+    hipStream_t s = c->compute;
+    const u32 n = c->n, n_order = c->n_order;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        c->stats.n_builds = (uint32_t)attempt + 1;
+        HIP_TRY(hipMemsetAsync(c->d_sc, 0, sizeof(Scalars), s));
+        if (n) {
+            HIP_TRY(hipMemsetAsync(c->d_dup, 0, n, s));
+            BuildOut o{};
+            o.ckey = c->sharded ? nullptr : c->d_ckey[0]; o.cval = c->d_cval[0];      // a shard's order keys come from k_order_keys
+            o.dk1 = c->d_k1[0]; o.dk2 = c->d_k2[0]; o.drec = c->d_prec[0]; o.sk1 = c->d_sk1[0]; o.srec = c->d_srec[0]; o.nk = c->d_nk[0]; o.nrec = c->d_nrec[0];
+            o.indicator = c->indicator.p; o.indicator_bits = c->indicator_bits; o.L = c->L;
+            o.packed_coord = c->packed_coord ? 1 : 0; o.packed_pair = c->packed_pair ? 1 : 0;
+            o.near_enabled = c->packed_pair ? 1 : 0;                                  // the one-word near key holds a 32-bit position
+            o.mate_flag = n < 0x80000000u ? 0x80000000u : 0u; o.half_hist = c->sharded ? nullptr : c->d_half_hist;
+            hipLaunchKernelGGL(k_build_emit, dim3((n + kBuildBlock - 1) / kBuildBlock), dim3(256), 0, s, c->recs.p, n, o, c->d_sc);
+            HIP_TRY(hipGetLastError());
         }
-        if (compact) {
-            HIP_TRY(hipMemcpyAsync(c->d_wire[buf], c->pinned[buf], m * sizeof(Wire24), hipMemcpyHostToDevice, c->copy));
-            hipLaunchKernelGGL(k_expand24, dim3((u32)((m + 255) / 256)), dim3(256), 0, c->copy, (const Wire24*)c->d_wire[buf], dst, (u32)m);
-        } else {
-            char* stage = static_cast<char*>(c->pinned[buf]);
-            const char* s8 = reinterpret_cast<const char*>(src);
-            gang.run(m * sizeof(mgx_rec_t), 4u << 20, [=](size_t a, size_t b) { memcpy(stage + a, s8 + a, b - a); });
-            HIP_TRY(hipMemcpyAsync(dst, c->pinned[buf], m * sizeof(mgx_rec_t), hipMemcpyHostToDevice, c->copy));
-        }
-        HIP_TRY(hipEventRecord(c->pin_ev[buf], c->copy));
+        if (c->sharded && n_order)
+            hipLaunchKernelGGL(k_order_keys, dim3(std::min<u32>((n_order + 255) / 256, (u32)c->n_cu * 16)), dim3(256), 0, s, c->ocoord.p, c->oarr.p,
+                               n_order, c->d_ckey[0], c->d_cval[0], c->packed_coord ? 1 : 0, c->d_sc);
+        // the round trip, inside the timed pipeline: the copy queues behind the kernels on their stream, one wait
+        HIP_TRY(hipMemcpyAsync(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const bool packed_coord = c->packed_coord && c->sc.max_coord < (1ull << 32), packed_pair = c->packed_pair && c->sc.max_k2d < (1ull << 32);
+        if (packed_coord == c->packed_coord && packed_pair == c->packed_pair) break;
+        c->packed_coord = packed_coord; c->packed_pair = packed_pair;
     }
+    if (c->sc.bad_mate) { set_error("a record's mate index is outside the uploaded shard"); return -EINVAL; }
+    c->stats.n_double = (uint64_t)c->sc.n_double + c->sc.n_near; c->stats.n_single = c->sc.n_single;     // sc.n_double: far pairs only
+    c->stats.key_bits_coord = bits_of(c->sc.max_coord);
+    c->stats.key_bits_pair1 = bits_of(std::max<uint64_t>(c->sc.max_k1d, c->sc.max_k1s));
+    c->stats.key_bits_pair2 = bits_of(c->sc.max_k2d);
+    return 0;
+}
+
+// The bitmap's layout for this run.  The atomic layout ORs into its words, so it is cleared here, on the main stream
+// ahead of every pass; the tiled one has no memset: the first pass over it stores every word (`define`).
+int plan_bitmap(mgx_sortdedup_t* c, BitmapPlan* bp) {
+    const uint64_t maxpos = std::max<uint64_t>(c->sc.max_k2d, std::max<uint64_t>(c->sc.max_k1d >> 2, c->sc.max_k1s >> 2));
+    const bool tiled = c->L > 64 && maxpos < c->L - 64;
+    const u64 Lp = tile_aligned(c->L);
+    *bp = BitmapPlan{tiled, Lp, tiled ? Lp : c->L, tiled ? 2 * Lp : c->indicator_bits, (u32)(Lp / kIndTile), (u32)(Lp / kNearSpan)};
+    c->stats.bitmap_tiled = tiled ? 1 : 0;
+    if (!tiled && c->n) HIP_TRY(hipMemsetAsync(c->indicator.p, 0, (size_t)((c->indicator_bits + 64 + 31) / 32) * 4, c->compute));
+    return 0;
+}
+
+// Near double pairs (see kNearShift): one sort of (key word, record) makes equal pairs adjacent, all the run search needs.
+// Records ev_ind once their ends are in the bitmap and ev_side[0] after the marks.  *defined: it stored every bitmap word.
+int near_pass(mgx_sortdedup_t* c, const BitmapPlan& bp, bool multi, bool* defined) {
+    hipStream_t sN = (multi && bp.tiled) ? c->side[0] : c->compute;      // atomic bitmap: behind plan_bitmap's memset
+    const u32 n = c->n, nn = c->sc.n_near;
+    const int near_shift = c->near_by_position ? kNearShift : kNearScoreBits;
+    auto with_ks = [c](auto&& f) {
+        with_bool(c->near_by_position, [&](auto by_pos) { f(std::integral_constant<int, decltype(by_pos)::value ? kNearShift : kNearScoreBits>{}); });
+    };
+    int cur = 0;
+    int rc = radix_sort(c, sN, c->scr[1], c->d_nk, nullptr, c->d_nrec, nn, near_shift, std::max(bits_of(c->sc.max_near) - near_shift, 1), &cur);
+    if (rc) return rc;
+    const u64* key = c->d_nk[cur]; const u32* rec = c->d_nrec[cur];
+    const bool near_tiles = bp.tiled && n && c->packed_pair;
+    u32* sub = near_tiles ? c->sub_start.p : nullptr;
+    // run heads first: the same pass over the sorted keys notes where they cross the bitmap's sub-tile boundaries
+    if (near_tiles && !nn) HIP_TRY(hipMemsetAsync(sub, 0, ((size_t)bp.n_sub + 1) * 4, sN));
+    with_ks([&](auto ks) { launch_find<true, false, decltype(ks)::value>(c, sN, key, nullptr, rec, nn, c->scr[1], &c->d_sc->n_multi_n, bp, sub, bp.n_sub); });
+    if (near_tiles)
+        hipLaunchKernelGGL(k_indicator_tiles_near, dim3(bp.n_ind_tiles), dim3(256), 0, sN, key, nn, c->indicator.p, bp.Lp, sub, bp.n_sub);
+    else if (!bp.tiled && nn)
+        hipLaunchKernelGGL(k_set_indicator_near, dim3((nn + 255) / 256), dim3(256), 0, sN, key, nn, c->indicator.p, c->indicator_bits, c->L);
+    *defined = near_tiles;
+    HIP_TRY(hipEventRecord(c->ev_ind, sN));
+    const u32 rec_mask = n < 0x80000000u ? 0x7FFFFFFFu : 0xFFFFFFFFu;      // bit 31 of an entry's record word: "the mate is rec ^ 1"
+    u32 *n_multi = &c->d_sc->n_multi_n, *n_long = &c->d_sc->n_long_n;
+    with_ks([&](auto ks) { launch_mark<true, false, decltype(ks)::value>(c, sN, key, nullptr, rec, nn, c->scr[1], n_multi, n_long, bp, true, rec_mask); });
+    HIP_TRY(hipEventRecord(c->ev_side[0], sN));
+    return 0;
+}
+
+// Records by unified coordinate (stable: equal coordinates keep arrival order) on side stream 1: order_buf, ev_side[1],
+// and the event range and bytes of "the record-sort scatter kernel" for the statistics.
+int record_sort(mgx_sortdedup_t* c, bool multi) {
+    hipStream_t sR = multi ? c->side[1] : c->compute;
+    const u32 n_order = c->n_order;
+    const u32* half_hist = c->sharded ? nullptr : c->d_half_hist;      // the build kernel's histogram of the first digit
+    const bool pc = c->packed_coord;          // key = coord << 32 | arrival index: sorted on the high half only, 8 bytes per record per pass
+    int cur = 0;
+    bool unpacked = false;                    // did the last pass store the order directly?
+    c->ev_rec_begin = c->ev_used;
+    const uint64_t bytes_before = c->scatter_bytes;
+    const int rc = radix_sort(c, sR, c->scr[2], c->d_ckey, nullptr, pc ? nullptr : c->d_cval, n_order, pc ? 32 : 0, bits_of(c->sc.max_coord), &cur,
+                              pc ? c->d_cval[0] : nullptr, pc ? &unpacked : nullptr, half_hist);
+    if (rc) return rc;
+    if (pc && n_order && !unpacked) hipLaunchKernelGGL(k_unpack_order, dim3((n_order + 255) / 256), dim3(256), 0, sR, c->d_ckey[cur], n_order, c->d_cval[0]);
+    c->order_buf = pc ? 0 : cur;
+    c->ev_rec_end = c->ev_used;
+    c->rec_scatter_bytes = c->scatter_bytes - bytes_before;
+    if (unpacked && c->ev_rec_end >= c->ev_rec_begin + 2) {
+        // the statistics cover the full-width launches only; the last one is a different instantiation (half the store bytes)
+        c->ev_rec_end -= 2;
+        c->rec_scatter_bytes -= (uint64_t)n_order * 12;
+    }
+    HIP_TRY(hipEventRecord(c->ev_side[1], sR));
+    return 0;
+}
+
+// Far double pairs (discordant, cross-contig, or all when keys are wider than 32 bits), main stream: LSD by the mate end,
+// then by sort_key.  Packed: sort_key and (mate end << 32 | record) take turns as key and payload, 16 B per entry per pass.
+int far_pass(mgx_sortdedup_t* c, const BitmapPlan& bp, bool defined) {
+    hipStream_t s = c->compute;
+    const u32 n = c->n, nd = c->sc.n_double;
+    const bool pk = c->packed_pair;
+    u32** prec = pk ? nullptr : c->d_prec;
+    int cur = 0, rc;
+    if ((rc = radix_sort(c, s, c->scr[0], c->d_k2, c->d_k1, prec, nd, pk ? 32 : 0, bits_of(c->sc.max_k2d), &cur))) return rc;
+    HIP_TRY(hipStreamWaitEvent(s, c->ev_ind, 0));      // the near pass writes the bitmap's words first
+    // tiled: record 2's pass defines the words the near pass has not, and for that runs even without far pairs
+    if (bp.tiled ? (n && (nd || !defined)) : nd != 0) launch_indicator<2>(c, s, c->d_k1[cur], c->d_k2[cur], nd, bp, !defined);
+    if (n && c->n_marks)      // ends of pairs that live in other shards
+        hipLaunchKernelGGL(k_or_marks, dim3((c->n_marks + 255) / 256), dim3(256), 0, s, c->marks.p, c->n_marks, c->indicator.p, bp.ind_bits, bp.ind_off,
+                           bp.tiled ? c->L - 64 : ~0ull);
+    if ((rc = radix_sort(c, s, c->scr[0], c->d_k1, c->d_k2, prec, nd, 0, bits_of(c->sc.max_k1d), &cur))) return rc;
+    if (!nd) return 0;
+    launch_indicator<1>(c, s, c->d_k1[cur], c->d_k2[cur], nd, bp);
+    with_bool(pk, [&](auto packed) {
+        constexpr bool PK = decltype(packed)::value;
+        launch_mark<true, PK>(c, s, c->d_k1[cur], c->d_k2[cur], PK ? nullptr : c->d_prec[cur], nd, c->scr[0], &c->d_sc->n_multi_d, &c->d_sc->n_long_d, bp);
+    });
+    return 0;
+}
+
+// Single reads, on the main stream after far_pass: they test the bitmap every pair end is in by now.
+int single_pass(mgx_sortdedup_t* c, const BitmapPlan& bp) {
+    const u32 ns = c->sc.n_single;
+    int cur = 0;
+    const int rc = radix_sort(c, c->compute, c->scr[0], c->d_sk1, nullptr, c->d_srec, ns, 0, bits_of(c->sc.max_k1s), &cur);
+    if (!rc) launch_mark<false, false>(c, c->compute, c->d_sk1[cur], nullptr, c->d_srec[cur], ns, c->scr[0], &c->d_sc->n_multi_s, &c->d_sc->n_long_s, bp);
+    return rc;
+}
+
+// Waits for the pipeline, fetches the scalars and applies the one fallback that can only be decided afterwards: a position with
+// more near pairs than the in-run comparison accepts sends the input through the pipeline again with the six-pass near sort.
+int finish_run(mgx_sortdedup_t* c) {
+    while (!c->finished) {
+        HIP_TRY(hipStreamSynchronize(c->compute));
+        HIP_TRY(hipMemcpy(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost));
+        c->finished = !(c->sc.huge_runs && c->near_by_position);
+        if (c->finished) break;
+        c->near_by_position = false;
+        const int rc = mgx_sortdedup_run(c);      // leaves finished == false: the scalars are read once more
+        if (rc) return rc;
+        c->stats.n_pipeline_runs = 2;
+    }
+    return 0;
+}
+
+// total time (and, if asked for, number) of the scatter launches timed by the event pairs [begin, end) of ev_scatter
+int sum_event_pairs(const mgx_sortdedup_t* c, size_t begin, size_t end, float* ms_sum, uint32_t* count = nullptr) {
+    *ms_sum = 0;
+    for (size_t k = begin; k + 1 < end; k += 2) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_scatter[k], c->ev_scatter[k + 1]));
+        *ms_sum += ms;
+    }
+    if (count) *count = (uint32_t)((end - begin) / 2);
     return 0;
 }
 
 }  // namespace
+
+extern "C" {
 
 int mgx_sortdedup_upload_begin(mgx_sortdedup_t* c, uint64_t L, uint64_t n_expected) {
     if (!c) { set_error("ctx is NULL"); return -EINVAL; }
@@ -1530,7 +1612,7 @@ int mgx_sortdedup_upload_chunk(mgx_sortdedup_t* c, uint64_t first_record, uint64
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_recs(c, (size_t)(first_record + n_records), (size_t)c->up_high);
     if (rc) return rc;
-    if ((rc = stream_up_recs(c, first_record, n_records, recs))) return rc;
+    if ((rc = staged_upload(c, c->recs.p + first_record, recs, (size_t)n_records, sizeof(mgx_rec_t), true))) return rc;
     c->up_high = std::max(c->up_high, first_record + n_records);
     return 0;
 }
@@ -1564,201 +1646,49 @@ int mgx_sortdedup_upload_shard(mgx_sortdedup_t* c, uint64_t L, const mgx_sortded
     c->uploading = false;
     int rc = ensure_recs(c, (size_t)sh->n_mark, 0);
     if (!rc) rc = prepare_input(c, L, (size_t)std::max(sh->n_order, sh->n_mark));
+    if (!rc) rc = c->ocoord.grow((size_t)sh->n_order);
+    if (!rc) rc = c->oarr.grow((size_t)sh->n_order);
+    if (!rc) rc = c->marks.grow((size_t)sh->n_marks);
     if (rc) return rc;
-    if (sh->n_order > c->order_cap) {
-        (void)hipFree(c->d_ocoord); (void)hipFree(c->d_oarr); c->d_ocoord = nullptr; c->d_oarr = nullptr; c->order_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_ocoord, sh->n_order * 8)); HIP_TRY(hipMalloc((void**)&c->d_oarr, sh->n_order * 4));
-        c->order_cap = sh->n_order;
-    }
-    if (sh->n_marks > c->marks_cap) {
-        (void)hipFree(c->d_marks); c->d_marks = nullptr; c->marks_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_marks, sh->n_marks * 8));
-        c->marks_cap = sh->n_marks;
-    }
     c->n = (u32)sh->n_mark; c->n_order = (u32)sh->n_order; c->n_marks = (u32)sh->n_marks; c->sharded = true;
-    if ((rc = stream_up_recs(c, 0, sh->n_mark, sh->mark_recs))) return rc;
-    if ((rc = stream_up(c, c->d_ocoord, sh->order_coord, (size_t)sh->n_order * 8))) return rc;
-    if ((rc = stream_up(c, c->d_oarr, sh->order_arrival, (size_t)sh->n_order * 4))) return rc;
-    if ((rc = stream_up(c, c->d_marks, sh->marks, (size_t)sh->n_marks * 8))) return rc;
+    if ((rc = staged_upload(c, c->recs.p, sh->mark_recs, (size_t)sh->n_mark, sizeof(mgx_rec_t), true))) return rc;
+    if ((rc = staged_upload(c, c->ocoord.p, sh->order_coord, (size_t)sh->n_order * 8, 1))) return rc;      // plain bytes
+    if ((rc = staged_upload(c, c->oarr.p, sh->order_arrival, (size_t)sh->n_order * 4, 1))) return rc;
+    if ((rc = staged_upload(c, c->marks.p, sh->marks, (size_t)sh->n_marks * 8, 1))) return rc;
     HIP_TRY(hipStreamSynchronize(c->copy));
     return 0;
 }
 
+// The three sorts are independent: near pairs on side stream 0, records on side stream 1, far pairs and singles on the
+// main stream, so their short histogram / scan launches overlap the other sorts' bandwidth-bound scatters: 18.0 ms against
+// 19.4 ms on a single stream (MGX_SORTDEDUP_STREAMS=1) at 200 M records, in-process A/B (tools/dev_sort_ab.py).
 int mgx_sortdedup_run(mgx_sortdedup_t* c) {
     if (!c) { set_error("ctx is NULL"); return -EINVAL; }
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->compute;
-    const u32 n = c->n, n_order = c->n_order;
-    c->stats = mgx_sortdedup_stats_t{};
-    c->stats.n_records = n_order;
-    c->ev_used = 0; c->scatter_bytes = 0;
-    HIP_TRY(hipEventRecord(c->ev_start, s));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        c->stats.n_builds = (uint32_t)attempt + 1;
-        HIP_TRY(hipMemsetAsync(c->d_sc, 0, sizeof(Scalars), s));
-        if (n) {
-            HIP_TRY(hipMemsetAsync(c->d_dup, 0, n, s));
-            const u32 nb = (n + kBuildBlock - 1) / kBuildBlock;
-            BuildOut o{c->sharded ? nullptr : c->d_ckey[0], c->d_cval[0], c->d_k1[0], c->d_k2[0], c->d_prec[0], c->d_sk1[0], c->d_srec[0],
-                       c->d_indicator, c->indicator_bits, c->L, c->packed_coord ? 1 : 0, c->packed_pair ? 1 : 0,
-                       c->d_nk[0], c->d_nrec[0], c->packed_pair ? 1 : 0, n < 0x80000000u ? 0x80000000u : 0u,
-                       c->sharded ? nullptr : c->d_half_hist};
-            hipLaunchKernelGGL(k_build_emit, dim3(nb), dim3(256), 0, s, c->d_recs, n, o, c->d_sc);
-            HIP_TRY(hipGetLastError());
-        }
-        if (c->sharded && n_order)
-            hipLaunchKernelGGL(k_order_keys, dim3(std::min<u32>((n_order + 255) / 256, (u32)c->n_cu * 16)), dim3(256), 0, s, c->d_ocoord, c->d_oarr,
-                               n_order, c->d_ckey[0], c->d_cval[0], c->packed_coord ? 1 : 0, c->d_sc);
-        // the only host round trip: entry counts and key maxima size the sorts
-        HIP_TRY(hipMemcpyAsync(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        // a coordinate beyond L (a position past the end of its contig) does not fit the packed
-        // (coord << 32 | index) key: rebuild once with separate key/value arrays
-        if ((c->packed_coord && c->sc.max_coord >= (1ull << 32)) || (c->packed_pair && c->sc.max_k2d >= (1ull << 32))) {
-            if (c->sc.max_coord >= (1ull << 32)) c->packed_coord = false;
-            if (c->sc.max_k2d >= (1ull << 32)) c->packed_pair = false;
-            continue;
-        }
-        break;
-    }
-    if (c->sc.bad_mate) { set_error("a record's mate index is outside the uploaded shard"); return -EINVAL; }
-    const u32 nd = c->sc.n_double, ns = c->sc.n_single, nn = c->sc.n_near;   // nd: far pairs only
-    c->stats.n_double = (uint64_t)nd + nn; c->stats.n_single = ns;
-    c->stats.key_bits_coord = bits_of(c->sc.max_coord);
-    c->stats.key_bits_pair1 = bits_of(std::max<uint64_t>(c->sc.max_k1d, c->sc.max_k1s));
-    c->stats.key_bits_pair2 = bits_of(c->sc.max_k2d);
-    int rc;
-    // indicator bitmap: tiled (plain stores, reverse half at a tile-aligned offset) whenever every 5' end
-    // is safely below L; otherwise the reference's exact layout with global atomics
-    const uint64_t maxpos = std::max<uint64_t>(c->sc.max_k2d, std::max<uint64_t>(c->sc.max_k1d >> 2, c->sc.max_k1s >> 2));
-    const bool tiled = c->L > 64 && maxpos < c->L - 64;
-    c->stats.bitmap_tiled = tiled ? 1 : 0;
-    c->stats.n_pipeline_runs = 1;
-    const uint64_t Lp = (c->L + kIndTile - 1) / kIndTile * kIndTile;
-    const uint64_t ind_off = tiled ? Lp : c->L;                 // offset of the reverse-strand half
-    const uint64_t ind_bits = tiled ? 2 * Lp : c->indicator_bits;
-    const u32 n_ind_tiles = (u32)((c->L + kIndTile - 1) / kIndTile);
-    if (!tiled && n) HIP_TRY(hipMemsetAsync(c->d_indicator, 0, (size_t)((c->indicator_bits + 64 + 31) / 32) * 4, s));
-
-    // near double pairs (mate 5' end within 65 535 of record 1's -- every proper pair): the whole
-    // (sort_key, mate end) identity is ONE injective key word p1 << 16 | orient << 14 | delta, so one
-    // LSD sort of (8-byte key, 4-byte record) groups equal pairs: 7 passes x 12 B instead of 9 x 16 B.
-    // Runs only need equal keys to be adjacent, not the reference's exact order.
-    // The three sorts are independent: near pairs go to side stream 0, records to side stream 1, far
-    // pairs and singles stay on the main stream, so their short histogram / scan launches overlap the
-    // other sorts' bandwidth-bound scatters.  In-process A/B on one device at 200 M records
-    // (tools/dev_sort_ab.py): 18.0 ms against 19.4 ms on a single stream (MGX_SORTDEDUP_STREAMS=1).
+    // both switches are read on every run: tests and the benchmark flip them between runs of one process
     if (const char* e = getenv("MGX_SORTDEDUP_NEAR_EXACT")) { if (atoi(e) != 0) c->near_by_position = false; }
     const char* env_streams = getenv("MGX_SORTDEDUP_STREAMS");
     const bool multi = !(env_streams && atoi(env_streams) == 1);
-    hipStream_t sN = (multi && tiled) ? c->side[0] : s;   // the atomic (non-tiled) bitmap needs the memset first
-    hipStream_t sR = multi ? c->side[1] : s;
-    int ncur = 0;
-    const int near_shift = c->near_by_position ? kNearShift : kNearScoreBits;
-    if ((rc = radix_sort(c, sN, c->scr[1], c->d_nk, nullptr, c->d_nrec, nn, near_shift,
-                         std::max(bits_of(c->sc.max_near) - near_shift, 1), &ncur))) return rc;
+    c->stats = mgx_sortdedup_stats_t{};
+    c->stats.n_records = c->n_order; c->stats.n_pipeline_runs = 1;
+    c->ev_used = 0; c->scatter_bytes = 0;
+    HIP_TRY(hipEventRecord(c->ev_start, c->compute));
+    BitmapPlan bp;
     bool defined = false;                     // has a pass already written every word of the tiled bitmap?
-    const bool near_tiles = tiled && n && c->packed_pair;
-    const u32 n_sub = (u32)(Lp / kNearSpan);
-    // run heads first: the same pass over the sorted keys notes where they cross the bitmap's sub-tile boundaries
-    if (near_tiles && !nn) HIP_TRY(hipMemsetAsync(c->d_sub_start, 0, ((size_t)n_sub + 1) * 4, sN));
-    with_bool(c->near_by_position, [&](auto by_pos) {
-        constexpr int KS = decltype(by_pos)::value ? kNearShift : kNearScoreBits;
-        launch_find<true, false, KS>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, ind_bits, ind_off,
-                                     near_tiles ? c->d_sub_start : nullptr, n_sub);
-    });
-    if (near_tiles) {
-        hipLaunchKernelGGL(k_indicator_tiles_near, dim3(n_ind_tiles), dim3(256), 0, sN, c->d_nk[ncur], nn, c->d_indicator, Lp, c->d_sub_start, n_sub);
-        defined = true;
-    } else if (!tiled && nn) {
-        hipLaunchKernelGGL(k_set_indicator_near, dim3((nn + 255) / 256), dim3(256), 0, sN, c->d_nk[ncur], nn, c->d_indicator, c->indicator_bits, c->L);
-    }
-    HIP_TRY(hipEventRecord(c->ev_ind, sN));
-    const u32 near_rec_mask = n < 0x80000000u ? 0x7FFFFFFFu : 0xFFFFFFFFu;
-    with_bool(c->near_by_position, [&](auto by_pos) {
-        constexpr int KS = decltype(by_pos)::value ? kNearShift : kNearScoreBits;
-        launch_mark<true, false, KS>(c, sN, c->d_nk[ncur], nullptr, c->d_nrec[ncur], nn, c->scr[1], &c->d_sc->n_multi_n, &c->d_sc->n_long_n, ind_bits, ind_off, true, near_rec_mask);
-    });
-    HIP_TRY(hipEventRecord(c->ev_side[0], sN));
-
-    // records by unified coordinate (stable: equal coordinates keep arrival order)
-    int ccur = 0;
-    bool unpacked = false;                    // did the last pass store the order directly?
-    c->ev_rec_begin = c->ev_used;
-    const uint64_t bytes_before_records = c->scatter_bytes;
-    if (c->packed_coord) {
-        // key = coord << 32 | arrival index: sort on the high half only, 8 bytes per record per pass
-        if ((rc = radix_sort(c, sR, c->scr[2], c->d_ckey, nullptr, nullptr, n_order, 32, bits_of(c->sc.max_coord), &ccur, c->d_cval[0], &unpacked,
-                             c->sharded ? nullptr : c->d_half_hist))) return rc;
-        if (n_order && !unpacked) hipLaunchKernelGGL(k_unpack_order, dim3((n_order + 255) / 256), dim3(256), 0, sR, c->d_ckey[ccur], n_order, c->d_cval[0]);
-        ccur = 0;
-    } else {
-        if ((rc = radix_sort(c, sR, c->scr[2], c->d_ckey, nullptr, c->d_cval, n_order, 0, bits_of(c->sc.max_coord), &ccur, nullptr, nullptr,
-                             c->sharded ? nullptr : c->d_half_hist))) return rc;
-    }
-    c->order_buf = ccur;
-    c->ev_rec_end = c->ev_used;
-    c->rec_scatter_bytes = c->scatter_bytes - bytes_before_records;
-    if (unpacked && c->ev_rec_end >= c->ev_rec_begin + 2) {
-        // the statistics of "the record-sort scatter kernel" cover the full-width launches only; the
-        // last one is a different instantiation (half the store bytes)
-        c->ev_rec_end -= 2;
-        c->rec_scatter_bytes -= (uint64_t)n_order * 12;
-    }
-    HIP_TRY(hipEventRecord(c->ev_side[1], sR));
-
-    // far double pairs (discordant, cross-contig, or every pair when keys are wider than 32 bits):
-    // LSD over (sort_key, mate 5' end): sort by the mate end first, then by sort_key.
-    // Packed form: two 8-byte arrays per entry -- sort_key and (mate end << 32 | record) -- take
-    // turns as key and payload (16 B per entry per pass, two LDS exchange rounds instead of three).
-    int cur = 0;
-    const bool pk = c->packed_pair;
-    if ((rc = radix_sort(c, s, c->scr[0], c->d_k2, c->d_k1, pk ? nullptr : c->d_prec, nd, pk ? 32 : 0, bits_of(c->sc.max_k2d), &cur))) return rc;
-    HIP_TRY(hipStreamWaitEvent(s, c->ev_ind, 0));      // the near pass defines the bitmap's words first
-    // tiled: also without far pairs, when no pass has defined the bitmap's words yet
-    if (tiled ? (n && (nd || !defined)) : nd != 0)
-        launch_indicator<2>(c, s, c->d_k1[cur], c->d_k2[cur], nd, tiled, Lp, n_ind_tiles, !defined);
-    if (n && c->n_marks)      // ends of pairs that live in other shards
-        hipLaunchKernelGGL(k_or_marks, dim3((c->n_marks + 255) / 256), dim3(256), 0, s, c->d_marks, c->n_marks, c->d_indicator, ind_bits, ind_off,
-                           tiled ? c->L - 64 : ~0ull);
-    if ((rc = radix_sort(c, s, c->scr[0], c->d_k1, c->d_k2, pk ? nullptr : c->d_prec, nd, 0, bits_of(c->sc.max_k1d), &cur))) return rc;
-    if (nd) {
-        launch_indicator<1>(c, s, c->d_k1[cur], c->d_k2[cur], nd, tiled, Lp, n_ind_tiles);
-        with_bool(pk, [&](auto packed) {
-            constexpr bool PK = decltype(packed)::value;
-            launch_mark<true, PK>(c, s, c->d_k1[cur], c->d_k2[cur], PK ? nullptr : c->d_prec[cur], nd, c->scr[0], &c->d_sc->n_multi_d, &c->d_sc->n_long_d, ind_bits, ind_off);
-        });
-    }
-    // singles
-    int scur = 0;
-    if ((rc = radix_sort(c, s, c->scr[0], c->d_sk1, nullptr, c->d_srec, ns, 0, bits_of(c->sc.max_k1s), &scur))) return rc;
-    launch_mark<false, false>(c, s, c->d_sk1[scur], nullptr, c->d_srec[scur], ns, c->scr[0], &c->d_sc->n_multi_s, &c->d_sc->n_long_s, ind_bits, ind_off);
-    HIP_TRY(hipStreamWaitEvent(s, c->ev_side[0], 0));
-    HIP_TRY(hipStreamWaitEvent(s, c->ev_side[1], 0));
-    if (n) hipLaunchKernelGGL(k_count_dup, dim3(c->n_cu * 4), dim3(256), 0, s, c->d_dup, n, c->d_sc);
-    HIP_TRY(hipEventRecord(c->ev_stop, s));
+    int rc = build_entries(c);
+    if (!rc) rc = plan_bitmap(c, &bp);
+    if (!rc) rc = near_pass(c, bp, multi, &defined);
+    if (!rc) rc = record_sort(c, multi);
+    if (!rc) rc = far_pass(c, bp, defined);
+    if (!rc) rc = single_pass(c, bp);
+    if (rc) return rc;
+    // the join: the duplicate count needs the marks of all three chains
+    HIP_TRY(hipStreamWaitEvent(c->compute, c->ev_side[0], 0));
+    HIP_TRY(hipStreamWaitEvent(c->compute, c->ev_side[1], 0));
+    if (c->n) hipLaunchKernelGGL(k_count_dup, dim3(c->n_cu * 4), dim3(256), 0, c->compute, c->d_dup, c->n, c->d_sc);
+    HIP_TRY(hipEventRecord(c->ev_stop, c->compute));
     HIP_TRY(hipGetLastError());
-    c->ran = true;
-    c->finished = false;
-    return 0;
-}
-
-// Waits for the pipeline and applies the one fallback that can only be decided afterwards: a position
-// holding more near pairs than the in-run comparison accepts sends the input through the pipeline again
-// with the six-pass near sort (equal identities adjacent, no quadratic step).
-static int finish_run(mgx_sortdedup_t* c) {
-    if (c->finished) return 0;
-    HIP_TRY(hipStreamSynchronize(c->compute));
-    HIP_TRY(hipMemcpy(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost));
-    if (c->sc.huge_runs && c->near_by_position) {
-        c->near_by_position = false;
-        const int rc = mgx_sortdedup_run(c);
-        if (rc) return rc;
-        c->stats.n_pipeline_runs = 2;
-        HIP_TRY(hipStreamSynchronize(c->compute));
-        HIP_TRY(hipMemcpy(&c->sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost));
-    }
-    c->finished = true;
+    c->ran = true; c->finished = false;
     return 0;
 }
 
@@ -1767,9 +1697,7 @@ int mgx_sortdedup_results(mgx_sortdedup_t* c, uint32_t* out_order, uint8_t* out_
     if (!c->ran) { set_error("mgx_sortdedup_run has not been called"); return -EINVAL; }
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = finish_run(c); if (rc) return rc; }
-    if (c->n) {
-        if (out_dup) HIP_TRY(hipMemcpyAsync(out_dup, c->d_dup, (size_t)c->n, hipMemcpyDeviceToHost, c->compute));
-    }
+    if (c->n && out_dup) HIP_TRY(hipMemcpyAsync(out_dup, c->d_dup, (size_t)c->n, hipMemcpyDeviceToHost, c->compute));
     if (c->n_order && out_order) HIP_TRY(hipMemcpyAsync(out_order, c->d_cval[c->order_buf], (size_t)c->n_order * 4, hipMemcpyDeviceToHost, c->compute));
     HIP_TRY(hipStreamSynchronize(c->compute));
     return 0;
@@ -1779,7 +1707,8 @@ int mgx_sortdedup_stats(mgx_sortdedup_t* c, mgx_sortdedup_stats_t* out) {
     if (!c || !out) { set_error("NULL argument"); return -EINVAL; }
     if (!c->ran) { set_error("mgx_sortdedup_run has not been called"); return -EINVAL; }
     HIP_TRY(hipSetDevice(c->device));
-    { const int rc = finish_run(c); if (rc) return rc; }
+    int rc = finish_run(c);
+    if (rc) return rc;
     mgx_sortdedup_stats_t st = c->stats;
     st.n_dup_records = c->sc.n_dup;
     st.n_near = c->sc.n_near;
@@ -1788,19 +1717,10 @@ int mgx_sortdedup_stats(mgx_sortdedup_t* c, mgx_sortdedup_stats_t* out) {
     st.packed_coord = c->packed_coord ? 1 : 0; st.packed_pair = c->packed_pair ? 1 : 0;
     st.near_by_position = c->near_by_position ? 1 : 0;
     HIP_TRY(hipEventElapsedTime(&st.ms_total, c->ev_start, c->ev_stop));
-    st.ms_radix_scatter = 0;
-    for (size_t k = 0; k + 1 < c->ev_used + 1 && k + 1 < c->ev_scatter.size() + 1 && k < c->ev_used; k += 2) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_scatter[k], c->ev_scatter[k + 1]));
-        st.ms_radix_scatter += ms;
-    }
+    if ((rc = sum_event_pairs(c, 0, c->ev_used, &st.ms_radix_scatter))) return rc;
+    if ((rc = sum_event_pairs(c, c->ev_rec_begin, c->ev_rec_end, &st.ms_scatter_records, &st.n_scatter_records))) return rc;
     st.radix_scatter_bytes = c->scatter_bytes;
-    st.ms_scatter_records = 0; st.n_scatter_records = 0; st.scatter_records_bytes = c->rec_scatter_bytes;
-    for (size_t k = c->ev_rec_begin; k + 1 < c->ev_rec_end + 1 && k < c->ev_rec_end; k += 2) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_scatter[k], c->ev_scatter[k + 1]));
-        st.ms_scatter_records += ms; st.n_scatter_records++;
-    }
+    st.scatter_records_bytes = c->rec_scatter_bytes;
     // LSD-8 traffic model, SURVEY.md section 8d
     const uint64_t N = c->n_order, P = (uint64_t)st.n_double + st.n_single;
     const uint64_t pc = (st.key_bits_coord + 7) / 8, pp = (st.key_bits_pair1 + st.key_bits_pair2 + 7) / 8;

@@ -1,16 +1,21 @@
 // tests/cpp/test_host_sanitize.cpp -- the host-only pieces of the library (record packing, the multi-GPU router and
-// merge, the PairHMM batch packer) driven over seeded random inputs; built by tests/test_host_sanitizers.py with
-// -fsanitize=address,undefined and with -fsanitize=thread (no HIP, no device).  Exit code 0 = nothing reported.
+// merge, the PairHMM batch packer, the upload path's thread gang and wire packing) driven over seeded random inputs;
+// built by tests/test_host_sanitizers.py with -fsanitize=address,undefined and with -fsanitize=thread (no HIP, no
+// device).  Exit code 0 = nothing reported.
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "mgx_pairhmm.h"
 #include "mgx_sortdedup.h"
 #include "../../fast-genomic-data-processing_amd/csrc/pairhmm_pack.h"
+#include "../../fast-genomic-data-processing_amd/csrc/sortdedup_stage.h"
 #include "../../fast-genomic-data-processing_amd/csrc/cli/sam_text.h"
 
 static uint64_t rng_state = 0x5EED;
@@ -194,8 +199,77 @@ static int sam_case() {
     return 0;
 }
 
+// Gang::run of the upload path: every index of [0, n) is visited exactly once per call (a plain counter per index: a
+// second visit from another thread is also a ThreadSanitizer report), at most one share per thread, the caller alone
+// below twice the minimum share; many calls on one gang, then its destruction; a gang that never runs anything.
+static int gang_case() {
+    { mgx_stage::Gang idle(4); }
+    const size_t min_share = 8;
+    for (int n_thr : {1, 2, 4, 16}) {
+        mgx_stage::Gang gang(n_thr);
+        struct Case { size_t n, min; bool alone; };
+        const Case cases[] = {{0, min_share, true}, {1, min_share, true}, {2 * min_share - 1, min_share, true}, {2 * min_share, min_share, n_thr == 1},
+                              {1003, min_share, n_thr == 1}, {(size_t)n_thr - 1, 1, n_thr <= 2}, {3, 1, n_thr == 1}, {0, 0, n_thr == 1}};
+        for (int it = 0; it < 300; ++it) {
+            const Case& k = it < 8 ? cases[it] : cases[4 + it % 3];
+            std::vector<uint32_t> hits(k.n, 0);
+            std::atomic<int> calls{0}, foreign{0};
+            const std::thread::id me = std::this_thread::get_id();
+            gang.run(k.n, k.min, [&](size_t a, size_t b) {
+                calls.fetch_add(1);
+                if (std::this_thread::get_id() != me) foreign.fetch_add(1);
+                for (size_t i = a; i < b; ++i) hits[i]++;
+            });
+            for (size_t i = 0; i < k.n; ++i) if (hits[i] != 1) { fprintf(stderr, "gang_case: %d threads, %zu items: index %zu visited %u times\n", n_thr, k.n, i, hits[i]); return 40; }
+            if (calls.load() > n_thr || (k.alone && (calls.load() != 1 || foreign.load() != 0))) { fprintf(stderr, "gang_case: %d threads, %zu items (min %zu): %d calls, %d off the caller\n", n_thr, k.n, k.min, calls.load(), foreign.load()); return 41; }
+            if (!k.alone && k.n >= (size_t)n_thr && calls.load() < 2) { fprintf(stderr, "gang_case: %d threads, %zu items (min %zu) were not split\n", n_thr, k.n, k.min); return 42; }
+        }
+    }
+    return 0;
+}
+
+// The 24-byte wire packing against a per-field restatement, and its "some value needs more than 32 bits" verdict: true
+// exactly when a coord or a prime5 is >= 2^32, wherever in the range (and in whichever thread's share) that value sits.
+static int pack24_case(int n_thr) {
+    struct Wire { uint32_t coord, prime5, mate; uint16_t flag, score, tile, x, y, pad_; };
+    static_assert(sizeof(Wire) == 24, "wire record");
+    const size_t m = 4 * 65536 + 3;           // pack24 gives a thread no less than 65 536 records: four full shares
+    const size_t part = (m + (size_t)n_thr - 1) / (size_t)n_thr;
+    std::vector<mgx_rec_t> recs(m);
+    for (auto& r : recs) {
+        r.coord = rnd() & 0xFFFFFFFFull; r.prime5 = rnd() & 0xFFFFFFFFull; r.mate = (uint32_t)rnd(); r.flag = (uint16_t)rnd(); r.score = (uint16_t)rnd();
+        r.tile = (uint16_t)rnd(); r.x = (uint16_t)rnd(); r.y = (uint16_t)rnd(); r.pad_ = 0;
+    }
+    recs[7].coord = recs[m - 9].prime5 = 0xFFFFFFFFull;              // the largest values that still fit
+    std::vector<Wire> wire(m);
+    mgx_stage::Gang gang(n_thr);
+    if (mgx_stage::pack24(gang, recs.data(), m, wire.data())) return 50;
+    for (size_t i = 0; i < m; ++i) {
+        const mgx_rec_t& r = recs[i]; const Wire& w = wire[i];
+        if (w.coord != r.coord || w.prime5 != r.prime5 || w.mate != r.mate || w.flag != r.flag || w.score != r.score || w.tile != r.tile || w.x != r.x || w.y != r.y || w.pad_ != 0) {
+            fprintf(stderr, "pack24_case: record %zu differs (%d threads)\n", i, n_thr); return 51;
+        }
+    }
+    // index 0 and m - 1 of the range, the first and the last index of a share (of every share when there are several)
+    std::vector<size_t> at = {0, m - 1, part - 1, std::min(part, m - 1), std::min(2 * part - 1, m - 1), (n_thr - 1) * part <= m - 1 ? (n_thr - 1) * part : m - 1};
+    for (size_t i : at)
+        for (int field = 0; field < 2; ++field)
+            for (uint64_t big : {1ull << 32, ~0ull - 4}) {
+                uint64_t& v = field ? recs[i].prime5 : recs[i].coord;
+                const uint64_t keep = v;
+                v = big;
+                const bool high = mgx_stage::pack24(gang, recs.data(), m, wire.data());
+                v = keep;
+                if (!high) { fprintf(stderr, "pack24_case: %s >= 2^32 at record %zu not reported (%d threads)\n", field ? "prime5" : "coord", i, n_thr); return 52; }
+            }
+    return mgx_stage::pack24(gang, recs.data(), m, wire.data()) ? 53 : 0;
+}
+
 int main() {
-    int rc = sam_case();
+    int rc = gang_case();
+    if (!rc) rc = pack24_case(1);
+    if (!rc) rc = pack24_case(4);
+    if (!rc) rc = sam_case();
     for (int it = 0; it < 40 && !rc; ++it) rc = route_case(1 + rnd() % 30000, 1 + (uint32_t)(rnd() % 9), 1000 + rnd() % 5000000);
     if (!rc) rc = route_case(400000, 8, 3100000000ull);         // large enough for the router's threads to split the work
     for (int it = 0; it < 20 && !rc; ++it) rc = pack_case(1 + rnd() % 200, 1 + rnd() % 50, rnd() % 3000, it % 3 == 0);

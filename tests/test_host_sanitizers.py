@@ -1,6 +1,7 @@
 """The host-only code of the library (record packing, the multi-GPU router / merge, the PairHMM batch packer and
-its callers' validation) and the CLI's SAM text parser under AddressSanitizer + UBSan and under ThreadSanitizer, CPU build, no device: the
-translation units are compiled directly with g++ (they contain no HIP) next to a small driver."""
+its callers' validation, the sort/mark-duplicate upload's thread gang and 24-byte wire packing) and the CLI's SAM
+text parser under AddressSanitizer + UBSan and under ThreadSanitizer, CPU build, no device: the translation units
+are compiled directly with g++ (they contain no HIP) next to a small driver."""
 import os
 import shutil
 import subprocess

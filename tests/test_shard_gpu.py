@@ -30,6 +30,36 @@ def test_small_cases_vs_oracle(pkg, sd_engine, sd_oracle, synth, k_shards):
         assert np.array_equal(dup, want_dup)
 
 
+def plain_upload_case(synth):
+    """530 000 records over two shards, most of them unmapped reads (ordered, never marked): each shard orders a little
+    more than 262 144 records but marks few, so its record upload leaves a new engine's staging buffers small and its
+    coordinates (8 bytes each, 2 MiB and a little) and arrival indices travel as plain bytes in several pieces."""
+    recs, L = synth.gen_sortdedup_packed(60_000, 41, n_contigs=3, contig_len=1_000_000)
+    fill = np.zeros(470_000, dtype=synth.REC_DTYPE)
+    fill["coord"] = np.random.RandomState(42).randint(0, L, len(fill)).astype(np.uint64); fill["prime5"] = fill["coord"]
+    fill["flag"] = 1 | 4 | 64; fill["mate"] = synth.NO_MATE
+    return np.concatenate([recs, fill]), L
+
+
+def test_plain_upload_on_the_seams_of_the_staging_buffers(pkg, sd_oracle, synth):
+    """The ordering half of a shard through the staging loop's plain-byte form in more than one piece: with buffers of
+    half the coordinates' size these make two full pieces and the arrival indices, half as many bytes, fill one buffer
+    exactly; every transfer starts on buffer 0 again.  The buffers always grow to half a transfer, so below 128 MiB plain
+    bytes never make a third piece: the reuse of buffer 0 inside one transfer is covered by the record upload's test
+    only.  The merged result equals the single-shard run."""
+    recs, L = plain_upload_case(synth)
+    want_order, want_dup, _ = sd_oracle.run(L, recs)
+    eng = pkg.SortDedupEngine(0)                       # its own engine: the buffers of a used one may be larger
+    try:
+        order, dup, info = sharded(pkg, device_shard(eng), L, recs, 2)
+    finally:
+        eng.close()
+    for sh in info:
+        assert 262_144 < len(sh["order_coord"]) < 270_000 and len(sh["mark_recs"]) <= 32_768
+    assert np.array_equal(order, want_order)
+    assert np.array_equal(dup, want_dup)
+
+
 def test_the_routed_mark_reaches_the_device_bitmap(pkg, sd_engine, sd_oracle, synth):
     raw = boundary_case(synth)
     recs, idx, L = pkg.sortdedup.pack(raw)

@@ -300,6 +300,34 @@ def test_streamed_upload_equals_one_shot(pkg, sd_engine, synth, monkeypatch):
         pkg.native.check(sd_engine.lib.mgx_sortdedup_upload_end(sd_engine.ctx, 5))
 
 
+@pytest.mark.parametrize("n", [65_536, 65_537])
+def test_record_upload_on_the_seams_of_the_staging_buffers(pkg, sd_oracle, synth, n):
+    """A new engine sizes its two staging buffers to half of the first upload, at least 1 MiB: 32 768 records per piece at
+    these counts.  65 536 records end exactly on the second buffer; 65 537 make three pieces of 32 768, 32 768 and 1, the
+    third in the first buffer again.  A 5' end wrapped below zero in the second piece only makes that piece travel raw
+    between two compact ones, through the same pair of buffers.  Order and flags equal the oracle's and those of a streamed
+    upload of the same records in uneven chunks."""
+    recs, L = synth.gen_sortdedup_packed(n + 3, 31, n_contigs=3, contig_len=1_000_000)
+    recs = recs[:n].copy()                             # the tail is fragments: no record loses its mate
+    assert len(recs) == n and (recs["mate"][-8:] == synth.NO_MATE).all()
+    recs["prime5"][40_001] = np.uint64(2**64 - 5)      # in [32 768, 65 536): the second piece
+    assert int((recs["prime5"] >= 2**32).sum()) == 1 and int((recs["coord"] >= 2**32).sum()) == 0
+    want_order, want_dup, _ = sd_oracle.run(L, recs)
+    eng = pkg.SortDedupEngine(0)                       # its own engine: the buffers of a used one may be larger
+    try:
+        order, dup = eng.sort_mark(L, recs)
+        st = eng.stats()
+        cuts = [0, 1, 30_000, 40_002, n]
+        eng.upload_chunks(L, (recs[a:b] for a, b in zip(cuts, cuts[1:])), n_expected=1000)
+        eng.run()
+        order2, dup2 = eng.results()
+    finally:
+        eng.close()
+    assert np.array_equal(order, want_order) and np.array_equal(dup, want_dup)
+    assert np.array_equal(order2, want_order) and np.array_equal(dup2, want_dup)
+    assert st["n_builds"] == 2 and st["packed_pair"] == 0 and st["n_records"] == n
+
+
 def test_histogram_pass_sort_matches_the_oracle_on_packed_and_raw_inputs(pkg, sd_oracle, synth):
     """The default engine (a histogram pass, a scan and a scatter per radix pass) on 3 M packed records and on a raw
     record set with every kind of pair: same order, same flags as the oracle."""
