@@ -106,6 +106,12 @@ class BgzfStore:
         native.check(self.lib.mgx_bgzf_store_put(self.h, _ptr(data), len(data), C.byref(addr)))
         return int(addr.value)
 
+    def put_device(self, device_ptr, n_bytes):
+        """n_bytes that lie in device memory (SamBatch.device_records() after a run) -> their address in the store"""
+        addr = C.c_uint64()
+        native.check(self.lib.mgx_bgzf_store_put_device(self.h, device_ptr, n_bytes, C.byref(addr)))
+        return int(addr.value)
+
     def emit(self, order, dup, addr, length):
         """Returns (all blocks back to back as bytes, compressed offset of every block, uoff[n + 1])."""
         order = np.ascontiguousarray(order, dtype=np.uint32); dup = np.ascontiguousarray(dup, dtype=np.uint8)

@@ -12,10 +12,16 @@
 #include <cstring>
 
 #include "mgx_bam.h"
+#include "mgx_sam.h"
 #include "mgx_pairhmm.h"       // mgx_last_error
 
 using slicecut::Slice;
 using clk = std::chrono::steady_clock;
+
+bool sam_on_device() {
+    const char* e = getenv("MGX_CLI_SAM");
+    return e && !strcmp(e, "device");
+}
 
 bool pread_all(int fd, char* dst, size_t n, uint64_t at) {
     while (n) {
@@ -55,7 +61,7 @@ void GpuBringUp::run(int device, uint64_t text_bytes, uint64_t inflate_hbm, uint
         }
     }
     if (tr) fprintf(stderr, "  bring-up: runtime up, device memory known at %.3f s\n", since());
-    if (use_store && mgx_bgzf_create(device, 0, &zctx)) ok = false;
+    if ((use_store || sam_on_device()) && mgx_bgzf_create(device, 0, &zctx)) ok = false;      // the SAM batches hang off it too
     if (tr) fprintf(stderr, "  bring-up: compressor context at %.3f s\n", since());
     if (ok && use_store && (mgx_bgzf_store_create(zctx, &store) || mgx_bgzf_store_reserve(store, text_bytes ? text_bytes * 6 / 10 : (1ull << 30)))) ok = false;
     if (tr) fprintf(stderr, "  bring-up: record store ready at %.3f s\n", since());
@@ -134,6 +140,24 @@ static std::string refused_record(const uint64_t* off, const std::vector<mgx_bam
     return "BAM record at offset " + std::to_string(base + off[i]) + " of the uncompressed stream: " + why.substr(colon + 2);
 }
 
+// What a Chunk holds per record besides the bytes, and the pairing, from complete keys (BAM input and SAM text encoded on the
+// device end here).  False: c->err.
+static bool chunk_from_keys(const std::vector<mgx_bam_key_t>& keys, const samtext::Header& h, Chunk* c) {
+    const uint64_t n = keys.size();
+    c->flag.resize(n); c->tid.resize(n); c->pos.resize(n); c->end.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const mgx_bam_key_t& k = keys[i];
+        c->flag[i] = k.flag; c->tid[i] = k.tid; c->pos[i] = k.pos; c->end[i] = k.end;
+    }
+    c->recs.resize(n); c->input_index.resize(n);
+    uint64_t L = 0;
+    if (mgx_bam_pack_keys(n, keys.data(), (uint32_t)h.ref_len.size(), h.ref_len.data(), c->recs.data(), c->input_index.data(), &L)) {
+        c->err = std::string("pack: ") + mgx_last_error();
+        return false;
+    }
+    return true;
+}
+
 static void parse_bam_slice(const Slice& sl, const samtext::Header& h, Chunk* c) {
     const uint8_t* data = sl.bam_data;
     const uint64_t* off = sl.rec_off;
@@ -161,7 +185,7 @@ static void parse_bam_slice(const Slice& sl, const samtext::Header& h, Chunk* c)
         // what the device rules declined (tokens that need strtol, the long-CIGAR placeholder) is derived here
         if (mgx_bam_keys_redo(data, off, n, keys.data())) { c->err = refused_record(off, keys, sl.bam_at - off[0]); return; }       // bam_at: where the slice's first record is
     }
-    c->flag.resize(n); c->tid.resize(n); c->pos.resize(n); c->end.resize(n); c->blob_off.resize(n + 1);
+    c->blob_off.resize(n + 1);
     uint64_t bytes = 0;
     for (uint64_t i = 0; i < n; ++i) {
         int32_t bs;
@@ -170,20 +194,117 @@ static void parse_bam_slice(const Slice& sl, const samtext::Header& h, Chunk* c)
     }
     c->blob_off[n] = bytes;
     c->blob.resize(bytes);
-    for (uint64_t i = 0; i < n; ++i) {
-        const mgx_bam_key_t& k = keys[i];
-        c->flag[i] = k.flag; c->tid[i] = k.tid; c->pos[i] = k.pos; c->end[i] = k.end;
-        memcpy(c->blob.data() + c->blob_off[i], data + off[i] + 4, c->blob_off[i + 1] - c->blob_off[i]);
+    for (uint64_t i = 0; i < n; ++i) memcpy(c->blob.data() + c->blob_off[i], data + off[i] + 4, c->blob_off[i + 1] - c->blob_off[i]);
+    if (!chunk_from_keys(keys, h, c)) c->err += " (records of the slice at offset " + std::to_string(sl.bam_at) + " of the uncompressed stream)";
+}
+
+// ---- one slice of SAM text, encoded on the device (MGX_CLI_SAM=device) ---------------------------------------
+// The thread's batch takes the slice's text, the device gives BAM records and keys; the lines its rule set declined, and the
+// few whose key the BAM rules left to the host, are encoded by parse_record_into as always and keyed by mgx_bam_keys_host
+// on those bytes.  Records keep the slice's order.  With a record store the device-made records go into it device to
+// device and never cross PCIe; otherwise they come back into c->blob.
+void Ingest::parse_slice_device(const char* data, size_t size, SamBatch* sb, Chunk* c) {
+    if (!gpu_.ready()) { c->err = "GPU: " + gpu_.error(); return; }
+    // thread time per step, summed over the slices and threads for MGX_CLI_TRACE: copy in | submit + wait | host lines | records placed | pairing
+    auto t_last = clk::now();
+    auto lap = [&](int k) { const auto t = clk::now(); sam_ns_[k] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_last).count(); t_last = t; };
+    mgx_bgzf_t* ctx = gpu_.zctx;
+    mgx_bgzf_store_t* store = gpu_.store;
+    uint64_t want_rec = std::max<uint64_t>(sb->max_rec, size / 64 + 1024);      // ordinary lines are a few hundred bytes
+    const uint64_t* line_off; const uint32_t* line_len; const uint64_t* rec_off; const mgx_bam_key_t* dkeys; const uint8_t* bytes = nullptr;
+    uint64_t n = 0, n_out = 0;
+    for (;;) {
+        if (!sb->b || sb->cap < size || sb->max_rec < want_rec) {            // grows with the slices (a window that doubled)
+            if (sb->b) mgx_sam_batch_destroy(ctx, sb->b);
+            sb->b = nullptr;
+            sb->cap = std::max<uint64_t>(size, sb->cap * 2); sb->max_rec = want_rec;
+            if (mgx_sam_batch_create(ctx, sam_table_, sb->cap, sb->max_rec, &sb->b)) { c->err = std::string("GPU: ") + mgx_last_error(); return; }
+        }
+        memcpy(mgx_sam_batch_input(sb->b), data, size);
+        lap(0);
+        int rc = mgx_sam_batch_submit(ctx, sb->b, size);
+        if (!rc) rc = mgx_sam_batch_wait(ctx, sb->b, &line_off, &line_len, &rec_off, &dkeys, &n, &n_out, store ? nullptr : &bytes);
+        if (rc == -E2BIG && want_rec < size / 2 + 1) { want_rec = std::min<uint64_t>(want_rec * 4, size / 2 + 1); continue; }      // short lines: more of them
+        if (rc) { c->err = std::string("GPU: ") + mgx_last_error(); return; }
+        break;
     }
-    c->recs.resize(n); c->input_index.resize(n);
-    uint64_t L = 0;
-    if (mgx_bam_pack_keys(n, keys.data(), (uint32_t)h.ref_len.size(), h.ref_len.data(), c->recs.data(), c->input_index.data(), &L))
-        c->err = std::string("pack: ") + mgx_last_error() + " (records of the slice at offset " + std::to_string(sl.bam_at) + " of the uncompressed stream)";
+    lap(1);
+    // the lines left to the host, in order: the first one the parser rejects is the slice's error, worded as parse_slice words it
+    std::vector<mgx_bam_key_t> keys(dkeys, dkeys + n);
+    std::vector<uint8_t> host;                               // their records, block_size in front
+    std::vector<uint64_t> host_line, host_off;
+    {
+        std::vector<uint32_t> cigar; std::vector<char> qname; std::vector<uint8_t> blob;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!keys[i].redo) continue;
+            samtext::Parsed pr;
+            cigar.clear(); qname.clear(); blob.clear();
+            if (!samtext::parse_record_into(data + line_off[i], line_len[i], hdr_, &pr, &cigar, nullptr, &qname, &blob, &c->err)) {
+                c->err += " at: " + std::string(data + line_off[i], std::min<size_t>(line_len[i], 80));
+                return;
+            }
+            const uint32_t bs = (uint32_t)blob.size();
+            host_line.push_back(i); host_off.push_back(host.size());
+            host.insert(host.end(), (const uint8_t*)&bs, (const uint8_t*)&bs + 4);
+            host.insert(host.end(), blob.begin(), blob.end());
+        }
+        if (!host_line.empty()) {
+            std::vector<mgx_bam_key_t> hk(host_line.size());
+            if (mgx_bam_keys_host(host.data(), host_off.data(), host_off.size(), hk.data())) { c->err = mgx_last_error(); return; }
+            for (size_t j = 0; j < hk.size(); ++j) {
+                const uint8_t same = keys[host_line[j]].same_qname;      // from the text, by the device: the host saw the record alone
+                keys[host_line[j]] = hk[j];
+                keys[host_line[j]].same_qname = same;
+            }
+        }
+    }
+    sam_lines_device_ += n - host_line.size(); sam_lines_host_ += host_line.size();
+    lap(2);
+    // where every record is: without its block_size field, as the writer takes it
+    std::vector<uint64_t> size_of(n);
+    for (uint64_t i = 0; i < n; ++i) size_of[i] = rec_off[i + 1] - rec_off[i];
+    for (size_t j = 0; j < host_line.size(); ++j) size_of[host_line[j]] = (j + 1 < host_off.size() ? host_off[j + 1] : host.size()) - host_off[j];
+    if (store) {
+        uint64_t dev_at = 0, host_at = 0;
+        if (mgx_bgzf_store_put_device(store, mgx_sam_batch_device_records(sb->b), n_out, &dev_at) || mgx_bgzf_store_put(store, host.data(), host.size(), &host_at)) {
+            c->err = std::string("GPU: ") + mgx_last_error();
+            return;
+        }
+        c->rec_addr.resize(n); c->rec_len.resize(n);
+        size_t j = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const bool on_host = j < host_line.size() && host_line[j] == i;
+            c->rec_addr[i] = (on_host ? host_at + host_off[j] : dev_at + rec_off[i]) + 4;
+            c->rec_len[i] = (uint32_t)(size_of[i] - 4);
+            j += on_host;
+        }
+    } else {
+        c->blob_off.resize(n + 1);
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < n; ++i) { c->blob_off[i] = total; total += size_of[i] - 4; }
+        c->blob_off[n] = total;
+        c->blob.resize(total);
+        size_t j = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const bool on_host = j < host_line.size() && host_line[j] == i;
+            memcpy(c->blob.data() + c->blob_off[i], (on_host ? host.data() + host_off[j] : bytes + rec_off[i]) + 4, size_of[i] - 4);
+            j += on_host;
+        }
+    }
+    lap(3);
+    chunk_from_keys(keys, hdr_, c);
+    lap(4);
 }
 
 // ---- Ingest ------------------------------------------------------------------------------------------------------------
 Ingest::Ingest(const samtext::Header& hdr, GpuBringUp& gpu, int threads, const char* in_base, int in_fd, slicecut::PieceSource* src)
     : hdr_(hdr), gpu_(gpu), in_base_(in_base), in_fd_(in_fd), src_(src), queue_cap_((size_t)threads * 2) {
+    if (sam_on_device()) {                                   // the header's names as the device looks them up
+        std::string names; std::vector<uint32_t> at(1, 0);
+        for (const std::string& nm : hdr.ref_name) { names += nm; at.push_back((uint32_t)names.size()); }
+        names.push_back('\0');
+        if (mgx_sam_table_create((uint32_t)hdr.ref_name.size(), (const uint8_t*)names.data(), at.data(), &sam_table_)) fail(std::string("SAM table: ") + mgx_last_error());
+    }
     for (int t = 0; t < threads; ++t) pool_.emplace_back([this]() { worker(); });
 }
 
@@ -217,6 +338,17 @@ void Ingest::finish() {
     for (auto& th : pool_) th.join();
     pool_.clear();
     queue_.clear();                                          // (after a failure: slices never parsed still hold inflated text)
+    if (sam_table_) {
+        if (getenv("MGX_CLI_TRACE"))
+            fprintf(stderr, "  sam device: %llu lines encoded on the device, %llu declined and encoded on the host\n",
+                    (unsigned long long)sam_lines_device_.load(), (unsigned long long)sam_lines_host_.load());
+        if (getenv("MGX_CLI_TRACE"))
+            fprintf(stderr, "  sam device: thread seconds over all parsers: %.3f copying text into pinned input, %.3f in submit + wait, %.3f on host-encoded lines, "
+                            "%.3f placing the records (store puts / copies into blob), %.3f filling the chunk and pairing\n",
+                    sam_ns_[0].load() / 1e9, sam_ns_[1].load() / 1e9, sam_ns_[2].load() / 1e9, sam_ns_[3].load() / 1e9, sam_ns_[4].load() / 1e9);
+        mgx_sam_table_destroy(sam_table_);
+        sam_table_ = nullptr;
+    }
 }
 
 // The in-order commit is the one serial step of the ingest: it only turns slice-local mate indices into arrival
@@ -247,7 +379,7 @@ void Ingest::commit_ready(std::vector<std::vector<mgx_rec_t>>* trash) {
 // in-order commit (upload of the packed records)
 bool Ingest::finish_chunk(std::unique_ptr<Chunk> ch, uint64_t seq) {
     mgx_bgzf_store_t* store = gpu_.store;
-    if (store) {                                    // the slice's BAM bytes go to HBM now and leave host memory
+    if (store && ch->rec_addr.empty()) {            // the slice's BAM bytes go to HBM now and leave host memory (device-encoded SAM: they are there)
         if (mgx_bgzf_store_put(store, ch->blob.data(), ch->blob.size(), &ch->dev_base)) { fail(std::string("GPU: ") + mgx_last_error()); return false; }
         std::vector<uint8_t>().swap(ch->blob);
     }
@@ -257,10 +389,13 @@ bool Ingest::finish_chunk(std::unique_ptr<Chunk> ch, uint64_t seq) {
         ch->kept.resize(n);
         for (size_t k = 0; k < n; ++k) {
             const uint32_t src = ch->input_index[k];
-            const uint8_t* where = store ? (const uint8_t*)(uintptr_t)(ch->dev_base + ch->blob_off[src]) : ch->blob.data() + ch->blob_off[src];
-            ch->kept[k] = Kept{where, (uint32_t)(ch->blob_off[src + 1] - ch->blob_off[src]), ch->tid[src], (int32_t)ch->pos[src], ch->end[src],
-                               (ch->flag[src] & 4) == 0};
+            const bool addressed = !ch->rec_addr.empty();
+            const uint8_t* where = addressed ? (const uint8_t*)(uintptr_t)ch->rec_addr[src]
+                                   : store   ? (const uint8_t*)(uintptr_t)(ch->dev_base + ch->blob_off[src]) : ch->blob.data() + ch->blob_off[src];
+            ch->kept[k] = Kept{where, addressed ? ch->rec_len[src] : (uint32_t)(ch->blob_off[src + 1] - ch->blob_off[src]), ch->tid[src], (int32_t)ch->pos[src],
+                               ch->end[src], (ch->flag[src] & 4) == 0};
         }
+        std::vector<uint64_t>().swap(ch->rec_addr); std::vector<uint32_t>().swap(ch->rec_len);
         std::vector<uint32_t>().swap(ch->input_index);
         std::vector<uint16_t>().swap(ch->flag); std::vector<int32_t>().swap(ch->tid); std::vector<int64_t>().swap(ch->pos);
         std::vector<int32_t>().swap(ch->end); std::vector<uint64_t>().swap(ch->blob_off);
@@ -276,7 +411,10 @@ bool Ingest::finish_chunk(std::unique_ptr<Chunk> ch, uint64_t seq) {
 
 // Parses one slice where its text is: in the mapping of the input file, in this thread's buffer after a pread, in a piece's
 // buffer, or in the slice itself.  False after fail().
-bool Ingest::parse(const Slice& sl, std::vector<char>* text_buf, Chunk* ch) {
+bool Ingest::parse(const Slice& sl, std::vector<char>* text_buf, SamBatch* sb, Chunk* ch) {
+    auto parse_slice = [&](const char* data, size_t size, const samtext::Header& h, Chunk* c) {
+        if (sam_table_) parse_slice_device(data, size, sb, c); else ::parse_slice(data, size, h, c);
+    };
     if (sl.bam) {
         parse_bam_slice(sl, hdr_, ch);
         if (!ch->err.empty()) { fail("BAM input: " + ch->err); return false; }
@@ -295,12 +433,14 @@ bool Ingest::parse(const Slice& sl, std::vector<char>* text_buf, Chunk* ch) {
         parse_slice(text_buf->data(), sl.file_len, hdr_, ch);
     } else if (sl.ext) parse_slice(sl.ext, sl.ext_len, hdr_, ch);
     else parse_slice(sl.text.data(), sl.text.size(), hdr_, ch);
-    if (!ch->err.empty()) { fail("SAM parse error: " + ch->err); return false; }
+    if (!ch->err.empty()) { fail(ch->err.compare(0, 5, "GPU: ") == 0 ? ch->err : "SAM parse error: " + ch->err); return false; }
     return true;
 }
 
 void Ingest::worker() {
     std::vector<char> text_buf;                          // this thread's slice of the input file
+    SamBatch sam_batch;                                  // ... and its device batch (MGX_CLI_SAM=device)
+    struct Release { Ingest* in; SamBatch* sb; ~Release() { if (sb->b) mgx_sam_batch_destroy(in->gpu_.zctx, sb->b); } } release{this, &sam_batch};
     // The HIP runtime and the contexts take 0.2-0.3 s to come up: until then a parser keeps its parsed slices and goes on with
     // the next one instead of waiting with one slice in hand (round 3: at 4 M records the parse itself is 0.05 s of thread
     // time per thread -- the ingest was the bring-up plus everything that waited for it)
@@ -322,7 +462,7 @@ void Ingest::worker() {
         std::unique_ptr<Chunk> ch;
         if (have) {
             ch.reset(new Chunk);
-            const bool parsed = parse(sl, &text_buf, ch.get());
+            const bool parsed = parse(sl, &text_buf, &sam_batch, ch.get());
             std::string().swap(sl.text);
             sl.hold.reset();                             // a piece's buffer goes back to its source once its text is parsed
             if (!parsed) return;

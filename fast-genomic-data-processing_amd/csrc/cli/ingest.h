@@ -14,10 +14,12 @@
 #include <vector>
 
 #include "../../../include/mgx_bgzf.h"
+#include "../../../include/mgx_sam.h"
 #include "mgx_sortdedup.h"
 #include "sam_text.h"
 #include "slice_cut.h"
 
+bool sam_on_device();                                          // MGX_CLI_SAM=device: SAM text is encoded on the device
 bool pread_all(int fd, char* dst, size_t n, uint64_t at);      // all n bytes at `at`; false on a read error or a short file
 
 enum OutMode { kOutDevice, kOutPinned, kOutZlib };      // -z: where the output is made
@@ -32,6 +34,7 @@ struct Chunk {                       // one parsed + packed slice
     std::vector<char> qname; std::vector<uint64_t> qname_off{0};
     std::vector<uint8_t> blob; std::vector<uint64_t> blob_off{0};      // BAM bytes per record (kept until the output is written)
     std::vector<mgx_rec_t> recs; std::vector<uint32_t> input_index;   // arrival order inside the slice
+    std::vector<uint64_t> rec_addr; std::vector<uint32_t> rec_len;     // device-encoded SAM with -z device: every record's own address in HBM
     uint64_t dev_base = 0;               // -z device: where the slice's BAM bytes are in HBM (blob is dropped then)
     uint64_t arrival_base = 0;           // set at commit: the slice's first arrival index
     std::vector<Kept> kept;              // what the writer needs per record, slice-local arrival order (filled by the parser thread)
@@ -82,8 +85,10 @@ public:
     double commit_seconds = 0, upload_seconds = 0;           // serial part of the ingest (MGX_CLI_TRACE)
 
 private:
+    struct SamBatch { mgx_sam_batch_t* b = nullptr; uint64_t cap = 0, max_rec = 0; };      // one per parser thread
     void worker();
-    bool parse(const slicecut::Slice& sl, std::vector<char>* text_buf, Chunk* ch);
+    bool parse(const slicecut::Slice& sl, std::vector<char>* text_buf, SamBatch* sb, Chunk* ch);
+    void parse_slice_device(const char* data, size_t size, SamBatch* sb, Chunk* c);
     bool finish_chunk(std::unique_ptr<Chunk> ch, uint64_t seq);
     void commit_ready(std::vector<std::vector<mgx_rec_t>>* trash);      // called with commit_mu_ held
 
@@ -95,4 +100,7 @@ private:
     std::mutex commit_mu_;                                   // guards ready_, next_commit_ and the public result
     std::map<uint64_t, std::unique_ptr<Chunk>> ready_; uint64_t next_commit_ = 0;
     std::vector<std::thread> pool_;
+    mgx_sam_table_t* sam_table_ = nullptr;                   // MGX_CLI_SAM=device: non-NULL
+    std::atomic<uint64_t> sam_lines_device_{0}, sam_lines_host_{0};
+    std::atomic<uint64_t> sam_ns_[5] = {};                   // thread time per step of parse_slice_device, for MGX_CLI_TRACE
 };

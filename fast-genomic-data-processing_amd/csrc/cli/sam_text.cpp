@@ -1,6 +1,8 @@
 // sam_text.cpp -- see sam_text.h.  Follows the SAM/BAM specification (SAMv1 sections 1.4, 4.2).
 #include "sam_text.h"
 
+#include "../sam_line_core.h"
+
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
@@ -172,6 +174,10 @@ inline bool to_int(const char* f, size_t n, int64_t* v) {
     return true;
 }
 
+// POS / PNEXT to 0-based in 32 bits, wrapping as the subtraction always has (a value whose low 32 bits are INT32_MIN must
+// not be an overflow of a signed int)
+inline int32_t minus_one(int64_t v) { return (int32_t)((uint32_t)v - 1u); }
+
 template <typename T>
 inline void put(std::vector<uint8_t>& a, T v) { const uint8_t* p = (const uint8_t*)&v; a.insert(a.end(), p, p + sizeof(T)); }
 
@@ -249,7 +255,7 @@ bool parse_record(const char* line, size_t len, const Header& h, Record* r, std:
     r->tid = (n[2] == 1 && f[2][0] == '*') ? -1 : find_ref(h, f[2], n[2]);
     if (r->tid < 0 && !(n[2] == 1 && f[2][0] == '*')) { *err = "RNAME not in the header"; return false; }
     if (!to_int(f[3], n[3], &v)) { *err = "bad POS"; return false; }
-    r->pos = (int32_t)v - 1;
+    r->pos = minus_one(v);
     if (!to_int(f[4], n[4], &v) || v < 0 || v > 255) { *err = "bad MAPQ"; return false; }
     r->mapq = (uint8_t)v;
     r->cigar.clear();
@@ -273,7 +279,7 @@ bool parse_record(const char* line, size_t len, const Header& h, Record* r, std:
     else if (n[6] == 1 && f[6][0] == '*') r->mtid = -1;
     else { r->mtid = find_ref(h, f[6], n[6]); if (r->mtid < 0) { *err = "RNEXT not in the header"; return false; } }
     if (!to_int(f[7], n[7], &v)) { *err = "bad PNEXT"; return false; }
-    r->mpos = (int32_t)v - 1;
+    r->mpos = minus_one(v);
     if (!to_int(f[8], n[8], &v)) { *err = "bad TLEN"; return false; }
     r->tlen = (int32_t)v;
     const uint8_t* nt16 = nt16_table();
@@ -317,7 +323,7 @@ bool parse_record_into(const char* line, size_t len, const Header& h, Parsed* ou
     const int32_t tid = no_ref ? -1 : find_ref(h, f[2], n[2]);
     if (tid < 0 && !no_ref) return bad("RNAME not in the header");
     if (!to_int(f[3], n[3], &v)) return bad("bad POS");
-    const int32_t pos = (int32_t)v - 1;
+    const int32_t pos = minus_one(v);
     if (!to_int(f[4], n[4], &v) || v < 0 || v > 255) return bad("bad MAPQ");
     const uint8_t mapq = (uint8_t)v;
     int64_t ref_len = 0;
@@ -347,7 +353,7 @@ bool parse_record_into(const char* line, size_t len, const Header& h, Parsed* ou
     else if (n[6] == 1 && f[6][0] == '*') mtid = -1;
     else { mtid = find_ref(h, f[6], n[6]); if (mtid < 0) return bad("RNEXT not in the header"); }
     if (!to_int(f[7], n[7], &v)) return bad("bad PNEXT");
-    const int32_t mpos = (int32_t)v - 1;
+    const int32_t mpos = minus_one(v);
     if (!to_int(f[8], n[8], &v)) return bad("bad TLEN");
     const int32_t tlen = (int32_t)v;
     const bool no_seq = n[9] == 1 && f[9][0] == '*';
@@ -389,15 +395,8 @@ bool parse_record_into(const char* line, size_t len, const Header& h, Parsed* ou
 
 namespace bamout {
 
-int reg2bin(int64_t beg, int64_t end) {
-    --end;
-    if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-    return 0;
-}
+// (the formula is stated once, in sam_line_core.h, where the device encoder reads it too)
+int reg2bin(int64_t beg, int64_t end) { return mgx_sam::reg2bin(beg, end); }
 
 void encode_record(const samtext::Record& r, std::vector<uint8_t>* out) {
     const size_t l_qn = r.qname.size() + 1, n_cig = r.cigar.size();

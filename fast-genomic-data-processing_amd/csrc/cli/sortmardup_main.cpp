@@ -289,7 +289,9 @@ int main(int argc, char** argv) {
     // (the sizes are stated in SAM text, of which BAM bytes are about 0.6)
     const uint64_t text_bytes = gzs ? (uint64_t)((double)in.file_bytes * gzs->ratio() * (opt.bam ? 5.0 / 3.0 : 1.0)) : in.file_bytes;
 
-    GpuBringUp gpu(opt.device, opt.out_mode, text_bytes, gzs ? gzs->hbm_bytes_to_come() : 0, L);
+    // MGX_CLI_SAM=device: every parser thread's batch holds a slice of text, twice that for its records and their arrays
+    const uint64_t sam_hbm = !opt.bam && sam_on_device() ? (uint64_t)opt.threads * opt.slice_bytes * 5 : 0;
+    GpuBringUp gpu(opt.device, opt.out_mode, text_bytes, (gzs ? gzs->hbm_bytes_to_come() : 0) + sam_hbm, L);
 
     // ---- ingest: the reader (this thread) cuts slices, the parsers take them from the queue
     Ingest ingest(hdr, gpu, opt.threads, in.base, in.fd, src.get());

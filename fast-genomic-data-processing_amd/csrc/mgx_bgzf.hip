@@ -1243,30 +1243,58 @@ void mgx_bgzf_store_destroy(mgx_bgzf_store_t* st) {
     delete st;
 }
 
+// n bytes of the store's HBM (1 GB pieces; a put never straddles two), 16-byte aligned
+static int store_alloc(mgx_bgzf_store* st, u64 n, u8** dst) {
+    std::lock_guard<std::mutex> g(st->mu);
+    const u64 need = (n + 15) & ~15ull;
+    if (st->cur_off + need > st->cur_cap) {
+        const u64 cap = std::max<u64>(need, 1ull << 30);
+        u8* p = nullptr;
+        if (hipMalloc((void**)&p, cap) != hipSuccess) { set_error("hipMalloc of %llu bytes for the record store failed (%llu bytes stored)", (unsigned long long)cap, (unsigned long long)st->total); return -ENOMEM; }
+        st->chunks.push_back(p); st->cur_off = 0; st->cur_cap = cap;
+    }
+    *dst = st->chunks.back() + st->cur_off;
+    st->cur_off += need; st->total += n;
+    return 0;
+}
+
+static int store_take_slot(mgx_bgzf_store* st) {
+    std::unique_lock<std::mutex> lk(st->stage_mu);
+    st->stage_cv.wait(lk, [&] { return !st->stage_free.empty(); });
+    const int k = st->stage_free.back(); st->stage_free.pop_back();
+    return k;
+}
+
+static void store_give_slot(mgx_bgzf_store* st, int k) {
+    { std::lock_guard<std::mutex> g(st->stage_mu); st->stage_free.push_back(k); }
+    st->stage_cv.notify_one();
+}
+
+int mgx_bgzf_store_put_device(mgx_bgzf_store_t* st, uint64_t device_ptr, uint64_t n, uint64_t* addr) {
+    if (!st || !addr || (n && !device_ptr)) { set_error("NULL argument"); return -EINVAL; }
+    if (n == 0) { *addr = 0; return 0; }
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    u8* dst;
+    if (const int rc = store_alloc(st, n, &dst)) return rc;
+    const int k = store_take_slot(st);             // for the slot's stream: nothing is staged
+    hipError_t e = hipSuccess;
+    if (!st->copy[k]) e = hipStreamCreateWithFlags(&st->copy[k], hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, (const void*)(uintptr_t)device_ptr, n, hipMemcpyDeviceToDevice, st->copy[k]);
+    if (e == hipSuccess) e = hipStreamSynchronize(st->copy[k]);
+    store_give_slot(st, k);
+    if (e != hipSuccess) { set_error("copy of %llu device bytes to the record store: %s", (unsigned long long)n, hipGetErrorString(e)); return -EIO; }
+    *addr = (uint64_t)(uintptr_t)dst;
+    return 0;
+}
+
 int mgx_bgzf_store_put(mgx_bgzf_store_t* st, const uint8_t* bytes, uint64_t n, uint64_t* addr) {
     if (!st || !addr || (n && !bytes)) { set_error("NULL argument"); return -EINVAL; }
     if (n == 0) { *addr = 0; return 0; }           // nothing to store (a slice of blank lines); no chunk is touched
     HIP_TRY(hipSetDevice(st->ctx->device));
     u8* dst;
-    {
-        std::lock_guard<std::mutex> g(st->mu);
-        const u64 need = (n + 15) & ~15ull;
-        if (st->cur_off + need > st->cur_cap) {
-            const u64 cap = std::max<u64>(need, 1ull << 30);          // HBM in 1 GB pieces; a put never straddles two
-            u8* p = nullptr;
-            if (hipMalloc((void**)&p, cap) != hipSuccess) { set_error("hipMalloc of %llu bytes for the record store failed (%llu bytes stored)", (unsigned long long)cap, (unsigned long long)st->total); return -ENOMEM; }
-            st->chunks.push_back(p); st->cur_off = 0; st->cur_cap = cap;
-        }
-        dst = st->chunks.back() + st->cur_off;
-        st->cur_off += need; st->total += n;
-    }
+    if (const int rc = store_alloc(st, n, &dst)) return rc;
     for (u64 done = 0; done < n;) {
-        int k;
-        {
-            std::unique_lock<std::mutex> lk(st->stage_mu);
-            st->stage_cv.wait(lk, [&] { return !st->stage_free.empty(); });
-            k = st->stage_free.back(); st->stage_free.pop_back();
-        }
+        const int k = store_take_slot(st);
         const u64 piece = std::min<u64>(mgx_bgzf_store::kStageBytes, n - done);
         hipError_t e = hipSuccess;
         if (!st->copy[k]) e = hipStreamCreateWithFlags(&st->copy[k], hipStreamNonBlocking);                                     // this slot's first use
@@ -1276,8 +1304,7 @@ int mgx_bgzf_store_put(mgx_bgzf_store_t* st, const uint8_t* bytes, uint64_t n, u
             e = hipMemcpyAsync(dst + done, st->stage[k], piece, hipMemcpyHostToDevice, st->copy[k]);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st->copy[k]);
-        { std::lock_guard<std::mutex> g(st->stage_mu); st->stage_free.push_back(k); }
-        st->stage_cv.notify_one();
+        store_give_slot(st, k);
         if (e != hipSuccess) { set_error("copy of %llu bytes to the record store: %s", (unsigned long long)piece, hipGetErrorString(e)); return -EIO; }
         done += piece;
     }

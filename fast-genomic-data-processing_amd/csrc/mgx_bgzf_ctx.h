@@ -29,6 +29,10 @@ struct mgx_bgzf {
     uint64_t bam_tiles = 0, bam_rewalked = 0, bam_redo = 0;
     uint32_t bam_rounds = 0;
     float bam_ms_index = 0, bam_ms_keys = 0;
+    // SAM text input (mgx_sam.hip): the last batch waited for
+    std::mutex sam_mu;
+    uint64_t sam_lines = 0, sam_declined = 0, sam_bytes_in = 0, sam_bytes_out = 0, sam_tiles = 0;
+    float sam_ms_lines = 0, sam_ms_encode = 0, sam_ms_keys = 0;
 };
 
 struct mgx_bgzf_inflate {

@@ -286,3 +286,33 @@ BAM_SYMBOLS = {
     "mgx_bam_stats": (C.c_int, [C.c_void_p, C.POINTER(BamStats)]),
 }
 SYMBOLS.update(BAM_SYMBOLS)
+
+
+# ---- include/mgx_sam.h ----------------------------------------------------------------------------
+class SamStats(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_declined", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("n_tiles", C.c_uint64), ("ms_lines", C.c_float), ("ms_encode", C.c_float), ("ms_keys", C.c_float)]
+
+
+_U64P = C.POINTER(C.c_uint64)
+SAM_SYMBOLS = {
+    "mgx_sam_table_create": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgx_sam_table_destroy": (None, [C.c_void_p]),
+    "mgx_sam_lines_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, _U64P]),
+    "mgx_sam_encode_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, _U64P, _U64P, _U64P]),
+    "mgx_sam_encode_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, _U64P, _U64P, _U64P, _U64P]),
+    "mgx_sam_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "mgx_sam_batch_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "mgx_sam_batch_input": (C.c_void_p, [C.c_void_p]),
+    "mgx_sam_batch_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mgx_sam_batch_wait": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), _U64P, _U64P, C.POINTER(C.c_void_p)]),
+    "mgx_sam_batch_device_records": (C.c_uint64, [C.c_void_p]),
+    "mgx_sam_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, _U64P, _U64P, _U64P]),
+    "mgx_sam_stats": (C.c_int, [C.c_void_p, C.POINTER(SamStats)]),
+    "mgx_bgzf_store_put_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _U64P]),
+}
+SYMBOLS.update(SAM_SYMBOLS)

@@ -74,6 +74,10 @@ void mgx_bgzf_store_destroy(mgx_bgzf_store_t* st);
 /* Optional: allocate HBM for about `bytes` of records now (at most one 256 MB piece) instead of inside the first put. */
 int mgx_bgzf_store_reserve(mgx_bgzf_store_t* st, uint64_t bytes);
 int mgx_bgzf_store_put(mgx_bgzf_store_t* st, const uint8_t* bytes, uint64_t n_bytes, uint64_t* device_address);
+/* put() for n_bytes that already lie in device memory (the records of a SAM batch, mgx_sam.h, after its wait): a copy
+ * device to device, nothing crosses PCIe.  Record i of such a batch is then at *device_address + rec_off[i] + 4, which is
+ * what emit() takes per record.  Returns when the copy is done: the source may be reused. */
+int mgx_bgzf_store_put_device(mgx_bgzf_store_t* st, uint64_t device_ptr, uint64_t n_bytes, uint64_t* device_address);
 /* order[q] = index (into addr / len / dup) of the q-th record of the output; addr[i] = device address of record i
  * (put()'s address plus the record's offset in that call's bytes), len[i] its length */
 int mgx_bgzf_store_emit(mgx_bgzf_store_t* st, uint64_t n, const uint32_t* order, const uint8_t* dup, const uint64_t* addr,
