@@ -11,8 +11,8 @@
 //      distance-1 candidate, the run-length case of quality strings -- byte-parallel up to 258 bytes;
 //   2. parse: every thread walks its own 1/NT of the block (greedy with one-step lazy evaluation, matches cut at
 //      the thread's boundary) and emits tokens, counting literal/length and distance symbols in LDS histograms;
-//   3. two length-limited Huffman codes per block (rank by counting, a two-queue merge on one lane, frequencies
-//      halved and rebuilt in the rare case a code comes out longer than 15 bits), the code-length code and the
+//   3. two length-limited Huffman codes per block (rank by counting, a two-queue merge on one lane, the counts
+//      per length repaired as zlib does in the rare case a code comes out longer than 15 bits), the code-length code and the
 //      run-length coded header of RFC 1951 section 3.2.7;
 //   4. every thread's tokens are measured, a scan gives its bit offset, and the bits go into the LDS buffer that
 //      held the input (OR into 32-bit words); a block that would not shrink is emitted stored;
@@ -196,6 +196,24 @@ __device__ __forceinline__ u32 block_scan(Lds& L, u32 v, u32* total) {
     return before + inc - v;
 }
 
+// A code deeper than `limit` (rare: the counts must grow like Fibonacci numbers) is repaired on the counts per length, as in
+// zlib's gen_bitlen.  Lifting the deeper leaves to the limit over-subscribes the code by `over` units of 2^-limit; a step
+// takes one unit back: the deepest leaf short of the limit goes one level down and a leaf from the limit becomes its
+// brother.  The code stays complete and as deep as the limit; the lengths go to the symbols by rank, longest to rarest.
+__device__ __attribute__((noinline)) void limit_lengths(Lds& L, const int n, const int limit, u8* len) {
+    for (int b = 0; b < 16; ++b) L.bl_count[b] = 0;
+    for (int r = 0; r < n; ++r) { const int d = len[L.sorted[r]]; ++L.bl_count[d < limit ? d : limit]; }
+    u32 over = 0;
+    for (int b = 1; b <= limit; ++b) over += L.bl_count[b] << (limit - b);
+    for (over -= 1u << limit; over; --over) {
+        int b = limit - 1;
+        while (b > 1 && L.bl_count[b] == 0) --b;
+        --L.bl_count[b]; L.bl_count[b + 1] += 2; --L.bl_count[limit];
+    }
+    int r = 0;
+    for (int b = limit; b >= 1; --b) for (u32 k = L.bl_count[b]; k; --k) len[L.sorted[r++]] = (u8)b;
+}
+
 // Length-limited Huffman code of freq[0, N): lengths and (bit-reversed) canonical codes.  Called by the whole workgroup.
 // At least two symbols get a code (inflate accepts no incomplete literal/length or code-length code).
 // Parallel but for the merge itself: ranks by counting, leaf depths by walking up the parent links, code values by
@@ -222,78 +240,78 @@ __device__ void huff_build(Lds& L, const u32* freq_in, const int N, const int li
         else if (used == 1) freq[freq[0] ? 1 : 0] = 1;
     }
     lap(8);
-    for (;;) {
-        sync();
-        if (tid < 16) L.bl_count[tid] = 0;
-        if (tid == 0) { L.vars[V_NUSED] = 0; L.vars[V_OVER] = 0; }
-        sync();
-        if (tid < N) {
-            len[tid] = 0;
-            const u32 f = freq[tid];
-            if (f) {
-                int r = 0;
-                for (int j = 0; j < N; ++j) { const u32 g = freq[j]; r += (g != 0) & ((g < f) | ((g == f) & (j < tid))); }
-                L.sorted[r] = (u16)tid;
-                L.wl[r] = f;
-                atomicAdd(&L.vars[V_NUSED], 1u);
-            }
+    sync();
+    if (tid < 16) L.bl_count[tid] = 0;
+    if (tid == 0) { L.vars[V_NUSED] = 0; L.vars[V_OVER] = 0; }
+    sync();
+    if (tid < N) {
+        len[tid] = 0;
+        const u32 f = freq[tid];
+        if (f) {
+            int r = 0;
+            for (int j = 0; j < N; ++j) { const u32 g = freq[j]; r += (g != 0) & ((g < f) | ((g == f) & (j < tid))); }
+            L.sorted[r] = (u16)tid;
+            L.wl[r] = f;
+            atomicAdd(&L.vars[V_NUSED], 1u);
         }
+    }
+    sync();
+    lap(9);
+    const int n = (int)L.vars[V_NUSED];
+    {
+        // Huffman's merges in rounds.  The active nodes form one sorted list Q.  t = Q[0] + Q[1] is the lightest node that
+        // can still be created, so every active node of weight <= t is merged before any new node is touched: the
+        // (even-sized) prefix of Q up to t pairs up neighbour with neighbour, exactly as the sequential algorithm
+        // would take them one pair at a time, and the new nodes -- their weights come out sorted -- are merged with
+        // the rest of Q into the next round's list (positions by binary search, old nodes first on equal weight).
+        // 12-16 rounds for the 250-280 symbols of a BAM block instead of as many dependent steps on one lane
+        // (126 k -> 36 k cycles per block; the same code lengths).
+        u32* qw[2] = {L.wl, L.wi};
+        u16* qi[2] = {L.qid[0], L.qid[1]};
+        if (tid < n) L.qid[0][tid] = (u16)tid;                       // leaves 0 .. n-1 in weight order (rank step above)
+        if (tid == 0) L.vars[V_K] = (u32)n;
         sync();
-        lap(9);
-        const int n = (int)L.vars[V_NUSED];
-        {
-            // Huffman's merges in rounds.  The active nodes form one sorted list Q.  t = Q[0] + Q[1] is the lightest node that
-            // can still be created, so every active node of weight <= t is merged before any new node is touched: the
-            // (even-sized) prefix of Q up to t pairs up neighbour with neighbour, exactly as the sequential algorithm
-            // would take them one pair at a time, and the new nodes -- their weights come out sorted -- are merged with
-            // the rest of Q into the next round's list (positions by binary search, old nodes first on equal weight).
-            // 12-16 rounds for the 250-280 symbols of a BAM block instead of as many dependent steps on one lane
-            // (126 k -> 36 k cycles per block; the same code lengths).
-            u32* qw[2] = {L.wl, L.wi};
-            u16* qi[2] = {L.qid[0], L.qid[1]};
-            if (tid < n) L.qid[0][tid] = (u16)tid;                       // leaves 0 .. n-1 in weight order (rank step above)
-            if (tid == 0) L.vars[V_K] = (u32)n;
+        u32 m = (u32)n, next_id = (u32)n;
+        int cur = 0;
+        while (m > 1) {
+            const u32* w = qw[cur];
+            const u32 t = w[0] + w[1];
+            if ((u32)tid + 1 < m && w[tid] <= t && w[tid + 1] > t) L.vars[V_K] = (u32)tid + 1;     // at most one thread: Q is sorted
             sync();
-            u32 m = (u32)n, next_id = (u32)n;
-            int cur = 0;
-            while (m > 1) {
-                const u32* w = qw[cur];
-                const u32 t = w[0] + w[1];
-                if ((u32)tid + 1 < m && w[tid] <= t && w[tid + 1] > t) L.vars[V_K] = (u32)tid + 1;     // at most one thread: Q is sorted
-                sync();
-                const u32 k = L.vars[V_K] & ~1u, a = m - k, b = k >> 1;
-                if ((u32)tid < b) {                                      // new node tid of this round
-                    const u32 nw = w[2 * tid] + w[2 * tid + 1];
-                    const u32 id = next_id + (u32)tid;
-                    L.parent[qi[cur][2 * tid]] = (u16)id; L.parent[qi[cur][2 * tid + 1]] = (u16)id;
-                    u32 lo = 0, hi = a;                                  // old nodes (Q[k ..)) of weight <= nw go first
-                    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (w[k + mid] <= nw) lo = mid + 1; else hi = mid; }
-                    qw[cur ^ 1][(u32)tid + lo] = nw; qi[cur ^ 1][(u32)tid + lo] = (u16)id;
-                } else if ((u32)tid >= k && (u32)tid < m) {              // old node that stays
-                    const u32 ow = w[tid];
-                    u32 lo = 0, hi = b;                                  // new nodes of weight < ow go first
-                    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (w[2 * mid] + w[2 * mid + 1] < ow) lo = mid + 1; else hi = mid; }
-                    qw[cur ^ 1][((u32)tid - k) + lo] = ow; qi[cur ^ 1][((u32)tid - k) + lo] = qi[cur][tid];
-                }
-                m = a + b; next_id += b; cur ^= 1;
-                sync();
-                if (tid == 0) L.vars[V_K] = m;                           // the next round's default: everything is <= t
-                sync();
+            const u32 k = L.vars[V_K] & ~1u, a = m - k, b = k >> 1;
+            if ((u32)tid < b) {                                      // new node tid of this round
+                const u32 nw = w[2 * tid] + w[2 * tid + 1];
+                const u32 id = next_id + (u32)tid;
+                L.parent[qi[cur][2 * tid]] = (u16)id; L.parent[qi[cur][2 * tid + 1]] = (u16)id;
+                u32 lo = 0, hi = a;                                  // old nodes (Q[k ..)) of weight <= nw go first
+                while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (w[k + mid] <= nw) lo = mid + 1; else hi = mid; }
+                qw[cur ^ 1][(u32)tid + lo] = nw; qi[cur ^ 1][(u32)tid + lo] = (u16)id;
+            } else if ((u32)tid >= k && (u32)tid < m) {              // old node that stays
+                const u32 ow = w[tid];
+                u32 lo = 0, hi = b;                                  // new nodes of weight < ow go first
+                while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (w[2 * mid] + w[2 * mid + 1] < ow) lo = mid + 1; else hi = mid; }
+                qw[cur ^ 1][((u32)tid - k) + lo] = ow; qi[cur ^ 1][((u32)tid - k) + lo] = qi[cur][tid];
             }
+            m = a + b; next_id += b; cur ^= 1;
+            sync();
+            if (tid == 0) L.vars[V_K] = m;                           // the next round's default: everything is <= t
+            sync();
         }
+    }
+    sync();
+    lap(10);
+    if (tid < n) {                               // depth of leaf tid: steps to the root (node 2n - 2)
+        int d = 0;
+        for (int id = tid; id != 2 * n - 2; id = L.parent[id]) ++d;
+        if (d > limit) L.vars[V_OVER] = 1;
+        len[L.sorted[tid]] = (u8)d;
+        atomicAdd(&L.bl_count[d < 16 ? d : 15], 1u);
+    }
+    sync();
+    lap(11);
+    if (L.vars[V_OVER]) {
+        if (tid == 0) limit_lengths(L, n, limit, len);
         sync();
-        lap(10);
-        if (tid < n) {                               // depth of leaf tid: steps to the root (node 2n - 2)
-            int d = 0;
-            for (int id = tid; id != 2 * n - 2; id = L.parent[id]) ++d;
-            if (d > limit) L.vars[V_OVER] = 1;
-            len[L.sorted[tid]] = (u8)d;
-            atomicAdd(&L.bl_count[d < 16 ? d : 15], 1u);
-        }
-        sync();
-        lap(11);
-        if (!L.vars[V_OVER]) break;
-        if (tid < N) { const u32 f = freq[tid]; if (f) freq[tid] = (f + 1) >> 1; }     // flatter, still >= 1
     }
     if (tid == 0) {
         u32 c = 0;
