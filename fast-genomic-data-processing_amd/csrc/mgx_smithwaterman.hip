@@ -21,7 +21,8 @@
 //                 16 bits (I16Rule; the realignment workload of Mutect2 always does): 12.6 instructions per cell
 //   k_sw_fill     32-bit scores, one pair per lane group, compare + select per decision, back-trace bytes, one launch per row class
 //                 -- everything else (long references with long alternates, large scoring parameters)
-// Both write what the trace kernel reads through BtView / LastRow / LastCol; a batch may mix them pair by pair.
+//   k_sw_fill_strip  the 32-bit cell with a strip loop around the sweep, for references of 2049 .. 32 767 bases (MGX_SW_LONG_REF)
+// All write what the trace kernel reads through BtView / LastRow / LastCol; a batch may mix them pair by pair.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +61,9 @@ constexpr int kOpMatch = 0, kOpInsert = 1, kOpDelete = 2, kInsertExt = 4, kDelet
 constexpr int kMinCutoff = -100000000;           // MATRIX_MIN_CUTOFF, smithwaterman_common.h:73
 constexpr int kLowInit = INT32_MIN / 2;          // LOW_INIT_VALUE, smithwaterman_common.h:74
 constexpr int kMaxRef = 2048;                    // 64 lanes x 32 rows
+constexpr int kStripRpl = 32;                    // k_sw_fill_strip (MGX_SW_LONG_REF): rows per lane ...
+constexpr int kStripRows = 64 * kStripRpl;       // ... and per strip
+constexpr int kMaxLen = 32767;                   // the reference's lengths are int16_t (IntelSmithWaterman.cc:77)
 
 struct SwJob {
     u64 off1, off2;      // into the uploaded ref / alt bytes
@@ -69,12 +73,14 @@ struct SwJob {
     u32 len1, len2, rpl, strategy, out_index;
     u32 g;               // bits 0-7: lanes per pair (32 or 64) | kJobI16 | kJobHalf
     u64 lr_off;          // 16-bit fill: the last lane's H values per swept position (back-trace arena, bytes)
+                         // strip fill: the pair's boundary array, (H, F) of a strip's bottom row per column
     u64 lc_off;          // 16-bit fill: every lane's packed H values at the pair's last swept position
     int32_t low16;       // 16-bit fill: this pair's stand-in for LOW_INIT_VALUE
     u32 pad_;
 };
 constexpr u32 kJobI16 = 0x200u;     // k_sw_fill16: packed 16-bit scores, two pairs per lane group, back-trace nibbles
 constexpr u32 kJobHalf = 0x400u;    // k_sw_fill16: this pair is the high half of its lane group
+constexpr u32 kJobStrip = 0x800u;   // k_sw_fill_strip: the reference is cut into strips of kStripRows rows, written one after another
 constexpr u32 kNoOutput = 0xFFFFFFFFu;   // out_index of a filler job (a 16-bit class is padded to whole wavefronts)
 
 struct SwResult { int32_t score, max_i, max_j, offset, n_elems; };
@@ -185,6 +191,127 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
     if (lane < n_lanes) {
 #pragma unroll
         for (int k = 0; k < RPL; ++k) if (r0 + k + 1 <= n_own) edge_swp[r0 + k + 1] = hl[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// References of more than kMaxRef bases (MGX_SW_LONG_REF): k_sw_fill<64, 32>'s cell body with a strip loop around the sweep, the
+// pattern of pairhmm_fwd_strip.  One pair per wavefront; the reference is cut into strips of 64 lanes x 32 rows, the
+// LAST strip takes the remainder, and the strips sweep the alternate (staged in LDS once) one after the other.
+//   * Hand-off.  Three things cross a seam: H and F (the vertical gap) of the strip's bottom row per column, and the diagonal
+//     H(r, j - 1), which is the H handed over one column earlier (diag_in, as between two lanes).  E belongs to a row.  The lane
+//     that owns a strip's bottom row (lane 63: every strip but the last is full) stores (H, F) of column j into the pair's
+//     boundary array bnd[j]; in the next strip lane 0 takes them where the one-strip kernel takes the matrix boundary.  In the
+//     first strip the same registers hold that boundary's closed form, so the sweep does not tell the strips apart.
+//   * One array per pair is enough.  Lane 0 is at column j in step j; lane 63 overwrites bnd[j] in step j + 63.  The boundary is
+//     not loaded per step (a dependent global load on every step's path) but 64 columns at a time, one per lane, one block of 64
+//     steps ahead: the block that starts at step t0 first loads columns t0 + 64 .. t0 + 127, which are overwritten from step
+//     t0 + 127 on, and hands column t0 + x to lane 0 in step t0 + x with a v_readlane.  Loads and stores are one wavefront's, in
+//     program order, and every value loaded sits in a register before its slot is stored to; a whole strip lies between a store
+//     and the load that wants it, with a fence at the seam.  The sweep proper holds no load, so it never waits for its own
+//     back-trace stores.  No workgroup waits for another.
+//   * Back-trace: strip s is written in the (step, lane, row-in-lane) layout at s * strip_bt_stride(ncol) (BtView adds the term).
+//   * H(i, ncol) is stored at the end of every strip, H(nrow, j) by the lane that owns row nrow in the last strip.
+__host__ __device__ constexpr u64 strip_bt_stride(u64 ncol) { return (ncol + 64) * 64 * bt_slot(kStripRpl); }   // steps + 1 = ncol + 64
+
+__global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ jobs, u32 n_jobs, const u8* __restrict__ s1, const u8* __restrict__ s2,
+                                                      u8* bt, int32_t* __restrict__ sc, SwParams P) {
+    extern __shared__ u8 sh_strip[];
+    constexpr int RPL = kStripRpl, SLOT = bt_slot(RPL);
+    if (blockIdx.x >= n_jobs) return;
+    const int lane = threadIdx.x;
+    const SwJob J = jobs[blockIdx.x];
+    const int nrow = (int)J.len1, ncol = (int)J.len2;
+    const bool indel = J.strategy == MGX_SW_INDEL || J.strategy == MGX_SW_LEADING_INDEL;
+    auto edge = [&](int x) { return indel ? P.open + (x - 1) * P.extend : 0; };      // H(x, 0) = H(0, x), x >= 1 (PairWiseSW.h:243-253)
+    const u8* own = s1 + J.off1;
+    const u8* swp = s2 + J.off2;
+    int32_t* const last_row = sc + J.sc_off;          // H(nrow, j), j = 1 .. ncol
+    int32_t* const last_col = last_row + ncol + 1;    // H(i, ncol), i = 1 .. nrow
+    int2* const bnd = reinterpret_cast<int2*>(bt + J.lr_off);     // [ncol + 1], entry 0 unused
+    for (int x = lane; x < ncol; x += 64) sh_strip[x] = swp[x];
+    __syncthreads();
+    const int n_strips = (nrow + kStripRows - 1) / kStripRows;
+    for (int s = 0; s < n_strips; ++s) {
+        const int base = s * kStripRows;              // rows base + 1 .. base + n_own
+        const int n_own = min(nrow - base, kStripRows);
+        const bool last = s == n_strips - 1;
+        const int r0 = base + lane * RPL;
+        int sa[RPL], hl[RPL], gs[RPL];
+#pragma unroll
+        for (int k = 0; k < RPL; ++k) {
+            const int i = r0 + k + 1;
+            const int b = (int)own[min(i, nrow) - 1];                 // every lane loads (a guarded load waits for its own round trip, 32 in a row)
+            sa[k] = i <= nrow ? b : 256;                              // padding rows never match and feed nothing beyond them
+            hl[k] = edge(i);                                          // H(i, 0)
+            gs[k] = kLowInit;                                         // E(i, 0)
+        }
+        int diag_in = r0 == 0 ? 0 : edge(r0);                         // H(r0, 0); lane 0 of a later strip: the row above the seam
+        const int n_lanes = (n_own + RPL - 1) / RPL, steps = ncol + n_lanes - 1;
+        const int lane_last = (n_own - 1) / RPL, k_last = (n_own - 1) % RPL;
+        u8* const btp = bt + J.bt_off + (u64)s * strip_bt_stride((u64)ncol);
+        // the row above this strip, 64 columns per block of 64 steps: lane l holds column (block start) + l
+        auto fetch = [&](int j, int& h, int& f) {
+            h = 0; f = kLowInit;
+            if (s == 0) { h = edge(j); }
+            else if (j <= ncol) { const int2 v = bnd[j]; h = v.x; f = v.y; }
+        };
+        int cur_h = 0, cur_f = kLowInit, nxt_h, nxt_f;
+        fetch(1 + lane, nxt_h, nxt_f);
+        int send_h = 0, send_g = kLowInit;
+        for (int t0 = 1; t0 <= steps; t0 += 64) {     // blocks of 64 steps: the sweep proper has no load to wait for
+            cur_h = nxt_h; cur_f = nxt_f;
+            fetch(t0 + 64 + lane, nxt_h, nxt_f);
+            const int t1 = min(t0 + 63, steps);
+            for (int t = t0; t <= t1; ++t) {
+                const int rh = __shfl_up(send_h, 1, 64), rg = __shfl_up(send_g, 1, 64);
+                const int bh = __builtin_amdgcn_readlane(cur_h, t - t0), bf = __builtin_amdgcn_readlane(cur_f, t - t0);
+                const int j = t - lane;
+                if (j >= 1 && j <= ncol && lane < n_lanes) {
+                    int up_h = lane == 0 ? bh : rh, up_g = lane == 0 ? bf : rg;      // H(r0, j), F(r0, j)
+                    int diag = diag_in;                                               // H(r0, j - 1)
+                    diag_in = up_h;
+                    const int c2 = (int)sh_strip[j - 1];
+                    u32 packed[RPL / 4];
+#pragma unroll
+                    for (int q = 0; q < RPL / 4; ++q) packed[q] = 0;
+#pragma unroll
+                    for (int k = 0; k < RPL; ++k) {                                   // the cell of k_sw_fill
+                        const int open_s = hl[k] + P.open, ext_s = gs[k] + P.extend;
+                        const int gs_new = max(open_s, ext_s);
+                        const int open_c = up_h + P.open, ext_c = up_g + P.extend;
+                        const int gc_new = max(ext_c, open_c);
+                        int ext = 0;
+                        if (!(open_s > ext_s)) ext |= kInsertExt;
+                        if (!(open_c > ext_c)) ext |= kDeleteExt;
+                        int h = max(diag + (sa[k] == c2 ? P.match : P.mismatch), kMinCutoff);
+                        int op = kOpMatch;
+                        if (gs_new > h) { op = kOpInsert; h = gs_new; }
+                        if (gc_new > h) { op = kOpDelete; h = gc_new; }
+                        diag = hl[k]; hl[k] = h; gs[k] = gs_new; up_h = h; up_g = gc_new;
+                        packed[k >> 2] |= (u32)(op | ext) << ((k & 3) * 8);
+                    }
+                    send_h = up_h; send_g = up_g;
+                    if (lane == lane_last) {
+                        if (!last) bnd[j] = make_int2(up_h, up_g);        // lane 63, row base + kStripRows
+                        else {
+                            int v = hl[0];
+#pragma unroll
+                            for (int k = 1; k < RPL; ++k) if (k == k_last) v = hl[k];
+                            last_row[j] = v;
+                        }
+                    }
+                    u8* dst = btp + ((size_t)t * 64 + lane) * SLOT;
+#pragma unroll
+                    for (int q = 0; q < SLOT / 4; ++q) reinterpret_cast<u32*>(dst)[q] = packed[q];
+                }
+            }
+        }
+        if (lane < n_lanes) {
+#pragma unroll
+            for (int k = 0; k < RPL; ++k) if (r0 + k + 1 <= nrow) last_col[r0 + k + 1] = hl[k];
+        }
+        __threadfence();                              // this strip's boundary stores before the next strip's loads
     }
 }
 
@@ -354,13 +481,18 @@ __global__ __launch_bounds__(64) void k_sw_fill16(const SwJob* __restrict__ jobs
 // what the trace kernel reads of a pair's back-trace, whichever kernel filled it: the byte of the 32-bit form (op | INSERT_EXT | DELETE_EXT)
 struct BtView {
     const u8* p; int rpl, g, slot; bool i16; int half;
+    u64 strip_stride;          // bytes from one strip to the next; 0: the pair is one strip (every class but k_sw_fill_strip's)
     __device__ BtView(const SwJob& J, const u8* bt) : p(bt + J.bt_off), rpl((int)J.rpl), g((int)(J.g & 0xFFu)),
-                                                     i16((J.g & kJobI16) != 0), half((J.g & kJobHalf) ? 1 : 0) {
+                                                     i16((J.g & kJobI16) != 0), half((J.g & kJobHalf) ? 1 : 0),
+                                                     strip_stride((J.g & kJobStrip) ? strip_bt_stride(J.len2) : 0) {
         slot = i16 ? bt_slot16(rpl) : bt_slot(rpl);
     }
     __device__ int cell(int i, int j) const {
-        const int l = (i - 1) / rpl, k = (i - 1) - l * rpl;          // the lane that owns row i and its row in the lane
-        const size_t base = ((size_t)(j + l) * g + l) * slot;
+        int r = i - 1;
+        size_t at = 0;
+        if (strip_stride) { const int s = r / kStripRows; r -= s * kStripRows; at = (size_t)s * strip_stride; }
+        const int l = r / rpl, k = r - l * rpl;                      // the lane that owns row i and its row in the lane
+        const size_t base = at + ((size_t)(j + l) * g + l) * slot;
         if (!i16) return p[base + k];
         const int by = p[base + (k >> 2) * 4 + half * 2 + ((k & 3) >> 1)];
         const int nib = (k & 1) ? by >> 4 : by & 15;
@@ -585,6 +717,13 @@ inline u64 bt_bytes(u64 len1, u64 len2, const Shape& sh) {
     const u64 n_lanes = (len1 + sh.rpl - 1) / sh.rpl, steps = len2 + n_lanes - 1;
     return ((steps + 1) * sh.g * bt_slot(sh.rpl) + 15) & ~15ull;
 }
+// the strip form: full strips at strip_bt_stride, then the last one with the lanes it has; and the boundary array
+inline u64 n_strips_of(u64 len1) { return (len1 + kStripRows - 1) / kStripRows; }
+inline u64 bt_bytes_strip(u64 len1, u64 len2) {
+    const u64 full = n_strips_of(len1) - 1;
+    return full * strip_bt_stride(len2) + bt_bytes(len1 - full * kStripRows, len2, Shape{64, kStripRpl});
+}
+inline u64 bnd_bytes_strip(u64 len2) { return ((len2 + 1) * 8 + 15) & ~15ull; }
 
 int itoa_len(int v) { const int neg = v < 0; if (neg) v = -v; int d = 0; while (v > 0) { v /= 10; ++d; } return d + neg; }
 
@@ -626,6 +765,7 @@ struct DevBuf {
 
 struct mgx_sw {
     int device = 0;
+    unsigned flags = 0;           // MGX_SW_*
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     DevBuf<u8> d_s1, d_s2, d_bt;
@@ -705,7 +845,14 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         Pre& J = pre[q];
         J.len1 = (u32)(in->ref_off[p + 1] - in->ref_off[p]); J.len2 = (u32)(in->alt_off[p + 1] - in->alt_off[p]);
         J.low16 = 0;
-        if (knobs.use16 && rule.admits(J.len1, J.len2, &J.low16)) {
+        if (J.len1 > (u32)kMaxRef) {
+            // the strip class (align_impl let the pair in: MGX_SW_LONG_REF): 64 lanes and 32-bit scores whatever MGX_SW_PAIRED and the
+            // 16-bit rule say.  It is launched LAST (the highest class key).  Launches of one stream run one after the other, so
+            // the place decides nothing about the time; last leaves the jobs of today's classes where a context without the flag
+            // puts them, arena offsets included.
+            J.rpl = (uint8_t)kStripRpl; J.g = 64; J.cls = 255;
+            c->stats.n_pairs_strip++; c->stats.n_strips += n_strips_of(J.len1);
+        } else if (knobs.use16 && rule.admits(J.len1, J.len2, &J.low16)) {
             const Shape sh = shape16_for((int)J.len1, paired);
             J.rpl = (uint8_t)sh.rpl; J.g = (uint8_t)sh.g;
             J.cls = (uint16_t)((sh.g == 64 ? 64 : 0) + (32 - sh.rpl));                                  // < 128
@@ -737,7 +884,7 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         J.len1 = R.len1; J.len2 = R.len2; J.rpl = R.rpl; J.strategy = in->strategy[p]; J.out_index = q;
         J.sc_off = J.off1 + J.off2 + 2ull * q; J.el_off = 2 * J.sc_off;
         J.low16 = R.low16;
-        J.g = (u32)R.g | (R.cls < 128 ? kJobI16 : 0u);
+        J.g = (u32)R.g | (R.cls < 128 ? kJobI16 : 0u) | (R.cls == 255 ? kJobStrip : 0u);
         return J;
     };
     u64 bt = 0;
@@ -776,7 +923,10 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
         } else {
             SwJob J = make_job(q0);
             const Shape sh{(int)(J.g & 0xFFu), (int)J.rpl};
-            J.bt_off = bt; bt += bt_bytes(J.len1, J.len2, sh);
+            if (J.g & kJobStrip) {
+                J.bt_off = bt; bt += bt_bytes_strip(J.len1, J.len2);
+                J.lr_off = bt; bt += bnd_bytes_strip(J.len2);
+            } else { J.bt_off = bt; bt += bt_bytes(J.len1, J.len2, sh); }
             jobs[n_jobs++] = J;
             ++x;
         }
@@ -816,6 +966,12 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
             continue;
         }
         while (b < n_jobs && jobs[b].rpl == jobs[a].rpl && jobs[b].g == jobs[a].g) { m2 = std::max(m2, jobs[b].len2); ++b; }
+        if (jobs[a].g & kJobStrip) {
+            hipLaunchKernelGGL(k_sw_fill_strip, dim3(b - a), dim3(64), (m2 + 15) & ~15u, s, dj, b - a, c->d_s1.p, c->d_s2.p, c->d_bt.p, c->d_sc.p, P);
+            c->stats.n_launches++;
+            a = b;
+            continue;
+        }
 #define MGX_SW_CASE(g, r) case r: launch_fill<g, r>(c, dj, b - a, m2, P); break;
         if ((jobs[a].g & 0xFFu) == 32) {
             switch (jobs[a].rpl) {
@@ -929,7 +1085,6 @@ int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in
 extern "C" {
 
 int mgx_sw_create(int device, unsigned flags, mgx_sw_t** out) {
-    (void)flags;
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
     int n_dev = 0;
@@ -943,6 +1098,7 @@ int mgx_sw_create(int device, unsigned flags, mgx_sw_t** out) {
     std::unique_ptr<mgx_sw> c(new (std::nothrow) mgx_sw);
     if (!c) return -ENOMEM;
     c->device = device;
+    c->flags = flags;
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
     *out = c.release();
@@ -968,12 +1124,13 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
     if (in->n_pairs == 0) return 0;
     if (!in->ref_off || !in->alt_off || !in->ref || !in->alt || !in->strategy) { set_error("NULL array in input"); return -EINVAL; }
     if (in->n_pairs > 0x7FFFFFFFull) { set_error("more than 2^31-1 pairs in one batch"); return -E2BIG; }
+    const int max_ref = (c->flags & MGX_SW_LONG_REF) ? kMaxLen : kMaxRef;
     for (u64 p = 0; p < in->n_pairs; ++p) {
         if (in->ref_off[p + 1] < in->ref_off[p] || in->alt_off[p + 1] < in->alt_off[p]) { set_error("pair %llu: offsets decrease", (unsigned long long)p); return -EINVAL; }
         const u64 l1 = in->ref_off[p + 1] - in->ref_off[p], l2 = in->alt_off[p + 1] - in->alt_off[p];
         if (l1 == 0 || l2 == 0) { set_error("pair %llu: empty sequence", (unsigned long long)p); return -EINVAL; }
-        if (l1 > (u64)kMaxRef) { set_error("pair %llu: reference of %llu bases (limit %d)", (unsigned long long)p, (unsigned long long)l1, kMaxRef); return -E2BIG; }
-        if (l2 > 32767) { set_error("pair %llu: alternate of %llu bases (limit 32767)", (unsigned long long)p, (unsigned long long)l2); return -E2BIG; }
+        if (l1 > (u64)max_ref) { set_error("pair %llu: reference of %llu bases (limit %d)", (unsigned long long)p, (unsigned long long)l1, max_ref); return -E2BIG; }
+        if (l2 > (u64)kMaxLen) { set_error("pair %llu: alternate of %llu bases (limit 32767)", (unsigned long long)p, (unsigned long long)l2); return -E2BIG; }
         const int st = in->strategy[p];
         if (st < MGX_SW_SOFTCLIP || st > MGX_SW_IGNORE) { set_error("pair %llu: unknown overhang strategy %d", (unsigned long long)p, st); return -EINVAL; }
     }
@@ -988,7 +1145,9 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
             // (the paired form and the 16-bit form are smaller) plus the 16-bit kernel's edge rows
             const u64 l1 = in->ref_off[hi + 1] - in->ref_off[hi], l2 = in->alt_off[hi + 1] - in->alt_off[hi];
             const u64 rows = (l1 + 63) / 64, slot = rows <= 8 ? ((rows + 3) & ~3ull) : rows <= 16 ? 16 : 32;
-            const u64 need = (l2 + 64 + 1) * 64 * slot + 8 * (l2 + 1) * ((l1 + 31) / 32 * 3 / 2 + 2) + 8 * (l1 + 64) + 64;
+            // (a reference of more than kMaxRef bases has one shape only: its strips and its boundary array, to the byte)
+            const u64 need = l1 > (u64)kMaxRef ? bt_bytes_strip(l1, l2) + bnd_bytes_strip(l2)
+                                               : (l2 + 64 + 1) * 64 * slot + 8 * (l2 + 1) * ((l1 + 31) / 32 * 3 / 2 + 2) + 8 * (l1 + 64) + 64;
             if (hi > lo && bt + need > limit) break;
             bt += need; ++hi;
         }

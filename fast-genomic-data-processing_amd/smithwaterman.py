@@ -13,6 +13,7 @@ from . import native
 SOFTCLIP, INDEL, LEADING_INDEL, IGNORE = 9, 10, 11, 12
 STANDARD_NGS = (25, -50, -110, -6)       # smithwaterman/SmithWatermanAligner.cpp:9
 ORIGINAL_DEFAULT = (3, -1, -4, -3)       # smithwaterman/SmithWatermanAligner.cpp:8
+LONG_REF = 1                             # MGX_SW_LONG_REF: SmithWatermanEngine(device, LONG_REF) takes references of up to 32 767 bases
 
 
 def _ptr(a):

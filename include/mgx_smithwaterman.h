@@ -21,8 +21,10 @@
  * code in the caller.
  *
  * Sequences are compared byte by byte (no base decoding), lengths are 1..2048 for ref and 1..32767
- * for alt; longer references are rejected with -E2BIG.  All functions return 0 (mgx_sw_align: the
- * alignment offset) or a negative errno-style code with mgx_last_error() set.  No CPU fallback.
+ * for alt; longer references are rejected with -E2BIG.  A context created with MGX_SW_LONG_REF takes
+ * 1..32767 for both, the range of the reference's int16_t lengths (IntelSmithWaterman.cc:77), and
+ * rejects 32768 and more with -E2BIG.  All functions return 0 (mgx_sw_align: the alignment offset)
+ * or a negative errno-style code with mgx_last_error() set.  No CPU fallback.
  */
 #ifndef MGX_SMITHWATERMAN_H
 #define MGX_SMITHWATERMAN_H
@@ -63,7 +65,13 @@ typedef struct mgx_sw_stats {
     float ms_fill, ms_trace;         /* HIP events around the matrix fill and the back-trace kernels */
     uint64_t backtrace_bytes;        /* back-trace arena written by the fill kernels */
     uint64_t n_pairs_i16;            /* pairs whose scores provably fit 16 bits: filled two to a lane group with packed arithmetic */
+    uint64_t n_pairs_strip;          /* pairs with a reference of more than 2048 bases: filled strip by strip (MGX_SW_LONG_REF) */
+    uint64_t n_strips;               /* the sum of their strip counts (2048 reference bases to a strip) */
 } mgx_sw_stats_t;
+
+/* flags of mgx_sw_create.  MGX_SW_LONG_REF: references of up to 32767 bases (without it: 2048).  Pairs of up to 2048
+ * reference bases are treated exactly as by a context without the flag. */
+#define MGX_SW_LONG_REF 1u
 
 int mgx_sw_create(int device, unsigned flags, mgx_sw_t** out);
 void mgx_sw_destroy(mgx_sw_t* ctx);

@@ -1,5 +1,5 @@
 """Randomised soak: loops over seeded random inputs for the paths and compares the device with the oracles
-(bit-exact for sort/dedup and Smith-Waterman, 1e-5 for PairHMM, zlib's inflate for the BGZF blocks).  usage: fuzz.py [seconds] [seed0] [kind 0..6: that path only; 3 = Smith-Waterman]"""
+(bit-exact for sort/dedup and Smith-Waterman, 1e-5 for PairHMM, zlib's inflate for the BGZF blocks).  usage: fuzz.py [seconds] [seed0] [kind 0..6: that path only; 3 = Smith-Waterman, one batch in four on a MGX_SW_LONG_REF context with references of up to 6 000 bases]"""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,6 +12,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1
 ph, sd, sw = pkg.PairHMMEngine(0), pkg.SortDedupEngine(0), pkg.SmithWatermanEngine(0)
+sw_long = pkg.SmithWatermanEngine(0, pkg.smithwaterman.LONG_REF)
 oph, osd, osw = PairHMMOracle(_ensure_oracle()), SortDedupOracle(), SmithWatermanOracle()
 rng = np.random.default_rng(seed0)
 t0 = time.time(); it = 0; fails = 0; counts = {"sort": 0, "pairhmm": 0, "regions": 0, "sw": 0, "shards": 0, "queue": 0, "bgzf": 0}
@@ -117,12 +118,16 @@ while time.time() - t0 < budget:
         else:
             os.environ["MGX_SW_PAIRED"] = str(rng.choice(["0", "1"]))
             os.environ["MGX_SW_I16"] = str(rng.choice(["0", "1", "1", "1"]))          # the packed 16-bit fill (round 3) or the 32-bit one for every pair
-            w = synth.gen_sw_pairs(int(rng.integers(1, 400)), seed, ref_range=(1, int(rng.choice([60, 300, 700, 2048]))), alt_range=(1, int(rng.choice([40, 200, 600]))))
+            long_ref = rng.integers(0, 4) == 0         # a context with MGX_SW_LONG_REF and references of up to 6 000 bases: the strip fill among the other classes
+            if long_ref:
+                w = synth.gen_sw_pairs(int(rng.integers(1, 40)), seed, ref_range=(1, 6000), alt_range=(1, int(rng.choice([40, 200, 600]))))
+            else:
+                w = synth.gen_sw_pairs(int(rng.integers(1, 400)), seed, ref_range=(1, int(rng.choice([60, 300, 700, 2048]))), alt_range=(1, int(rng.choice([40, 200, 600]))))
             params = tuple(int(x) for x in rng.choice([[25, -50, -110, -6], [3, -1, -4, -3], [1, -2, -3, -1], [10, -15, -30, -5]]))
             if rng.integers(0, 3) == 0:         # anything: the 16-bit admission rule decides pair by pair
                 params = (int(rng.integers(1, 80)), -int(rng.integers(0, 160)), -int(rng.integers(0, 300)), -int(rng.integers(0, 50)))
             wc, wo, ws = osw.batch(w, params)
-            gc, go, gs = sw.align_batch(w["ref_off"], w["ref"], w["alt_off"], w["alt"], w["strategy"], params, want_score=True)
+            gc, go, gs = (sw_long if long_ref else sw).align_batch(w["ref_off"], w["ref"], w["alt_off"], w["alt"], w["strategy"], params, want_score=True)
             ok = gc == wc and np.array_equal(go, wo) and np.array_equal(gs, ws)
             counts["sw"] += 1
     except Exception as e:            # noqa: BLE001
