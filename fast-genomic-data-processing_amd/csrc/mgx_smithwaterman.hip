@@ -15,7 +15,7 @@
 // Back-trace bytes are laid out by (step, lane, row-in-lane) so that one step of a wavefront stores
 // 64 * RPL consecutive bytes; the trace kernel converts (i, j) back to that index (BtView).
 //
-// Two fill kernels (round 3):
+// Three fill kernels:
 //   k_sw_fill16   packed 16-bit scores, two pairs per lane group, the four decisions of a cell taken from the sign bits of four
 //                 packed differences, back-trace nibbles, all row classes in one launch -- for every pair whose scores provably fit
 //                 16 bits (I16Rule; the realignment workload of Mutect2 always does): 12.6 instructions per cell
@@ -41,7 +41,7 @@
 
 #include "../../include/mgx_smithwaterman.h"
 #include "mgx_common.h"
-#include "sw_i16_rule.h"
+#include "sw_layout.h"
 
 using mgx::set_error;
 
@@ -53,41 +53,45 @@ using mgx::set_error;
 
 namespace {
 
-typedef uint8_t u8;
-typedef uint32_t u32;
-typedef uint64_t u64;
+using namespace mgx_sw_layout;     // SwJob, shapes, region sizes, chunks, build_jobs, next_launch: sw_layout.h (CPU-tested)
 
 constexpr int kOpMatch = 0, kOpInsert = 1, kOpDelete = 2, kInsertExt = 4, kDeleteExt = 8;
 constexpr int kMinCutoff = -100000000;           // MATRIX_MIN_CUTOFF, smithwaterman_common.h:73
 constexpr int kLowInit = INT32_MIN / 2;          // LOW_INIT_VALUE, smithwaterman_common.h:74
-constexpr int kMaxRef = 2048;                    // 64 lanes x 32 rows
-constexpr int kStripRpl = 32;                    // k_sw_fill_strip (MGX_SW_LONG_REF): rows per lane ...
-constexpr int kStripRows = 64 * kStripRpl;       // ... and per strip
-constexpr int kMaxLen = 32767;                   // the reference's lengths are int16_t (IntelSmithWaterman.cc:77)
-
-struct SwJob {
-    u64 off1, off2;      // into the uploaded ref / alt bytes
-    u64 bt_off;          // back-trace arena, bytes
-    u64 sc_off;          // score arena (int32): last_row[ncol + 1] then last_col[nrow + 1]
-    u64 el_off;          // element arena (int16): 2 * (len1 + len2 + 2)
-    u32 len1, len2, rpl, strategy, out_index;
-    u32 g;               // bits 0-7: lanes per pair (32 or 64) | kJobI16 | kJobHalf
-    u64 lr_off;          // 16-bit fill: the last lane's H values per swept position (back-trace arena, bytes)
-                         // strip fill: the pair's boundary array, (H, F) of a strip's bottom row per column
-    u64 lc_off;          // 16-bit fill: every lane's packed H values at the pair's last swept position
-    int32_t low16;       // 16-bit fill: this pair's stand-in for LOW_INIT_VALUE
-    u32 pad_;
-};
-constexpr u32 kJobI16 = 0x200u;     // k_sw_fill16: packed 16-bit scores, two pairs per lane group, back-trace nibbles
-constexpr u32 kJobHalf = 0x400u;    // k_sw_fill16: this pair is the high half of its lane group
-constexpr u32 kJobStrip = 0x800u;   // k_sw_fill_strip: the reference is cut into strips of kStripRows rows, written one after another
-constexpr u32 kNoOutput = 0xFFFFFFFFu;   // out_index of a filler job (a 16-bit class is padded to whole wavefronts)
 
 struct SwResult { int32_t score, max_i, max_j, offset, n_elems; };
-// back-trace bytes of one lane and step: RPL of them, in a slot of whole 32-bit words from three positions per lane up (a 5-, 6- or
-// 7-byte slot would be stored byte by byte)
-__host__ __device__ constexpr int bt_slot(int rpl) { return rpl <= 2 ? rpl : (rpl + 3) & ~3; }
 struct SwParams { int match, mismatch, open, extend; };
+
+// ---- what the fill kernels share.  H(x, 0) = H(0, x), x >= 1: the matrix boundary per overhang strategy (PairWiseSW.h:243-253)
+__device__ __forceinline__ int sw_edge(bool indel, const SwParams& P, int x) { return indel ? P.open + (x - 1) * P.extend : 0; }
+// One 32-bit cell (PairWiseSW.h:31-66), row k of a lane: hl / gs are the row's H and its gap state along the sweep, diag / up_h / up_g
+// come from the row above and leave as this row's for the row below; the back-trace byte goes into the lane's packed word.
+__device__ __forceinline__ void sw_cell(const SwParams& P, int sa, int c2, int k, int& hl, int& gs, int& diag, int& up_h, int& up_g, u32& packed) {
+    const int open_s = hl + P.open, ext_s = gs + P.extend;               // along the sweep
+    const int ee = max(open_s, ext_s);
+    const int open_c = up_h + P.open, ext_c = up_g + P.extend;           // along the lanes' own positions
+    const int ff = max(ext_c, open_c);
+    // E is the horizontal gap (INSERT), F the vertical one (DELETE); ties prefer the extension
+    int ext = 0;
+    if (!(open_s > ext_s)) ext |= kInsertExt;
+    if (!(open_c > ext_c)) ext |= kDeleteExt;
+    int h = max(diag + (sa == c2 ? P.match : P.mismatch), kMinCutoff);   // H prefers the diagonal, then E, then F
+    int op = kOpMatch;
+    if (ee > h) { op = kOpInsert; h = ee; }
+    if (ff > h) { op = kOpDelete; h = ff; }
+    diag = hl; hl = h; gs = ee; up_h = h; up_g = ff;
+    packed |= (u32)(op | ext) << ((k & 3) * 8);
+}
+// Two pieces that take a lane's register arrays are macros over the kernel's RPL: a function is optimised on its own before it is inlined,
+// with the array as a pointer, and the pick became ONE indexed load, which moved hl to scratch memory (the store merely came out otherwise).
+// H of the pair's last row, which is row k_last of the lane that owns it: a select per row, the registers are not indexable
+#define MGX_SW_LAST_ROW_H(dst, hl, k_last) \
+    do { int v_ = hl[0]; _Pragma("unroll") for (int k_ = 1; k_ < RPL; ++k_) if (k_ == k_last) v_ = hl[k_]; dst = v_; } while (0)
+// the back-trace bytes of one lane and step into their slot (bt_slot)
+#define MGX_SW_STORE_BT(dst_, packed) do { u8* dst = (dst_); \
+    if constexpr (RPL == 1) dst[0] = (u8)packed[0]; \
+    else if constexpr (RPL == 2) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)packed[0]; \
+    else { _Pragma("unroll") for (int q = 0; q < bt_slot(RPL) / 4; ++q) reinterpret_cast<u32*>(dst)[q] = packed[q]; } } while (0)
 
 // G lanes per pair (two pairs share a wavefront when G = 32), RPL rows per lane.  Back-trace byte:
 // bits 0-1 op, bit 2 INSERT_EXT, bit 3 DELETE_EXT (PairWiseSW.h:31-66).  (Storing the length of the
@@ -122,10 +126,10 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
     for (int k = 0; k < RPL; ++k) {
         const int i = r0 + k + 1;
         sa[k] = (live && i <= n_own) ? (int)own[i - 1] : 256;     // padding positions never match and feed nothing beyond them
-        hl[k] = indel ? P.open + (i - 1) * P.extend : 0;          // H(i, 0) / H(0, j), PairWiseSW.h:243-253
+        hl[k] = sw_edge(indel, P, i);                             // H(i, 0) / H(0, j)
         gs[k] = kLowInit;                                         // E(i, 0) / F(0, j)
     }
-    int diag_in = r0 == 0 ? 0 : (indel ? P.open + (r0 - 1) * P.extend : 0);   // H(r0, 0) / H(0, r0)
+    int diag_in = sw_edge(r0 != 0 && indel, P, r0);               // H(r0, 0) / H(0, r0); H(0, 0) = 0
     const int n_lanes = live ? (n_own + RPL - 1) / RPL : 0;
     const int steps = live ? n_swp + n_lanes - 1 : 0;
     int steps_w = steps;                              // the wavefront walks to its longest pair
@@ -142,48 +146,18 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
         if (j >= 1 && j <= n_swp && lane < n_lanes) {
             int up_h, up_g, diag;
             if (lane == 0) {
-                up_h = indel ? P.open + (j - 1) * P.extend : 0;                           // H(0, j) / H(i, 0)
-                up_g = kLowInit;                                                          // F(0, j) / E(i, 0)
-                diag = j == 1 ? 0 : (indel ? P.open + (j - 2) * P.extend : 0);            // the boundary one position back, H(0,0) = 0
+                up_h = sw_edge(indel, P, j);                         // H(0, j) / H(i, 0)
+                up_g = kLowInit;                                     // F(0, j) / E(i, 0)
+                diag = sw_edge(j != 1 && indel, P, j - 1);           // the boundary one position back; H(0, 0) = 0
             } else { up_h = rh; up_g = rg; diag = diag_in; }
             diag_in = up_h;                                          // this step's neighbour value is the next step's diagonal
             const int c2 = (int)sh_b[j - 1];
-            u32 packed[(RPL + 3) / 4];
+            u32 packed[(RPL + 3) / 4] = {};
 #pragma unroll
-            for (int q = 0; q < (RPL + 3) / 4; ++q) packed[q] = 0;
-#pragma unroll
-            for (int k = 0; k < RPL; ++k) {
-                const int open_s = hl[k] + P.open, ext_s = gs[k] + P.extend;         // along the sweep
-                const int gs_new = max(open_s, ext_s);
-                const int open_c = up_h + P.open, ext_c = up_g + P.extend;           // along the lanes' own positions
-                const int gc_new = max(ext_c, open_c);
-                // E is the horizontal gap (INSERT), F the vertical one (DELETE); ties prefer the extension
-                int ext = 0;
-                if (!(open_s > ext_s)) ext |= kInsertExt;
-                if (!(open_c > ext_c)) ext |= kDeleteExt;
-                const int ee = gs_new, ff = gc_new;
-                int h = max(diag + (sa[k] == c2 ? P.match : P.mismatch), kMinCutoff);
-                int op = kOpMatch;
-                if (ee > h) { op = kOpInsert; h = ee; }
-                if (ff > h) { op = kOpDelete; h = ff; }
-                diag = hl[k]; hl[k] = h; gs[k] = gs_new; up_h = h; up_g = gc_new;
-                packed[k >> 2] |= (u32)(op | ext) << ((k & 3) * 8);
-            }
+            for (int k = 0; k < RPL; ++k) sw_cell(P, sa[k], c2, k, hl[k], gs[k], diag, up_h, up_g, packed[k >> 2]);
             send_h = up_h; send_g = up_g;
-            if (lane == lane_last) {
-                int v = hl[0];
-#pragma unroll
-                for (int k = 1; k < RPL; ++k) if (k == k_last) v = hl[k];
-                edge_own[j] = v;
-            }
-            constexpr int SLOT = bt_slot(RPL);
-            u8* dst = btp + ((size_t)t * G + lane) * SLOT;
-            if constexpr (RPL == 1) dst[0] = (u8)packed[0];
-            else if constexpr (RPL == 2) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)packed[0];
-            else {
-#pragma unroll
-                for (int q = 0; q < SLOT / 4; ++q) reinterpret_cast<u32*>(dst)[q] = packed[q];
-            }
+            if (lane == lane_last) MGX_SW_LAST_ROW_H(edge_own[j], hl, k_last);
+            MGX_SW_STORE_BT(btp + ((size_t)t * G + lane) * bt_slot(RPL), packed);
         }
     }
     // a lane's last active step is the last sweep position: its registers now hold H there (kept out of the loop --
@@ -212,8 +186,6 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
 //     back-trace stores.  No workgroup waits for another.
 //   * Back-trace: strip s is written in the (step, lane, row-in-lane) layout at s * strip_bt_stride(ncol) (BtView adds the term).
 //   * H(i, ncol) is stored at the end of every strip, H(nrow, j) by the lane that owns row nrow in the last strip.
-__host__ __device__ constexpr u64 strip_bt_stride(u64 ncol) { return (ncol + 64) * 64 * bt_slot(kStripRpl); }   // steps + 1 = ncol + 64
-
 __global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ jobs, u32 n_jobs, const u8* __restrict__ s1, const u8* __restrict__ s2,
                                                       u8* bt, int32_t* __restrict__ sc, SwParams P) {
     extern __shared__ u8 sh_strip[];
@@ -223,7 +195,6 @@ __global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ 
     const SwJob J = jobs[blockIdx.x];
     const int nrow = (int)J.len1, ncol = (int)J.len2;
     const bool indel = J.strategy == MGX_SW_INDEL || J.strategy == MGX_SW_LEADING_INDEL;
-    auto edge = [&](int x) { return indel ? P.open + (x - 1) * P.extend : 0; };      // H(x, 0) = H(0, x), x >= 1 (PairWiseSW.h:243-253)
     const u8* own = s1 + J.off1;
     const u8* swp = s2 + J.off2;
     int32_t* const last_row = sc + J.sc_off;          // H(nrow, j), j = 1 .. ncol
@@ -243,17 +214,17 @@ __global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ 
             const int i = r0 + k + 1;
             const int b = (int)own[min(i, nrow) - 1];                 // every lane loads (a guarded load waits for its own round trip, 32 in a row)
             sa[k] = i <= nrow ? b : 256;                              // padding rows never match and feed nothing beyond them
-            hl[k] = edge(i);                                          // H(i, 0)
+            hl[k] = sw_edge(indel, P, i);                             // H(i, 0)
             gs[k] = kLowInit;                                         // E(i, 0)
         }
-        int diag_in = r0 == 0 ? 0 : edge(r0);                         // H(r0, 0); lane 0 of a later strip: the row above the seam
+        int diag_in = sw_edge(r0 != 0 && indel, P, r0);               // H(r0, 0), H(0, 0) = 0; lane 0 of a later strip: the row above the seam
         const int n_lanes = (n_own + RPL - 1) / RPL, steps = ncol + n_lanes - 1;
         const int lane_last = (n_own - 1) / RPL, k_last = (n_own - 1) % RPL;
         u8* const btp = bt + J.bt_off + (u64)s * strip_bt_stride((u64)ncol);
         // the row above this strip, 64 columns per block of 64 steps: lane l holds column (block start) + l
         auto fetch = [&](int j, int& h, int& f) {
             h = 0; f = kLowInit;
-            if (s == 0) { h = edge(j); }
+            if (s == 0) { h = sw_edge(indel, P, j); }
             else if (j <= ncol) { const int2 v = bnd[j]; h = v.x; f = v.y; }
         };
         int cur_h = 0, cur_f = kLowInit, nxt_h, nxt_f;
@@ -272,38 +243,15 @@ __global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ 
                     int diag = diag_in;                                               // H(r0, j - 1)
                     diag_in = up_h;
                     const int c2 = (int)sh_strip[j - 1];
-                    u32 packed[RPL / 4];
+                    u32 packed[RPL / 4] = {};
 #pragma unroll
-                    for (int q = 0; q < RPL / 4; ++q) packed[q] = 0;
-#pragma unroll
-                    for (int k = 0; k < RPL; ++k) {                                   // the cell of k_sw_fill
-                        const int open_s = hl[k] + P.open, ext_s = gs[k] + P.extend;
-                        const int gs_new = max(open_s, ext_s);
-                        const int open_c = up_h + P.open, ext_c = up_g + P.extend;
-                        const int gc_new = max(ext_c, open_c);
-                        int ext = 0;
-                        if (!(open_s > ext_s)) ext |= kInsertExt;
-                        if (!(open_c > ext_c)) ext |= kDeleteExt;
-                        int h = max(diag + (sa[k] == c2 ? P.match : P.mismatch), kMinCutoff);
-                        int op = kOpMatch;
-                        if (gs_new > h) { op = kOpInsert; h = gs_new; }
-                        if (gc_new > h) { op = kOpDelete; h = gc_new; }
-                        diag = hl[k]; hl[k] = h; gs[k] = gs_new; up_h = h; up_g = gc_new;
-                        packed[k >> 2] |= (u32)(op | ext) << ((k & 3) * 8);
-                    }
+                    for (int k = 0; k < RPL; ++k) sw_cell(P, sa[k], c2, k, hl[k], gs[k], diag, up_h, up_g, packed[k >> 2]);
                     send_h = up_h; send_g = up_g;
                     if (lane == lane_last) {
                         if (!last) bnd[j] = make_int2(up_h, up_g);        // lane 63, row base + kStripRows
-                        else {
-                            int v = hl[0];
-#pragma unroll
-                            for (int k = 1; k < RPL; ++k) if (k == k_last) v = hl[k];
-                            last_row[j] = v;
-                        }
+                        else MGX_SW_LAST_ROW_H(last_row[j], hl, k_last);
                     }
-                    u8* dst = btp + ((size_t)t * 64 + lane) * SLOT;
-#pragma unroll
-                    for (int q = 0; q < SLOT / 4; ++q) reinterpret_cast<u32*>(dst)[q] = packed[q];
+                    MGX_SW_STORE_BT(btp + ((size_t)t * 64 + lane) * SLOT, packed);
                 }
             }
         }
@@ -342,7 +290,6 @@ __device__ __forceinline__ u32 bfi(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b
 // 1 in every half whose bases differ (as a compare it becomes two 16-bit compares, two selects and a v_perm)
 __device__ __forceinline__ u32 pk_min_u16(u32 a, u32 b) { u32 r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ s16x2 pk_mad(u32 a, s16x2 b, s16x2 c) { u32 r; asm("v_pk_mad_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(bits(b)), "v"(bits(c))); return s16(r); }
-__host__ __device__ constexpr int bt_slot16(int rpl) { return 4 * ((rpl + 3) / 4); }
 
 template <int G, int RPL>
 __device__ __forceinline__ void sw_fill16_body(const SwJob& JA, const SwJob& JB, const int lane, const u8* __restrict__ s1, const u8* __restrict__ s2,
@@ -367,10 +314,10 @@ __device__ __forceinline__ void sw_fill16_body(const SwJob& JA, const SwJob& JB,
     for (int k = 0; k < RPL; ++k) {
         const int i = r0 + k + 1;
         sa[k] = (i <= nrowA ? (u32)rowsA[i - 1] : 256u) | ((i <= nrowB ? (u32)rowsB[i - 1] : 256u) << 16);
-        hl[k] = pk2(indelA ? P.open + (i - 1) * P.extend : 0, indelB ? P.open + (i - 1) * P.extend : 0);     // H(i, 0)
-        gs[k] = vlow;                                                                                       // E(i, 0)
+        hl[k] = pk2(sw_edge(indelA, P, i), sw_edge(indelB, P, i));                                 // H(i, 0)
+        gs[k] = vlow;                                                                             // E(i, 0)
     }
-    s16x2 diag_in = r0 == 0 ? pk2(0, 0) : pk2(indelA ? P.open + (r0 - 1) * P.extend : 0, indelB ? P.open + (r0 - 1) * P.extend : 0);   // H(r0, 0)
+    s16x2 diag_in = r0 == 0 ? pk2(0, 0) : pk2(sw_edge(indelA, P, r0), sw_edge(indelB, P, r0));    // H(r0, 0)
     s16x2 bnd = pk2(indelA ? P.open : 0, indelB ? P.open : 0);                      // lane 0: H(0, j), starting at j = 1
     const s16x2 bstep = pk2(indelA ? P.extend : 0, indelB ? P.extend : 0);
     const int n_lanes = max((nrowA + RPL - 1) / RPL, (nrowB + RPL - 1) / RPL);
@@ -425,26 +372,13 @@ __device__ __forceinline__ void sw_fill16_body(const SwJob& JA, const SwJob& JB,
             u32* dst = reinterpret_cast<u32*>(btp + ((size_t)t * G + lane) * (4 * W));
 #pragma unroll
             for (int q = 0; q < W; ++q) dst[q] = word[q];
-            if (lane == lane_lastA) {
-                u32* d = lrA + (size_t)j * RPL;
-#pragma unroll
-                for (int k = 0; k < RPL; ++k) d[k] = bits(hl[k]);
-            }
-            if (lr_apart && lane == lane_lastB) {
-                u32* d = lrB + (size_t)j * RPL;
-#pragma unroll
-                for (int k = 0; k < RPL; ++k) d[k] = bits(hl[k]);
-            }
-            if (j == ncolA) {
-                u32* d = lcA + r0;
-#pragma unroll
-                for (int k = 0; k < RPL; ++k) d[k] = bits(hl[k]);
-            }
-            if (lc_apart && j == ncolB) {
-                u32* d = lcB + r0;
-#pragma unroll
-                for (int k = 0; k < RPL; ++k) d[k] = bits(hl[k]);
-            }
+            // the lane's RPL packed H values (both halves) where LastRow / LastCol read them; a macro for the reason MGX_SW_LAST_ROW_H is one
+#define MGX_SW16_STORE_ROWS(dst) do { u32* d_ = (dst); _Pragma("unroll") for (int k = 0; k < RPL; ++k) d_[k] = bits(hl[k]); } while (0)
+            if (lane == lane_lastA) MGX_SW16_STORE_ROWS(lrA + (size_t)j * RPL);
+            if (lr_apart && lane == lane_lastB) MGX_SW16_STORE_ROWS(lrB + (size_t)j * RPL);
+            if (j == ncolA) MGX_SW16_STORE_ROWS(lcA + r0);
+            if (lc_apart && j == ncolB) MGX_SW16_STORE_ROWS(lcB + r0);
+#undef MGX_SW16_STORE_ROWS
         }
     }
 }
@@ -673,21 +607,6 @@ __global__ __launch_bounds__(256) void k_sw_gather(const GatherRef* __restrict__
     }
 }
 
-// lanes per pair and reference positions per lane
-struct Shape { int g, rpl; };
-// The lanes own the reference and sweep the alternate.  Up to 256 reference positions two pairs share a wavefront
-// (32 lanes x 1..8) whenever the batch is large enough to fill the device that way; otherwise, and beyond, one pair per
-// wavefront (64 lanes x 1..32) so that every SIMD still has several wavefronts to hide the dependent integer chain of a
-// step behind.
-Shape shape_for(int len1, bool paired) {
-    if (paired) {
-        static const int cls32[] = {1, 2, 3, 4, 5, 6, 7, 8, 12, 16};
-        for (int r : cls32) if (len1 <= 32 * r) return Shape{32, r};
-    }
-    static const int cls64[] = {1, 2, 3, 4, 5, 6, 8, 16, 32};
-    for (int r : cls64) if (len1 <= 64 * r) return Shape{64, r};
-    return Shape{0, 0};
-}
 // knobs of one call, read from the environment once (tests and A/B runs set them between calls)
 struct Knobs {
     int paired = -1;          // MGX_SW_PAIRED: force two lane groups per wavefront (1) or one (0)
@@ -699,31 +618,7 @@ struct Knobs {
         if (const char* e = getenv("MGX_SW_ARENA_LIMIT")) { const long long v = atoll(e); if (v > 0) arena = (u64)v; }
     }
 };
-constexpr u32 kPairedFrom = 8192;             // pairs in a chunk from which two lane groups share a wavefront (round 2: 32768)
-
-// ---- the packed 16-bit fill (k_sw_fill16): shapes and admission
-Shape shape16_for(int len1, bool paired) {
-    static const int cls[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 20, 24, 32};
-    if (paired) for (int r : cls) if (len1 <= 32 * r) return Shape{32, r};
-    for (int r : cls) if (len1 <= 64 * r) return Shape{64, r};
-    return Shape{0, 0};
-}
-// admission: I16Rule (sw_i16_rule.h), bounds on every value and difference from the lengths and the scoring parameters
-using mgx_sw16::I16Rule;
-inline u64 bt_bytes16(u64 steps_max, const Shape& sh) { return ((steps_max + 1) * sh.g * bt_slot16(sh.rpl) + 15) & ~15ull; }
-inline u64 lr_bytes16(u64 n_swp, const Shape& sh) { return ((n_swp + 1) * sh.rpl * 4 + 15) & ~15ull; }
 constexpr int kCompactElems = 16;             // merged CIGAR elements copied back per pair without a second look
-inline u64 bt_bytes(u64 len1, u64 len2, const Shape& sh) {
-    const u64 n_lanes = (len1 + sh.rpl - 1) / sh.rpl, steps = len2 + n_lanes - 1;
-    return ((steps + 1) * sh.g * bt_slot(sh.rpl) + 15) & ~15ull;
-}
-// the strip form: full strips at strip_bt_stride, then the last one with the lanes it has; and the boundary array
-inline u64 n_strips_of(u64 len1) { return (len1 + kStripRows - 1) / kStripRows; }
-inline u64 bt_bytes_strip(u64 len1, u64 len2) {
-    const u64 full = n_strips_of(len1) - 1;
-    return full * strip_bt_stride(len2) + bt_bytes(len1 - full * kStripRows, len2, Shape{64, kStripRpl});
-}
-inline u64 bnd_bytes_strip(u64 len2) { return ((len2 + 1) * 8 + 15) & ~15ull; }
 
 int itoa_len(int v) { const int neg = v < 0; if (neg) v = -v; int d = 0; while (v > 0) { v /= 10; ++d; } return d + neg; }
 
@@ -760,6 +655,19 @@ struct DevBuf {
     }
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
+// pinned host memory; `want` >= n is what a growing buffer asks for (each user keeps its growth factor)
+struct PinBuf {
+    char* p = nullptr; size_t cap = 0;
+    int reserve(size_t n, size_t want) {
+        if (n <= cap) return 0;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
+        cap = want;
+        return 0;
+    }
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+};
 
 }  // namespace
 
@@ -775,10 +683,8 @@ struct mgx_sw {
     DevBuf<GatherRef> d_gather;
     DevBuf<SwResult> d_res;
     mgx_sw_stats_t stats{};
-    void* pin = nullptr;          // pinned staging for the uploads (a pageable source is copied at a few GB/s)
-    size_t pin_cap = 0;
-    void* pin_out = nullptr;      // pinned landing area of the results (a pageable target goes through the runtime's own staging)
-    size_t pin_out_cap = 0;
+    PinBuf pin;                   // pinned staging for the uploads (a pageable source is copied at a few GB/s)
+    PinBuf pin_out;               // pinned landing area of the results (a pageable target goes through the runtime's own staging)
 };
 
 namespace {
@@ -786,296 +692,205 @@ namespace {
 // chunks the call took 50-60 ms (a 20 ms stall follows every very large chunk), with 4 GB chunks 29 ms.
 constexpr u64 kArenaLimit = 4ull << 30;
 
-template <int G, int RPL>
-void launch_fill(mgx_sw* c, const SwJob* jobs, u32 n, u32 max_swept, SwParams P) {
-    constexpr u32 GPW = 64 / G;
-    const u32 stride = (max_swept + 15) & ~15u;
-    hipLaunchKernelGGL((k_sw_fill<G, RPL>), dim3((n + GPW - 1) / GPW), dim3(64), GPW * stride, c->stream, jobs, n, c->d_s1.p, c->d_s2.p,
-                       c->d_bt.p, c->d_sc.p, stride, P);
+// pairs [lo, hi) of the input, already validated
+struct Chunk {
+    u64 lo, hi; u32 n;
+    u64 base1, base2, n1, n2;     // the first byte and the byte count of the chunk's references / alternates in the caller's arrays
+    size_t a1, a2;                // the byte counts rounded up to 256: pinned memory holds [references | alternates | jobs]
+    Chunk(const mgx_sw_input_t* in, u64 lo_, u64 hi_) : lo(lo_), hi(hi_), n((u32)(hi_ - lo_)), base1(in->ref_off[lo_]), base2(in->alt_off[lo_]),
+        n1(in->ref_off[hi_] - base1), n2(in->alt_off[hi_] - base2), a1((n1 + 255) & ~(size_t)255), a2((n2 + 255) & ~(size_t)255) {}
+};
+struct Outputs { int32_t* offset; char* cigar; u32 stride; int32_t* score; int cap_override; };      // the caller's, indexed by input pair
+Lens pair_lens(const mgx_sw_input_t* in, u64 p) { return mgx_sw_layout::pair_lens(in->ref_off, in->alt_off, p); }
+struct Stager {                   // the helper threads of stage_sequences: upload_jobs joins them, and so does every way out before it
+    std::thread t[2]; std::atomic<int> err{0}; bool apart = false;
+    void join() { for (auto& x : t) if (x.joinable()) x.join(); }
+    ~Stager() { join(); }
+};
+// The sequences travel to pinned memory, on helper threads when there is a megabyte of them, while the caller lays out the jobs.
+int stage_sequences(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, Stager& st) {
+    const size_t total = k.a1 + k.a2 + max_jobs(k.n) * sizeof(SwJob);
+    int rc;
+    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = c->d_s1.reserve(k.n1 + 16)) || (rc = c->d_s2.reserve(k.n2 + 16))) return rc;
+    char* const pin = c->pin.p;
+    st.apart = k.n1 + k.n2 >= (1u << 20);
+    if (!st.apart) { memcpy(pin, in->ref + k.base1, k.n1); memcpy(pin + k.a1, in->alt + k.base2, k.n2); return 0; }
+    // each helper also queues its array's upload as soon as it is staged: the copies cross the link while the jobs are laid out
+    auto stage = [c, &st](u8* dst, char* via, const u8* src, size_t bytes) {
+        memcpy(via, src, bytes);
+        if (hipSetDevice(c->device) != hipSuccess || hipMemcpyAsync(dst, via, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) st.err = 1;
+    };
+    st.t[0] = std::thread(stage, c->d_s1.p, pin, in->ref + k.base1, (size_t)k.n1);
+    st.t[1] = std::thread(stage, c->d_s2.p, pin + k.a1, in->alt + k.base2, (size_t)k.n2);
+    return 0;
+}
+// the jobs in launch order and their places in the arenas (sw_layout.h), built in place behind the sequences in pinned memory
+Layout lay_out(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const Chunk& k, const Knobs& knobs, SwJob* jobs) {
+    const bool paired = knobs.paired >= 0 ? knobs.paired != 0 : k.n >= kPairedFrom;
+    const mgx_sw16::I16Rule rule(params->match, params->mismatch, params->gap_open, params->gap_extend);
+    const Layout L = build_jobs(in->ref_off, in->alt_off, in->strategy, k.lo, k.hi, paired, knobs.use16, rule, jobs);
+    c->stats.n_pairs_i16 += L.n_pairs_i16; c->stats.n_pairs_strip += L.n_pairs_strip; c->stats.n_strips += L.n_strips;
+    return L;
 }
 
-// pairs [lo, hi) of the input, already validated
-int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, u64 lo, u64 hi, const Knobs& knobs,
-              int32_t* out_offset, char* out_cigar, u32 stride, int32_t* out_score, int cap_override) {
-    const u32 n = (u32)(hi - lo);
-    static const bool prof = [] { const char* e = getenv("MGX_SW_PROF"); return e && atoi(e) != 0; }();      // host stage times on stderr
-    double tp[6] = {0};
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    tp[0] = now();
-    const bool paired = knobs.paired >= 0 ? knobs.paired != 0 : n >= kPairedFrom;
-    const SwParams P{params->match, params->mismatch, params->gap_open, params->gap_extend};
-    const I16Rule rule(P.match, P.mismatch, P.open, P.extend);
-    const u64 base1 = in->ref_off[lo], base2 = in->alt_off[lo];
-    const u64 n1 = in->ref_off[hi] - base1, n2 = in->alt_off[hi] - base2;
-    // the sequences travel to pinned memory on a helper thread while this one lays out the jobs
-    const u32 max_jobs = n + 256;                        // fillers: at most 3 per 16-bit class
-    const size_t a1 = (n1 + 255) & ~(size_t)255, a2 = (n2 + 255) & ~(size_t)255, total = a1 + a2 + max_jobs * sizeof(SwJob);
-    if (total > c->pin_cap) {
-        if (c->pin) (void)hipHostFree(c->pin);
-        c->pin = nullptr; c->pin_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->pin, total + total / 4, hipHostMallocDefault));
-        c->pin_cap = total + total / 4;
-    }
-    char* const pin = static_cast<char*>(c->pin);
-    int rc;
-    if ((rc = c->d_s1.reserve(n1 + 16)) || (rc = c->d_s2.reserve(n2 + 16))) return rc;
+int upload_jobs(mgx_sw* c, const Chunk& k, Stager& st, const Layout& L, const SwJob* jobs) {
     hipStream_t s = c->stream;
-    std::thread stager[2];
-    struct Joiner { std::thread* t; ~Joiner() { for (int k = 0; k < 2; ++k) if (t[k].joinable()) t[k].join(); } } joiner{stager};
-    std::atomic<int> stage_err{0};
-    const bool staged_apart = n1 + n2 >= (1u << 20);
-    if (staged_apart) {
-        // each helper also queues its array's upload as soon as it is staged: the copies cross the link while the jobs are laid out
-        const int dev = c->device;
-        u8* const d1 = c->d_s1.p; u8* const d2 = c->d_s2.p;
-        stager[0] = std::thread([=, &stage_err] { memcpy(pin, in->ref + base1, n1);
-                                                  if (hipSetDevice(dev) != hipSuccess || hipMemcpyAsync(d1, pin, n1, hipMemcpyHostToDevice, s) != hipSuccess) stage_err = 1; });
-        stager[1] = std::thread([=, &stage_err] { memcpy(pin + a1, in->alt + base2, n2);
-                                                  if (hipSetDevice(dev) != hipSuccess || hipMemcpyAsync(d2, pin + a1, n2, hipMemcpyHostToDevice, s) != hipSuccess) stage_err = 1; });
-    } else { memcpy(pin, in->ref + base1, n1); memcpy(pin + a1, in->alt + base2, n2); }
-    // Per pair in input order: class and admission.  Then launch order: the packed 16-bit classes first (32 lanes, then 64; most
-    // rows per lane first), the 32-bit classes after them, longest alternate first inside a class (the two pairs of a lane group
-    // and the groups of a wavefront finish together; a launch drains on its cheapest jobs).  Two counting sorts: a comparison sort
-    // of 10^5 jobs costs more than their alignments.  The score and element arenas are laid out in input order: pair q's score
-    // rows start at (bases before it) + 2 q.
-    struct Pre { u32 len1, len2; int32_t low16; uint16_t cls; uint8_t rpl, g; };
-    std::vector<Pre> pre(n);
-    for (u32 q = 0; q < n; ++q) {
-        const u64 p = lo + q;
-        Pre& J = pre[q];
-        J.len1 = (u32)(in->ref_off[p + 1] - in->ref_off[p]); J.len2 = (u32)(in->alt_off[p + 1] - in->alt_off[p]);
-        J.low16 = 0;
-        if (J.len1 > (u32)kMaxRef) {
-            // the strip class (align_impl let the pair in: MGX_SW_LONG_REF): 64 lanes and 32-bit scores whatever MGX_SW_PAIRED and the
-            // 16-bit rule say.  It is launched LAST (the highest class key).  Launches of one stream run one after the other, so
-            // the place decides nothing about the time; last leaves the jobs of today's classes where a context without the flag
-            // puts them, arena offsets included.
-            J.rpl = (uint8_t)kStripRpl; J.g = 64; J.cls = 255;
-            c->stats.n_pairs_strip++; c->stats.n_strips += n_strips_of(J.len1);
-        } else if (knobs.use16 && rule.admits(J.len1, J.len2, &J.low16)) {
-            const Shape sh = shape16_for((int)J.len1, paired);
-            J.rpl = (uint8_t)sh.rpl; J.g = (uint8_t)sh.g;
-            J.cls = (uint16_t)((sh.g == 64 ? 64 : 0) + (32 - sh.rpl));                                  // < 128
-            c->stats.n_pairs_i16++;
-        } else {
-            const Shape sh = shape_for((int)J.len1, paired);
-            J.rpl = (uint8_t)sh.rpl; J.g = (uint8_t)sh.g;
-            J.cls = (uint16_t)(128 + (sh.g == 64 ? 64 : 0) + sh.rpl);                                   // < 256
-        }
+    const u64 scn = k.n1 + k.n2 + 2ull * k.n, eln = 2 * scn;
+    int rc;
+    if ((rc = c->d_bt.reserve(L.bt_bytes + 16)) || (rc = c->d_jobs.reserve(L.n_jobs)) || (rc = c->d_sc.reserve(scn)) || (rc = c->d_el.reserve(eln)) ||
+        (rc = c->d_res.reserve(k.n)) || (rc = c->d_cel.reserve((size_t)k.n * 2 * kCompactElems))) return rc;
+    st.join();                                    // the helpers have queued the sequences: the jobs follow them on the stream
+    if (st.err.load()) { (void)hipGetLastError(); set_error("upload of the sequences failed"); return -EIO; }
+    if (!st.apart) {
+        HIP_TRY(hipMemcpyAsync(c->d_s1.p, c->pin.p, k.n1, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->d_s2.p, c->pin.p + k.a1, k.n2, hipMemcpyHostToDevice, s));
     }
-    std::vector<u32> order(n);
-    {
-        std::vector<u32> cnt(32770, 0), tmp(n);
-        for (u32 q = 0; q < n; ++q) cnt[32767 - pre[q].len2 + 1]++;
-        for (u32 k = 0; k < 32768; ++k) cnt[k + 1] += cnt[k];
-        for (u32 q = 0; q < n; ++q) tmp[cnt[32767 - pre[q].len2]++] = q;
-        u32 c2[257] = {0};
-        for (u32 q = 0; q < n; ++q) c2[pre[q].cls + 1]++;
-        for (int k = 0; k < 256; ++k) c2[k + 1] += c2[k];
-        for (u32 x = 0; x < n; ++x) order[c2[pre[tmp[x]].cls]++] = tmp[x];
-    }
-    SwJob* const jobs = reinterpret_cast<SwJob*>(pin + a1 + a2);             // built in place, in launch order
-    u32 n_jobs = 0;
-    auto make_job = [&](u32 q) {
-        const u64 p = lo + q;
-        const Pre& R = pre[q];
-        SwJob J{};
-        J.off1 = in->ref_off[p] - base1; J.off2 = in->alt_off[p] - base2;
-        J.len1 = R.len1; J.len2 = R.len2; J.rpl = R.rpl; J.strategy = in->strategy[p]; J.out_index = q;
-        J.sc_off = J.off1 + J.off2 + 2ull * q; J.el_off = 2 * J.sc_off;
-        J.low16 = R.low16;
-        J.g = (u32)R.g | (R.cls < 128 ? kJobI16 : 0u) | (R.cls == 255 ? kJobStrip : 0u);
-        return J;
-    };
-    u64 bt = 0;
-    for (u32 x = 0; x < n;) {
-        const u32 q0 = order[x];
-        if (pre[q0].cls < 128) {
-            // one class: lane groups of two pairs, whole wavefronts
-            const u32 cl = pre[q0].cls;
-            const Shape sh{(int)pre[q0].g, (int)pre[q0].rpl};
-            const u32 per_wave = 2 * (64 / sh.g);
-            u32 y = x;
-            while (y < n && pre[order[y]].cls == cl) ++y;
-            for (u32 z = x; z < y; z += 2) {
-                SwJob A = make_job(order[z]), B{};
-                if (z + 1 < y) B = make_job(order[z + 1]);
-                else { B.out_index = kNoOutput; B.rpl = A.rpl; B.g = A.g; }
-                B.g |= kJobHalf;
-                auto lanes = [&](const SwJob& j) { return (u64)(j.len1 + sh.rpl - 1) / sh.rpl; };
-                const u64 n_swp = std::max(A.len2, B.len2), steps = n_swp + std::max(lanes(A), lanes(B)) - 1;
-                A.bt_off = B.bt_off = bt; bt += bt_bytes16(steps, sh);
-                A.lr_off = bt; bt += lr_bytes16(n_swp, sh);
-                const bool same_lane = B.len1 > 0 && (A.len1 - 1) / sh.rpl == (B.len1 - 1) / sh.rpl;
-                if (same_lane || B.len1 == 0) B.lr_off = A.lr_off;
-                else { B.lr_off = bt; bt += lr_bytes16(n_swp, sh); }
-                const u64 lc_bytes = (std::max(lanes(A), lanes(B)) * sh.rpl * 4 + 15) & ~15ull;
-                A.lc_off = bt; bt += lc_bytes;
-                if (B.len2 == A.len2 || B.len1 == 0) B.lc_off = A.lc_off;
-                else { B.lc_off = bt; bt += lc_bytes; }
-                jobs[n_jobs++] = A; jobs[n_jobs++] = B;
-            }
-            while (n_jobs % per_wave) {                      // filler groups up to the wavefront boundary
-                SwJob F{}; F.out_index = kNoOutput; F.rpl = (u32)sh.rpl; F.g = (u32)sh.g | kJobI16 | (n_jobs % 2 ? kJobHalf : 0u);
-                jobs[n_jobs++] = F;
-            }
-            x = y;
-        } else {
-            SwJob J = make_job(q0);
-            const Shape sh{(int)(J.g & 0xFFu), (int)J.rpl};
-            if (J.g & kJobStrip) {
-                J.bt_off = bt; bt += bt_bytes_strip(J.len1, J.len2);
-                J.lr_off = bt; bt += bnd_bytes_strip(J.len2);
-            } else { J.bt_off = bt; bt += bt_bytes(J.len1, J.len2, sh); }
-            jobs[n_jobs++] = J;
-            ++x;
-        }
-    }
-    const u64 scn = n1 + n2 + 2ull * n, eln = 2 * scn;
-    tp[1] = now();
-    if ((rc = c->d_bt.reserve(bt + 16)) || (rc = c->d_jobs.reserve(n_jobs)) ||
-        (rc = c->d_sc.reserve(scn)) || (rc = c->d_el.reserve(eln)) || (rc = c->d_res.reserve(n)) ||
-        (rc = c->d_cel.reserve((size_t)n * 2 * kCompactElems))) return rc;
-    for (auto& t : stager) if (t.joinable()) t.join();
-    if (stage_err.load()) { (void)hipGetLastError(); set_error("upload of the sequences failed"); return -EIO; }
-    if (!staged_apart) {
-        HIP_TRY(hipMemcpyAsync(c->d_s1.p, pin, n1, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->d_s2.p, pin + a1, n2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, n_jobs * sizeof(SwJob), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, L.n_jobs * sizeof(SwJob), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(c->ev[0], s));
-    tp[2] = now();
-    for (u32 a = 0; a < n_jobs;) {
-        u32 b = a;
-        u32 m2 = 0;
+    return 0;
+}
+// one launch per next_launch (sw_layout.h); `jobs` is the host copy, the kernels read the device's
+void launch_fills(mgx_sw* c, const SwJob* jobs, u32 n_jobs, const SwParams& P) {
+    hipStream_t s = c->stream;
+#define MGX_SW_ARGS dj, m, c->d_s1.p, c->d_s2.p, c->d_bt.p, c->d_sc.p
+#define MGX_SW16_LAUNCH(G_, BIG_) hipLaunchKernelGGL((k_sw_fill16<G_, BIG_>), dim3(m / (2 * gpw)), dim3(64), gpw * stride * sizeof(u32), s, MGX_SW_ARGS, stride, P)
+#define MGX_SW_FILL(G_, R_) hipLaunchKernelGGL((k_sw_fill<G_, R_>), dim3((m + 64 / G_ - 1) / (64 / G_)), dim3(64), 64 / G_ * stride, s, MGX_SW_ARGS, stride, P)
+#define MGX_SW_CASE(g, r) case r: MGX_SW_FILL(g, r); break;
+    for (u32 a = 0; a < n_jobs; c->stats.n_launches++) {
+        const Launch l = next_launch(jobs, n_jobs, a);
         const SwJob* dj = c->d_jobs.p + a;
-        if (jobs[a].g & kJobI16) {
-            // every class of one lane-group width in one launch (two when classes of more than 16 rows per lane are present)
-            const u32 g = jobs[a].g & 0xFFu, gpw = 64 / g;
+        const u32 m = l.end - a, g = jobs[a].g & 0xFFu, gpw = 64 / g, stride = (l.max_len2 + 15) & ~15u;      // stride: the LDS stage of one lane group
+        if (jobs[a].g & kJobI16) {                        // m / (2 * gpw) whole wavefronts: build_jobs pads every class with fillers
             const bool big = jobs[a].rpl > 16;
-            while (b < n_jobs && (jobs[b].g & kJobI16) && (jobs[b].g & 0xFFu) == g && (jobs[b].rpl > 16) == big) { m2 = std::max(m2, jobs[b].len2); ++b; }
-            const u32 stride = (m2 + 15) & ~15u;
-            const dim3 grid((b - a) / (2 * gpw));
-            const size_t lds = gpw * stride * sizeof(u32);
-#define MGX_SW16_LAUNCH(G_, BIG_) hipLaunchKernelGGL((k_sw_fill16<G_, BIG_>), grid, dim3(64), lds, s, dj, b - a, c->d_s1.p, c->d_s2.p, c->d_bt.p, c->d_sc.p, stride, P)
             if (g == 32) { if (big) MGX_SW16_LAUNCH(32, true); else MGX_SW16_LAUNCH(32, false); }
             else         { if (big) MGX_SW16_LAUNCH(64, true); else MGX_SW16_LAUNCH(64, false); }
-#undef MGX_SW16_LAUNCH
-            c->stats.n_launches++;
-            a = b;
-            continue;
-        }
-        while (b < n_jobs && jobs[b].rpl == jobs[a].rpl && jobs[b].g == jobs[a].g) { m2 = std::max(m2, jobs[b].len2); ++b; }
-        if (jobs[a].g & kJobStrip) {
-            hipLaunchKernelGGL(k_sw_fill_strip, dim3(b - a), dim3(64), (m2 + 15) & ~15u, s, dj, b - a, c->d_s1.p, c->d_s2.p, c->d_bt.p, c->d_sc.p, P);
-            c->stats.n_launches++;
-            a = b;
-            continue;
-        }
-#define MGX_SW_CASE(g, r) case r: launch_fill<g, r>(c, dj, b - a, m2, P); break;
-        if ((jobs[a].g & 0xFFu) == 32) {
+        } else if (jobs[a].g & kJobStrip) {
+            hipLaunchKernelGGL(k_sw_fill_strip, dim3(m), dim3(64), stride, s, MGX_SW_ARGS, P);
+        } else if (g == 32) {
             switch (jobs[a].rpl) {
                 MGX_SW_CASE(32, 1) MGX_SW_CASE(32, 2) MGX_SW_CASE(32, 3) MGX_SW_CASE(32, 4) MGX_SW_CASE(32, 5) MGX_SW_CASE(32, 6) MGX_SW_CASE(32, 7)
                 MGX_SW_CASE(32, 8) MGX_SW_CASE(32, 12)
-                default: launch_fill<32, 16>(c, dj, b - a, m2, P); break;
+                default: MGX_SW_FILL(32, 16); break;
             }
         } else {
             switch (jobs[a].rpl) {
                 MGX_SW_CASE(64, 1) MGX_SW_CASE(64, 2) MGX_SW_CASE(64, 3) MGX_SW_CASE(64, 4) MGX_SW_CASE(64, 5) MGX_SW_CASE(64, 6) MGX_SW_CASE(64, 8)
                 MGX_SW_CASE(64, 16)
-                default: launch_fill<64, 32>(c, dj, b - a, m2, P); break;
+                default: MGX_SW_FILL(64, 32); break;
             }
         }
-#undef MGX_SW_CASE
-        c->stats.n_launches++;
-        a = b;
+        a = l.end;
     }
+#undef MGX_SW_CASE
+#undef MGX_SW_FILL
+#undef MGX_SW16_LAUNCH
+#undef MGX_SW_ARGS
+}
+
+int launch_trace(mgx_sw* c, u32 n_jobs) {
+    hipStream_t s = c->stream;
     HIP_TRY(hipEventRecord(c->ev[1], s));
-    hipLaunchKernelGGL(k_sw_trace_wave, dim3(n_jobs), dim3(64), 0, s, c->d_jobs.p, n_jobs, c->d_bt.p, c->d_sc.p, c->d_el.p, c->d_res.p,
-                       c->d_cel.p, kCompactElems);
+    hipLaunchKernelGGL(k_sw_trace_wave, dim3(n_jobs), dim3(64), 0, s, c->d_jobs.p, n_jobs, c->d_bt.p, c->d_sc.p, c->d_el.p, c->d_res.p, c->d_cel.p, kCompactElems);
     HIP_TRY(hipEventRecord(c->ev[2], s));
     HIP_TRY(hipGetLastError());
-    tp[3] = now();
-    const size_t res_bytes = ((size_t)n * sizeof(SwResult) + 63) & ~(size_t)63, cel_bytes = (size_t)n * 2 * kCompactElems * sizeof(int16_t);
-    if (res_bytes + cel_bytes > c->pin_out_cap) {
-        if (c->pin_out) (void)hipHostFree(c->pin_out);
-        c->pin_out = nullptr; c->pin_out_cap = 0;
-        const size_t want = (res_bytes + cel_bytes) * 5 / 4;
-        HIP_TRY(hipHostMalloc(&c->pin_out, want, hipHostMallocDefault));
-        c->pin_out_cap = want;
-    }
-    SwResult* const res = static_cast<SwResult*>(c->pin_out);
-    int16_t* const cel = reinterpret_cast<int16_t*>(static_cast<char*>(c->pin_out) + res_bytes);
-    HIP_TRY(hipMemcpyAsync(res, c->d_res.p, n * sizeof(SwResult), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+// what came back: a fixed record per pair, and the element lists longer than kCompactElems, densely (pair q's starts at big_at[q])
+struct Fetched { const SwResult* res; const int16_t* cel; std::vector<u64> big_at; std::unique_ptr<int16_t[]> big; };
+int fetch_results(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, u64 bt_bytes, Fetched& f) {
+    hipStream_t s = c->stream;
+    const size_t res_bytes = ((size_t)k.n * sizeof(SwResult) + 63) & ~(size_t)63, cel_bytes = (size_t)k.n * 2 * kCompactElems * sizeof(int16_t);
+    int rc;
+    if ((rc = c->pin_out.reserve(res_bytes + cel_bytes, (res_bytes + cel_bytes) * 5 / 4))) return rc;
+    SwResult* const res = reinterpret_cast<SwResult*>(c->pin_out.p);
+    int16_t* const cel = reinterpret_cast<int16_t*>(c->pin_out.p + res_bytes);
+    HIP_TRY(hipMemcpyAsync(res, c->d_res.p, k.n * sizeof(SwResult), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(cel, c->d_cel.p, cel_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // alignments with more elements than the fixed record holds: one gather launch, one more download
     std::vector<GatherRef> big_refs;
-    std::vector<u64> big_at(n, ~0ull);
-    {
-        u64 eo2 = 0, dense_n = 0;
-        for (u32 q = 0; q < n; ++q) {
-            const u64 p = lo + q;
-            if (res[q].n_elems > kCompactElems) {
-                big_at[q] = dense_n;
-                big_refs.push_back(GatherRef{eo2, dense_n, (u32)(2 * res[q].n_elems), 0});
-                dense_n += 2ull * res[q].n_elems;
-            }
-            eo2 += 2 * ((in->ref_off[p + 1] - in->ref_off[p]) + (in->alt_off[p + 1] - in->alt_off[p]) + 2);
+    f.big_at.assign(k.n, ~0ull);
+    u64 eo2 = 0, dense_n = 0;
+    for (u32 q = 0; q < k.n; ++q) {
+        if (res[q].n_elems > kCompactElems) {
+            f.big_at[q] = dense_n;
+            big_refs.push_back(GatherRef{eo2, dense_n, (u32)(2 * res[q].n_elems), 0});
+            dense_n += 2ull * res[q].n_elems;
         }
-        if (!big_refs.empty()) {
-            if ((rc = c->d_gather.reserve(big_refs.size())) || (rc = c->d_dense.reserve(dense_n))) return rc;
-            HIP_TRY(hipMemcpyAsync(c->d_gather.p, big_refs.data(), big_refs.size() * sizeof(GatherRef), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_sw_gather, dim3((u32)std::min<size_t>(big_refs.size(), 65535)), dim3(256), 0, s, c->d_gather.p,
-                               (u32)big_refs.size(), c->d_el.p, c->d_dense.p);
-        }
-        big_at.push_back(dense_n);
+        const Lens l = pair_lens(in, k.lo + q);
+        eo2 += 2 * (l.l1 + l.l2 + 2);
     }
-    std::unique_ptr<int16_t[]> big(new (std::nothrow) int16_t[big_at.back() + 1]);
-    if (!big) return -ENOMEM;
+    f.big.reset(new (std::nothrow) int16_t[dense_n + 1]);
+    if (!f.big) return -ENOMEM;
     if (!big_refs.empty()) {
-        HIP_TRY(hipMemcpyAsync(big.get(), c->d_dense.p, big_at.back() * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+        if ((rc = c->d_gather.reserve(big_refs.size())) || (rc = c->d_dense.reserve(dense_n))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_gather.p, big_refs.data(), big_refs.size() * sizeof(GatherRef), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_sw_gather, dim3((u32)std::min<size_t>(big_refs.size(), 65535)), dim3(256), 0, s, c->d_gather.p,
+                           (u32)big_refs.size(), c->d_el.p, c->d_dense.p);
+        HIP_TRY(hipMemcpyAsync(f.big.get(), c->d_dense.p, dense_n * sizeof(int16_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); c->stats.ms_fill += ms;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2])); c->stats.ms_trace += ms;
-    c->stats.backtrace_bytes += bt;
-    // results and CIGAR text, a few threads when the batch is large (rendering long element lists is
-    // the library's biggest host cost)
-    tp[4] = now();
+    c->stats.backtrace_bytes += bt_bytes;
+    f.res = res; f.cel = cel;
+    return 0;
+}
+// results and CIGAR text, a few threads when the batch is large (rendering long element lists is the library's biggest host cost)
+void emit_text(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, const Fetched& f, const Outputs& out) {
     auto emit = [&](u32 q0, u32 q1, u64* cells_out) {
         u64 cells = 0;
         for (u32 q = q0; q < q1; ++q) {
-            const u64 p = lo + q;
-            const u32 l1 = (u32)(in->ref_off[p + 1] - in->ref_off[p]), l2 = (u32)(in->alt_off[p + 1] - in->alt_off[p]);
-            const SwResult& r = res[q];
-            out_offset[p] = r.offset;
-            if (out_score) out_score[p] = r.score;
-            if (out_cigar) {
-                char* dst = out_cigar + (size_t)p * stride;
-                const int cap = cap_override >= 0 ? cap_override
-                                                  : (int)std::min<u64>(2ull * std::max(l1, l2), (u64)stride - 1);   // IntelSmithWaterman.cpp:8
-                const int16_t* src = cel + (size_t)q * 2 * kCompactElems;
-                if (r.n_elems > kCompactElems) src = big.get() + big_at[q];
+            const u64 p = k.lo + q;
+            const Lens l = pair_lens(in, p);
+            const SwResult& r = f.res[q];
+            out.offset[p] = r.offset;
+            if (out.score) out.score[p] = r.score;
+            if (out.cigar) {
+                char* dst = out.cigar + (size_t)p * out.stride;
+                const int cap = out.cap_override >= 0 ? out.cap_override
+                                                      : (int)std::min<u64>(2ull * std::max(l.l1, l.l2), (u64)out.stride - 1);   // IntelSmithWaterman.cpp:8
+                const int16_t* src = r.n_elems > kCompactElems ? f.big.get() + f.big_at[q] : f.cel + (size_t)q * 2 * kCompactElems;
                 const int len = render(src, r.n_elems, dst, cap);
                 dst[len] = 0;                             // cap <= stride - 1
             }
-            cells += (u64)l1 * l2;
+            cells += l.l1 * l.l2;
         }
         *cells_out = cells;
     };
     constexpr u32 kThreads = 4;
     u64 cells[kThreads] = {0};
-    if (n < 16384) emit(0, n, &cells[0]);
+    if (k.n < 16384) emit(0, k.n, &cells[0]);
     else {
         std::thread th[kThreads];
-        for (u32 t = 0; t < kThreads; ++t) th[t] = std::thread(emit, (u32)((u64)n * t / kThreads), (u32)((u64)n * (t + 1) / kThreads), &cells[t]);
+        for (u32 t = 0; t < kThreads; ++t) th[t] = std::thread(emit, (u32)((u64)k.n * t / kThreads), (u32)((u64)k.n * (t + 1) / kThreads), &cells[t]);
         for (auto& t : th) t.join();
     }
     for (u64 x : cells) c->stats.cells += x;
+}
+
+int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const Chunk& k, const Knobs& knobs, const Outputs& out) {
+    static const bool prof = [] { const char* e = getenv("MGX_SW_PROF"); return e && atoi(e) != 0; }();      // host stage times on stderr
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double tp[6] = {now()};
+    const SwParams P{params->match, params->mismatch, params->gap_open, params->gap_extend};
+    Stager st;
+    Fetched f;
+    if (int rc = stage_sequences(c, in, k, st)) return rc;
+    SwJob* const jobs = reinterpret_cast<SwJob*>(c->pin.p + k.a1 + k.a2);
+    const Layout L = lay_out(c, params, in, k, knobs, jobs);
+    tp[1] = now();
+    if (int rc = upload_jobs(c, k, st, L, jobs)) return rc;
+    tp[2] = now();
+    launch_fills(c, jobs, L.n_jobs, P);
+    if (int rc = launch_trace(c, L.n_jobs)) return rc;
+    tp[3] = now();
+    if (int rc = fetch_results(c, in, k, L.bt_bytes, f)) return rc;
+    tp[4] = now();
+    emit_text(c, in, k, f, out);
     tp[5] = now();
-    if (prof) fprintf(stderr, "[mgx_sw] %u pairs: jobs %.3f  stage+H2D %.3f  launches %.3f  kernels+D2H %.3f  text %.3f ms\n", n, tp[1] - tp[0], tp[2] - tp[1],
+    if (prof) fprintf(stderr, "[mgx_sw] %u pairs: jobs %.3f  stage+H2D %.3f  launches %.3f  kernels+D2H %.3f  text %.3f ms\n", k.n, tp[1] - tp[0], tp[2] - tp[1],
                       tp[3] - tp[2], tp[4] - tp[3], tp[5] - tp[4]);
     return 0;
 }
@@ -1110,8 +925,6 @@ void mgx_sw_destroy(mgx_sw_t* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->pin) (void)hipHostFree(c->pin);
-    if (c->pin_out) (void)hipHostFree(c->pin_out);
     delete c;
 }
 
@@ -1127,7 +940,7 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
     const int max_ref = (c->flags & MGX_SW_LONG_REF) ? kMaxLen : kMaxRef;
     for (u64 p = 0; p < in->n_pairs; ++p) {
         if (in->ref_off[p + 1] < in->ref_off[p] || in->alt_off[p + 1] < in->alt_off[p]) { set_error("pair %llu: offsets decrease", (unsigned long long)p); return -EINVAL; }
-        const u64 l1 = in->ref_off[p + 1] - in->ref_off[p], l2 = in->alt_off[p + 1] - in->alt_off[p];
+        const auto [l1, l2] = pair_lens(in, p);
         if (l1 == 0 || l2 == 0) { set_error("pair %llu: empty sequence", (unsigned long long)p); return -EINVAL; }
         if (l1 > (u64)max_ref) { set_error("pair %llu: reference of %llu bases (limit %d)", (unsigned long long)p, (unsigned long long)l1, max_ref); return -E2BIG; }
         if (l2 > (u64)kMaxLen) { set_error("pair %llu: alternate of %llu bases (limit 32767)", (unsigned long long)p, (unsigned long long)l2); return -E2BIG; }
@@ -1137,23 +950,11 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
     HIP_TRY(hipSetDevice(c->device));
     const Knobs knobs;
     const u64 limit = knobs.arena ? knobs.arena : kArenaLimit;
-    u64 lo = 0;
-    while (lo < in->n_pairs) {
-        u64 hi = lo, bt = 0;
-        while (hi < in->n_pairs) {
-            // an upper bound of what the pair takes of the back-trace arena in any shape: the one-pair-per-wavefront 32-bit form
-            // (the paired form and the 16-bit form are smaller) plus the 16-bit kernel's edge rows
-            const u64 l1 = in->ref_off[hi + 1] - in->ref_off[hi], l2 = in->alt_off[hi + 1] - in->alt_off[hi];
-            const u64 rows = (l1 + 63) / 64, slot = rows <= 8 ? ((rows + 3) & ~3ull) : rows <= 16 ? 16 : 32;
-            // (a reference of more than kMaxRef bases has one shape only: its strips and its boundary array, to the byte)
-            const u64 need = l1 > (u64)kMaxRef ? bt_bytes_strip(l1, l2) + bnd_bytes_strip(l2)
-                                               : (l2 + 64 + 1) * 64 * slot + 8 * (l2 + 1) * ((l1 + 31) / 32 * 3 / 2 + 2) + 8 * (l1 + 64) + 64;
-            if (hi > lo && bt + need > limit) break;
-            bt += need; ++hi;
-        }
-        const int rc = run_chunk(c, params, in, lo, hi, knobs, out_offset, out_cigar, cigar_stride, out_score, cap_override);
+    const Outputs out{out_offset, out_cigar, cigar_stride, out_score, cap_override};
+    for (u64 lo = 0, hi; lo < in->n_pairs; lo = hi) {
+        hi = chunk_end(in->ref_off, in->alt_off, in->n_pairs, lo, limit);      // by chunk_bound per pair (sw_layout.h)
+        const int rc = run_chunk(c, params, in, Chunk(in, lo, hi), knobs, out);
         if (rc) return rc;
-        lo = hi;
     }
     return 0;
 }

@@ -137,8 +137,23 @@ def concat(pairs, strategies):
                 strategy=np.array(strategies, dtype=np.uint8))
 
 
-# ---- the launch order of a batch (mgx_smithwaterman.hip, run_chunk): which pairs share a lane group
-ROW_CLASSES16 = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 20, 24, 32)
+# ---- one fixed batch whose layout is pinned: (reference, alternate) lengths in input order, strategies rotating, STANDARD_NGS.
+# Both 16-bit widths when paired (references up to 1024 bases take 32 lanes), classes of odd size, (2000, 600) which the rule
+# refuses, and two strip pairs (a context with MGX_SW_LONG_REF).  FIXED_STATS: (MGX_SW_PAIRED, MGX_SW_I16) -> what stats()
+# reported for it on the commit BEFORE csrc/sw_layout.h existed (profiles/sw_layout_refactor_ab.txt): the CPU test holds the
+# header to these numbers (tests/test_sw_layout_host.py), the GPU test the library (test_stats_of_the_fixed_batch).
+FIXED_LENS = ((1, 1), (17, 5), (32, 64), (33, 17), (64, 151), (65, 16), (100, 100), (100, 100), (128, 65), (129, 2), (250, 151),
+              (251, 151), (256, 150), (300, 120), (320, 64), (321, 1), (400, 151), (2049, 1), (500, 130), (512, 17), (513, 16),
+              (640, 100), (700, 90), (2000, 600), (1000, 151), (1024, 64), (1025, 65), (1100, 151), (1280, 16), (4097, 65),
+              (1500, 100), (2047, 17), (2048, 2), (2048, 151), (90, 40), (350, 151), (351, 149), (1300, 17), (7, 300), (960, 33))
+FIXED_STRATEGIES = tuple(STRATEGIES[q % 4] for q in range(len(FIXED_LENS)))
+FIXED_STAT_KEYS = ("backtrace_bytes", "n_launches", "n_pairs_i16", "n_pairs_strip", "n_strips")
+FIXED_STATS = {(0, 0): (5728160, 10, 0, 2, 5), (0, 1): (4945776, 4, 37, 2, 5), (1, 0): (5463872, 11, 0, 2, 5), (1, 1): (4555936, 5, 37, 2, 5)}
+
+
+# ---- the launch order of a batch (csrc/sw_layout.h, sw_build_jobs): which pairs share a lane group.  The GPU tests go by this
+# restatement; tests/test_sw_layout_host.py ties it to the C++ (the partners tests/cpp/sw_layout_driver.cpp reports).
+ROW_CLASSES16 =(1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 20, 24, 32)
 
 
 def shape16(len1, paired):

@@ -196,6 +196,27 @@ def test_largest_sizes_and_many_chunks(sw_engine, sw_oracle, synth, monkeypatch)
     assert st["n_pairs_i16"] == 600 and st["n_launches"] >= 4
 
 
+def test_stats_of_the_fixed_batch(pkg, sw_oracle, monkeypatch):
+    """sw_frontier.FIXED_LENS under both lane-group families and both fills: what the library launches and reserves is what
+    tests/test_sw_layout_host.py holds csrc/sw_layout.h to on the CPU (the same literal numbers), and the answers are the oracle's"""
+    import sw_frontier as F
+    import sw_long as L
+    pairs = [L.make_pair(n, m, 9000 + q) for q, (n, m) in enumerate(F.FIXED_LENS)]
+    w = L.concat(pairs, F.FIXED_STRATEGIES)
+    want_c, want_o, want_s = sw_oracle.batch(w, F.STANDARD_NGS)
+    eng = pkg.SmithWatermanEngine(0, pkg.smithwaterman.LONG_REF)              # the batch holds references of 2049 and 4097 bases
+    try:
+        for (paired, i16), want in sorted(F.FIXED_STATS.items()):
+            monkeypatch.setenv("MGX_SW_PAIRED", str(paired))
+            monkeypatch.setenv("MGX_SW_I16", str(i16))
+            got_c, got_o, got_s = eng.align_batch(w["ref_off"], w["ref"], w["alt_off"], w["alt"], w["strategy"], F.STANDARD_NGS, want_score=True)
+            assert np.array_equal(got_o, want_o) and np.array_equal(got_s, want_s) and got_c == want_c, (paired, i16)
+            st = eng.stats()
+            assert tuple(int(st[k]) for k in F.FIXED_STAT_KEYS) == want, (paired, i16)
+    finally:
+        eng.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The packed 16-bit fill along its admission frontier.  Whether a pair is admitted is asked of the host driver
 # (tests/cpp/sw_i16_rule_driver.cpp over csrc/sw_i16_rule.h), never of the device; CIGAR, offset and score come from the
