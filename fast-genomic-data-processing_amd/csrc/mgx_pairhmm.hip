@@ -24,7 +24,9 @@
 #include <vector>
 
 #include "../../include/mgx_pairhmm.h"
+#include "../../include/mgx_realign.h"
 #include "mgx_common.h"
+#include "mgx_realign_internal.h"
 #include "mgx_tables.h"
 #include "pairhmm_pack.h"
 #include "pairhmm_wire.h"
@@ -92,6 +94,7 @@ struct mgx_pairhmm {
     bool wire = false;           // MGX_PAIRHMM_WIRE, or its environment override: staged pair-list batches upload the wire form
     std::vector<Slab> free_slabs;
     void* d_strip = nullptr; size_t strip_cap = 0;      // boundary rows of the strip-mined class (one compute stream: launches do not overlap)
+    mgx_internal::PairhmmExt ext;                       // mgx_realign.hip's buffers and statistics
 };
 
 struct mgx_pairhmm_batch {
@@ -425,6 +428,7 @@ int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
 void mgx_pairhmm_destroy(mgx_pairhmm_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    if (c->ext.p && c->ext.free_fn) c->ext.free_fn(c->ext.p);
     (void)hipFree(c->d_ph2pr_f); (void)hipFree(c->d_mm_f);
     (void)hipFree(c->d_ph2pr_d); (void)hipFree(c->d_mm_d);
     (void)hipFree(c->d_div3_f); (void)hipFree(c->d_ratio_f); (void)hipFree(c->d_div3_d); (void)hipFree(c->d_ratio_d);
@@ -1369,6 +1373,58 @@ void cut_regions(const mgx_pairhmm_input_t* regions, uint32_t n_regions, uint64_
 }
 }  // namespace
 
+// The stages of a whole-region call (mgx_realign_internal.h): mgx_pairhmm_regions below runs them back to back, mgx_realign_regions
+// (mgx_realign.hip) puts the best-haplotype and verbatim kernels between the run and the download.
+extern "C++" {
+namespace mgx_internal {
+PairhmmView pairhmm_view(mgx_pairhmm_t* c) { return PairhmmView{c->device, c->flags, c->compute, c->d2h, &c->ext}; }
+
+int regions_begin(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, const uint8_t* const* mapq,
+                  const mgx_read_model_t* model, double* const* out_log10, RegionBatch* rb) {
+    if (n_regions == 0) return 0;
+    int rc;
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        if ((rc = validate(&regions[g]))) return rc;
+        if (regions[g].n_reads * regions[g].n_haps && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    BatchPtr b = new_batch();
+    if (!b) return -ENOMEM;
+    if ((rc = create_cross(c, n_regions, regions, b.get(), &rb->base, mapq, model))) return rc;
+    if (b->n_pairs == 0) return 0;
+    mgx_pairhmm_batch* raw = b.release();
+    if ((rc = mgx_pairhmm_batch_run(c, raw))) { mgx_pairhmm_batch_destroy(c, raw); return rc; }
+    rb->batch = raw; rb->n_pairs = raw->n_pairs; rb->n_reads = raw->n_reads;
+    rb->d_bases = raw->d_bases; rb->d_hap = raw->d_hap; rb->d_keep = raw->d_keep; rb->d_out = raw->d_out;
+    rb->d_row_off = raw->d_row_off; rb->d_row_nh = raw->d_row_nh; rb->done = raw->done;
+    return 0;
+}
+
+int regions_queue_download(mgx_pairhmm_t* c, const RegionBatch& rb, hipStream_t s) {
+    const mgx_pairhmm_batch* b = rb.batch;
+    if (s != c->compute) HIP_TRY(hipStreamWaitEvent(s, b->done, 0));
+    HIP_TRY(hipMemcpyAsync(b->slab.pin + b->o_out, b->d_out, b->result_bytes, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+void regions_scatter(const RegionBatch& rb, const mgx_pairhmm_input_t* regions, uint32_t n_regions, double* const* out_log10,
+                     uint8_t* const* out_keep) {
+    scatter_region_results(rb.batch, rb.base, regions, 0, n_regions, out_log10, out_keep);
+}
+
+void regions_end(mgx_pairhmm_t* c, RegionBatch* rb) {
+    mgx_pairhmm_batch_destroy(c, rb->batch);
+    rb->batch = nullptr;
+}
+
+void launch_best_allele_rows(hipStream_t s, const double* d_values, const uint32_t* d_row_off, const uint32_t* d_row_nh,
+                             const double* d_priority, const uint32_t* d_pri_off, uint32_t n_rows, int32_t* d_best) {
+    hipLaunchKernelGGL(pairhmm_best_allele_rows, dim3((n_rows + 3) / 4), dim3(256), 0, s, d_values, d_row_off, d_row_nh, d_priority, d_pri_off,
+                       n_rows, d_best);
+}
+}  // namespace mgx_internal
+}  // extern "C++"
+
 int mgx_pairhmm_batch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, double* out_log10,
                               uint8_t* used_f64) {
     if (!c || !b) { set_error("ctx/batch is NULL"); return -EINVAL; }
@@ -1413,30 +1469,52 @@ int mgx_pairhmm_compute(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, double*
 int mgx_pairhmm_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, const uint8_t* const* mapq,
                         const mgx_read_model_t* model, double* const* out_log10, uint8_t* const* out_keep) {
     if (!c || !model || (n_regions && (!regions || !mapq || !out_log10))) { set_error("NULL argument"); return -EINVAL; }
-    if (n_regions == 0) return 0;
-    int rc;
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        if ((rc = validate(&regions[g]))) return rc;
-        if (regions[g].n_reads * regions[g].n_haps && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    BatchPtr b = new_batch();
-    if (!b) return -ENOMEM;
-    std::vector<uint64_t> base;
-    if ((rc = create_cross(c, n_regions, regions, b.get(), &base, mapq, model))) return rc;
-    if (b->n_pairs == 0) return 0;
-    mgx_pairhmm_batch* raw = b.release();
-    rc = mgx_pairhmm_batch_run(c, raw);
-    if (!rc) {
-        rc = [&]() -> int {       // values and keep flags in one copy, behind the kernels on their own stream
-            HIP_TRY(hipMemcpyAsync(raw->slab.pin + raw->o_out, raw->d_out, raw->result_bytes, hipMemcpyDeviceToHost, c->compute));
-            HIP_TRY(hipStreamSynchronize(c->compute));
-            return 0;
-        }();
-        if (!rc) scatter_region_results(raw, base, regions, 0, n_regions, out_log10, out_keep);
-    }
-    mgx_pairhmm_batch_destroy(c, raw);
+    // the stages below are shared with mgx_realign_regions (mgx_realign.hip), which puts its own between the run and the download
+    mgx_internal::RegionBatch rb;
+    int rc = mgx_internal::regions_begin(c, n_regions, regions, mapq, model, out_log10, &rb);
+    if (rc || !rb.batch) return rc;
+    rc = [&]() -> int {           // values and keep flags in one copy, behind the kernels on their own stream
+        if (const int e = mgx_internal::regions_queue_download(c, rb, c->compute)) return e;
+        HIP_TRY(hipStreamSynchronize(c->compute));
+        return 0;
+    }();
+    if (!rc) mgx_internal::regions_scatter(rb, regions, n_regions, out_log10, out_keep);
+    mgx_internal::regions_end(c, &rb);
     return rc;
+}
+
+int mgx_pairhmm_best_alleles(mgx_pairhmm_t* c, uint64_t n_rows, const uint64_t* row_off, const uint32_t* row_nh, const double* values_log10,
+                             const double* priority, int32_t* out_best) {
+    if (!c || (n_rows && (!row_off || !row_nh || !out_best))) { set_error("NULL argument"); return -EINVAL; }
+    if (n_rows == 0) return 0;
+    if (n_rows > 0xFFFFFFF0ull) { set_error("more than 2^32 rows"); return -E2BIG; }
+    uint64_t n_values = 0;
+    std::vector<uint32_t> off32(n_rows);
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        if (row_off[r] + row_nh[r] > 0xFFFFFFF0ull) { set_error("row %llu ends beyond 2^32 values", (unsigned long long)r); return -E2BIG; }
+        off32[r] = (uint32_t)row_off[r];
+        n_values = std::max(n_values, row_off[r] + row_nh[r]);
+    }
+    if (n_values && !values_log10) { set_error("NULL argument"); return -EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    // [values | priorities | row_off | row_nh | best] in one allocation of the call's own
+    const size_t vb = align_up(n_values * sizeof(double)), ib = align_up(n_rows * sizeof(uint32_t));
+    uint8_t* dv = nullptr;
+    HIP_TRY(hipMalloc((void**)&dv, 2 * vb + 3 * ib + 16));
+    std::unique_ptr<uint8_t, void (*)(uint8_t*)> hold(dv, [](uint8_t* p) { (void)hipFree(p); });
+    double* d_val = (double*)dv; double* d_pri = (double*)(dv + vb);
+    uint32_t* d_off = (uint32_t*)(dv + 2 * vb); uint32_t* d_nh = (uint32_t*)(dv + 2 * vb + ib);
+    int32_t* d_best = (int32_t*)(dv + 2 * vb + 2 * ib);
+    hipStream_t s = c->compute;
+    if (n_values) HIP_TRY(hipMemcpyAsync(d_val, values_log10, n_values * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_values && priority) HIP_TRY(hipMemcpyAsync(d_pri, priority, n_values * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_off, off32.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_nh, row_nh, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    mgx_internal::launch_best_allele_rows(s, d_val, d_off, d_nh, priority ? d_pri : nullptr, nullptr, (uint32_t)n_rows, d_best);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_best, d_best, n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
 }
 
 int mgx_pairhmm_region(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const uint8_t* mapq,

@@ -1,0 +1,375 @@
+// mgx_realign.hip -- realignReadsToTheirBestHaplotype in one device call (C ABI: include/mgx_realign.h).
+//
+// The reference runs computeReadLikelihoods, then per read bestAllelesBreakingTies and createReadAlignedToRef's aligner call
+// (M2/Mutect2Engine.cpp:223-231).  Here the PairHMM batch stays in HBM between the two: the best haplotype of every read
+// (pairhmm_best_allele_rows, pairhmm_kernels.hip.inc) and SWNativeAlignerWrapper's verbatim shortcut (k_realign_verbatim) run behind
+// the PairHMM epilogue, 9 bytes per read come back, and the reads that still need the aligner are gathered out of the batch's slab
+// into the Smith-Waterman context's sequence arrays (k_realign_gather) instead of being assembled and uploaded by the host.
+//   * Mutect2Utils::lastIndexOf (Mutect2Utils.cpp:69-82): the LAST verbatim occurrence, bytes compared as the aligner compares them.
+//   * The aligner's jobs derive their score and element offsets from the sequence offsets (sw_layout.h: sc_off = off1 + off2 + 2q),
+//     so its sequences must be dense and in pair order: hence a gather, not pointers into the slab.
+//   * Region batches upload the caller's bytes unchanged (the wire form is for staged pair lists only): the slab's bases are the caller's.
+// The two contexts' internals are reached through mgx_realign_internal.h; both keep their own code paths.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/mgx_realign.h"
+#include "mgx_common.h"
+#include "mgx_realign_internal.h"
+#include "pairhmm_pack.h"
+
+using mgx::set_error;
+using namespace mgx_internal;
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(e_)); return -EIO; } \
+    } while (0)
+
+namespace {
+typedef uint8_t u8; typedef uint32_t u32; typedef uint64_t u64;
+
+// per read, in global read order: its bases in the slab and where its region's haplotypes start in the haplotype table
+struct ReadRef { u64 off; u32 len, hap_base; };
+struct HapRef { u64 off; u32 len, pad_; };                 // in input order, region after region
+// one read that needs the aligner: sources in the slab, destinations as the aligner's offsets (the chunk's first is subtracted)
+struct GatherJob { u64 src_ref, src_alt, dst_ref, dst_alt; u32 len_ref, len_alt; };
+static_assert(sizeof(ReadRef) == 16 && sizeof(HapRef) == 16 && sizeof(GatherJob) == 40, "table entries");
+
+// One wavefront per kept read: does the read occur verbatim in its best haplotype, and where last?  Lanes take the start positions
+// from H - R downwards, 64 at a time, and compare with an early exit; a ballot picks the highest matching start of the first block
+// that has one.  R > H: no start at all, -1.  Lane 0 also copies the keep flag next to the result, so that the host fetches
+// [best | match | keep] in one copy.
+__global__ __launch_bounds__(256) void k_realign_verbatim(const ReadRef* __restrict__ reads, const HapRef* __restrict__ haps,
+                                                          const u8* __restrict__ bases, const u8* __restrict__ hap_bases,
+                                                          const int32_t* __restrict__ best, const u8* __restrict__ keep, u32 n_reads,
+                                                          int enabled, int32_t* __restrict__ match, u8* __restrict__ keep_out) {
+    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= n_reads) return;
+    const bool kept = keep[r] != 0;
+    int found = -1;
+    if (kept && enabled) {
+        const ReadRef R = reads[r];
+        const HapRef H = haps[R.hap_base + (u32)best[r]];
+        const u8* rd = bases + R.off;
+        const u8* hp = hap_bases + H.off;
+        const int n = (int)R.len;
+        for (int top = (int)H.len - n; top >= 0; top -= 64) {          // the block's highest start; every start s has s + n <= H
+            const int start = top - lane;
+            bool ok = start >= 0;
+            if (ok) {
+                const u8* w = hp + start;
+                int i = 0;
+                while (i < n && w[i] == rd[i]) ++i;
+                ok = i == n;
+            }
+            const unsigned long long m = __ballot(ok);
+            if (m) { found = top - (__ffsll((long long)m) - 1); break; }
+        }
+    }
+    if (lane == 0) { match[r] = found; keep_out[r] = kept ? 1 : 0; }
+}
+
+// One wavefront per read that needs the aligner: its best haplotype and its bases out of the slab into the aligner's dense arrays.
+__global__ __launch_bounds__(256) void k_realign_gather(const GatherJob* __restrict__ jobs, u32 n_jobs, u64 base_ref, u64 base_alt,
+                                                        const u8* __restrict__ bases, const u8* __restrict__ hap_bases,
+                                                        u8* __restrict__ d_ref, u8* __restrict__ d_alt) {
+    const u32 q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const u32 lane = threadIdx.x & 63;
+    if (q >= n_jobs) return;
+    const GatherJob J = jobs[q];
+    const u8* s1 = hap_bases + J.src_ref; u8* d1 = d_ref + (J.dst_ref - base_ref);
+    const u8* s2 = bases + J.src_alt;     u8* d2 = d_alt + (J.dst_alt - base_alt);
+    for (u32 x = lane; x < J.len_ref; x += 64) d1[x] = s1[x];
+    for (u32 x = lane; x < J.len_alt; x += 64) d2[x] = s2[x];
+}
+
+// a device buffer with a pinned mirror, grown on demand
+struct Mirror {
+    u8* dev = nullptr; u8* pin = nullptr; size_t cap = 0;
+    int reserve(size_t n) {
+        if (n <= cap) return 0;
+        release();
+        const size_t want = n + n / 4 + 256;
+        if (hipMalloc((void**)&dev, want) != hipSuccess || hipHostMalloc((void**)&pin, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); release(); set_error("allocation of %zu bytes failed", want); return -ENOMEM;
+        }
+        cap = want;
+        return 0;
+    }
+    void release() { if (dev) (void)hipFree(dev); if (pin) (void)hipHostFree(pin); dev = pin = nullptr; cap = 0; }
+    ~Mirror() { release(); }
+};
+
+// what a PairHMM context keeps for this call (mgx_internal::PairhmmExt)
+struct Realign {
+    Mirror tables, small, gjobs;      // [ReadRef | HapRef | priority | pri_off] up | [best | match | keep] down | GatherJob up
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // best: 0-1, verbatim: 1-2, gather: 3-4
+    mgx_realign_stats_t stats{};
+    ~Realign() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+int realign_of(const PairhmmView& v, Realign** out) {
+    if (!v.ext->p) {
+        Realign* r = new (std::nothrow) Realign;
+        if (!r) return -ENOMEM;
+        v.ext->p = r; v.ext->free_fn = [](void* p) { delete static_cast<Realign*>(p); };
+        for (auto& e : r->ev) HIP_TRY(hipEventCreate(&e));
+    }
+    *out = static_cast<Realign*>(v.ext->p);
+    return 0;
+}
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+struct Args {
+    mgx_pairhmm_t* c; mgx_sw_t* sw; u32 n_regions; const mgx_pairhmm_input_t* regions; const double* const* hap_priority;
+    mgx_sw_params_t params; u8 strategy;
+    int32_t* const* out_best; int32_t* const* out_offset; char* const* out_cigar; u32 stride; int32_t* const* out_score;
+};
+bool shortcut_applies(u8 strategy) { return strategy == MGX_SW_SOFTCLIP || strategy == MGX_SW_IGNORE; }      // SWNativeAlignerWrapper.cpp:14
+
+// ---- before anything is launched: arguments, devices, lengths
+int check(const Args& a, const uint8_t* const* mapq, const mgx_read_model_t* model, double* const* out_log10, u64* n_reads) {
+    if (!a.c || !a.sw || !model || (a.n_regions && (!a.regions || !mapq || !out_log10 || !a.out_best || !a.out_offset))) { set_error("NULL argument"); return -EINVAL; }
+    if (a.out_cigar && a.stride < 2) { set_error("cigar_stride must be at least 2"); return -EINVAL; }
+    if (a.strategy < MGX_SW_SOFTCLIP || a.strategy > MGX_SW_IGNORE) { set_error("unknown overhang strategy %d", (int)a.strategy); return -EINVAL; }
+    const SwView sv = sw_view(a.sw);
+    if (pairhmm_view(a.c).device != sv.device) { set_error("the PairHMM context is on device %d, the Smith-Waterman context on %d", pairhmm_view(a.c).device, sv.device); return -EINVAL; }
+    *n_reads = 0;
+    for (u32 g = 0; g < a.n_regions; ++g) {
+        const mgx_pairhmm_input_t& in = a.regions[g];
+        if (in.pair_read || in.pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
+        if (int rc = mgx::validate(&in)) return rc;
+        *n_reads += in.n_reads;
+        if (in.n_reads == 0) continue;
+        if (!a.out_best[g] || !a.out_offset[g] || (a.out_cigar && !a.out_cigar[g]) || (a.out_score && !a.out_score[g])) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
+        if (in.n_haps == 0) continue;
+        // every haplotype of a region that has reads may come out best
+        for (u64 h = 0; h < in.n_haps; ++h)
+            if (in.hap_off[h + 1] - in.hap_off[h] > (u64)sv.max_ref) {
+                set_error("region %u: haplotype %llu of %llu bases exceeds the aligner's reference limit %d", g, (unsigned long long)h,
+                          (unsigned long long)(in.hap_off[h + 1] - in.hap_off[h]), sv.max_ref);
+                return -E2BIG;
+            }
+        for (u64 r = 0; r < in.n_reads; ++r)
+            if (in.read_off[r + 1] - in.read_off[r] > (u64)sv.max_alt) { set_error("region %u: read %llu exceeds the aligner's alternate limit %d", g, (unsigned long long)r, sv.max_alt); return -E2BIG; }
+    }
+    if (*n_reads > 0x7FFFFFF0ull) { set_error("more than 2^31 reads in one call"); return -E2BIG; }
+    return 0;
+}
+
+// ---- the tables of the two kernels, into the pinned mirror: reads and haplotypes as create_cross lays them out in the slab
+// (region after region, offsets rebased to each region's first byte), priorities per haplotype (0 where a region has none)
+struct Tables { size_t o_reads, o_haps, o_pri, o_prioff, bytes; u64 n_reads, n_haps; bool has_pri; };
+int stage_tables(const Args& a, u64 n_reads, Realign* st, Tables* t) {
+    u64 n_haps = 0;
+    bool has_pri = false;
+    for (u32 g = 0; g < a.n_regions; ++g) { n_haps += a.regions[g].n_haps; has_pri |= a.hap_priority && a.hap_priority[g]; }
+    t->n_reads = n_reads; t->n_haps = n_haps; t->has_pri = has_pri;
+    t->o_reads = 0; t->o_haps = up256(n_reads * sizeof(ReadRef)); t->o_pri = t->o_haps + up256(n_haps * sizeof(HapRef));
+    t->o_prioff = t->o_pri + up256(n_haps * sizeof(double)); t->bytes = t->o_prioff + up256(n_reads * sizeof(u32));
+    if (int rc = st->tables.reserve(t->bytes)) return rc;
+    ReadRef* reads = (ReadRef*)(st->tables.pin + t->o_reads); HapRef* haps = (HapRef*)(st->tables.pin + t->o_haps);
+    double* pri = (double*)(st->tables.pin + t->o_pri); u32* prioff = (u32*)(st->tables.pin + t->o_prioff);
+    u64 r_at = 0, h_at = 0, rb = 0, hb = 0;
+    for (u32 g = 0; g < a.n_regions; ++g) {
+        const mgx_pairhmm_input_t& in = a.regions[g];
+        for (u64 r = 0; r < in.n_reads; ++r) {
+            reads[r_at + r] = ReadRef{rb + (in.read_off[r] - in.read_off[0]), (u32)(in.read_off[r + 1] - in.read_off[r]), (u32)h_at};
+            prioff[r_at + r] = (u32)h_at;
+        }
+        for (u64 h = 0; h < in.n_haps; ++h) {
+            haps[h_at + h] = HapRef{hb + (in.hap_off[h] - in.hap_off[0]), (u32)(in.hap_off[h + 1] - in.hap_off[h]), 0};
+            pri[h_at + h] = (a.hap_priority && a.hap_priority[g]) ? a.hap_priority[g][h] : 0.0;
+        }
+        if (in.n_reads) rb += in.read_off[in.n_reads] - in.read_off[0];
+        if (in.n_haps) hb += in.hap_off[in.n_haps] - in.hap_off[0];
+        r_at += in.n_reads; h_at += in.n_haps;
+    }
+    return 0;
+}
+
+// ---- behind the epilogue on the PairHMM compute stream: best haplotype and verbatim search of every read; 9 bytes per read come back
+struct Small { const int32_t* best; const int32_t* match; const u8* keep; };
+int launch_best_and_verbatim(const Args& a, const PairhmmView& v, const RegionBatch& rb, const Tables& t, Realign* st, Small* out) {
+    hipStream_t s = v.compute;
+    const u32 n = rb.n_reads;
+    const size_t o_match = up256((size_t)n * 4), o_keep = 2 * o_match, bytes = o_keep + up256(n);
+    if (int rc = st->small.reserve(bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(st->tables.dev, st->tables.pin, t.bytes, hipMemcpyHostToDevice, s));
+    int32_t* d_best = (int32_t*)st->small.dev; int32_t* d_match = (int32_t*)(st->small.dev + o_match);
+    HIP_TRY(hipEventRecord(st->ev[0], s));
+    launch_best_allele_rows(s, rb.d_out, rb.d_row_off, rb.d_row_nh, t.has_pri ? (const double*)(st->tables.dev + t.o_pri) : nullptr,
+                            (const u32*)(st->tables.dev + t.o_prioff), n, d_best);
+    HIP_TRY(hipEventRecord(st->ev[1], s));
+    hipLaunchKernelGGL(k_realign_verbatim, dim3((n + 3) / 4), dim3(256), 0, s, (const ReadRef*)(st->tables.dev + t.o_reads),
+                       (const HapRef*)(st->tables.dev + t.o_haps), rb.d_bases, rb.d_hap, d_best, rb.d_keep, n, shortcut_applies(a.strategy) ? 1 : 0,
+                       d_match, st->small.dev + o_keep);
+    HIP_TRY(hipEventRecord(st->ev[2], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(st->small.pin, st->small.dev, bytes, hipMemcpyDeviceToHost, s));
+    out->best = (const int32_t*)st->small.pin; out->match = (const int32_t*)(st->small.pin + o_match); out->keep = st->small.pin + o_keep;
+    return 0;
+}
+
+// ---- the aligner's input over the reads that still need it: offset prefixes on the host, the bytes stay on the device
+struct Pairs { std::vector<u64> ref_off, alt_off; std::vector<u8> strategy; u64 n = 0; };
+int plan_pairs(const Args& a, const Tables& t, const Small& sm, Realign* st, Pairs* p) {
+    const ReadRef* reads = (const ReadRef*)(st->tables.pin + t.o_reads); const HapRef* haps = (const HapRef*)(st->tables.pin + t.o_haps);
+    u64 n = 0;
+    for (u64 r = 0; r < t.n_reads; ++r) {
+        st->stats.n_kept += sm.keep[r] != 0;
+        if (sm.keep[r] && sm.match[r] >= 0) st->stats.n_verbatim++;
+        n += sm.keep[r] && sm.match[r] < 0;
+    }
+    st->stats.n_sw_pairs = n;
+    p->n = n;
+    p->ref_off.assign(n + 1, 0); p->alt_off.assign(n + 1, 0); p->strategy.assign(n, a.strategy);
+    if (int rc = st->gjobs.reserve(n * sizeof(GatherJob))) return rc;
+    GatherJob* jobs = (GatherJob*)st->gjobs.pin;
+    u64 q = 0;
+    for (u64 r = 0; r < t.n_reads; ++r) {
+        if (!sm.keep[r] || sm.match[r] >= 0) continue;
+        const ReadRef& R = reads[r];
+        const HapRef& H = haps[R.hap_base + (u32)sm.best[r]];
+        jobs[q] = GatherJob{H.off, R.off, p->ref_off[q], p->alt_off[q], H.len, R.len};
+        p->ref_off[q + 1] = p->ref_off[q] + H.len; p->alt_off[q + 1] = p->alt_off[q] + R.len;
+        ++q;
+    }
+    return 0;
+}
+
+// the aligner's callback, per chunk in place of its upload (mgx_internal::SwDeviceSource)
+struct GatherCtx { Realign* st; const RegionBatch* rb; const Pairs* pairs; bool timing, pending; };
+int gather_chunk(void* user, hipStream_t s, u64 lo, u64 hi, u8* d_ref, u8* d_alt) {
+    GatherCtx* g = static_cast<GatherCtx*>(user);
+    Realign* st = g->st;
+    float ms = 0;
+    if (g->pending) { HIP_TRY(hipEventElapsedTime(&ms, st->ev[3], st->ev[4])); st->stats.ms_gather += ms; g->pending = false; }   // the chunk before has been fetched
+    const u32 n = (u32)(hi - lo);
+    HIP_TRY(hipMemcpyAsync(st->gjobs.dev + lo * sizeof(GatherJob), st->gjobs.pin + lo * sizeof(GatherJob), n * sizeof(GatherJob), hipMemcpyHostToDevice, s));
+    if (g->timing) HIP_TRY(hipEventRecord(st->ev[3], s));
+    hipLaunchKernelGGL(k_realign_gather, dim3((n + 3) / 4), dim3(256), 0, s, (const GatherJob*)st->gjobs.dev + lo, n, g->pairs->ref_off[lo],
+                       g->pairs->alt_off[lo], g->rb->d_bases, g->rb->d_hap, d_ref, d_alt);
+    if (g->timing) { HIP_TRY(hipEventRecord(st->ev[4], s)); g->pending = true; }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// "<len>M" under the aligner's capacity rule (PairWiseSW.h:410-444: an element whose text does not fit is skipped)
+void verbatim_text(u32 len, u64 hap_len, char* dst, u32 stride) {
+    char tmp[16];
+    const int need = snprintf(tmp, sizeof tmp, "%uM", len);
+    const u64 cap = std::min<u64>(2ull * std::max<u64>(hap_len, len), (u64)stride - 1);
+    if ((u64)need <= cap) memcpy(dst, tmp, (size_t)need + 1); else dst[0] = 0;
+}
+
+// ---- the per-read results into the caller's arrays of every region: dropped, verbatim, aligned
+struct Aligned { std::vector<int32_t> offset, score; std::vector<char> cigar; };
+void scatter_reads(const Args& a, const Tables* t, const Small* sm, const Realign* st, const Aligned& al) {
+    u64 r_at = 0, q = 0;
+    for (u32 g = 0; g < a.n_regions; ++g) {
+        const u64 nr = a.regions[g].n_reads;
+        for (u64 r = 0; r < nr; ++r) {
+            const u64 R = r_at + r;
+            char* text = a.out_cigar ? a.out_cigar[g] + r * a.stride : nullptr;
+            const bool kept = sm && sm->keep[R];
+            a.out_best[g][r] = sm ? sm->best[R] : 0;
+            if (!kept) {
+                a.out_offset[g][r] = MGX_REALIGN_NOT_ALIGNED;
+                if (text) text[0] = 0;
+                if (a.out_score) a.out_score[g][r] = 0;
+            } else if (sm->match[R] >= 0) {
+                const ReadRef& rd = ((const ReadRef*)(st->tables.pin + t->o_reads))[R];
+                const HapRef& hp = ((const HapRef*)(st->tables.pin + t->o_haps))[rd.hap_base + (u32)sm->best[R]];
+                a.out_offset[g][r] = sm->match[R];
+                if (text) verbatim_text(rd.len, hp.len, text, a.stride);
+                if (a.out_score) a.out_score[g][r] = (int32_t)rd.len * a.params.match;
+            } else {
+                a.out_offset[g][r] = al.offset[q];
+                if (text) memcpy(text, al.cigar.data() + q * a.stride, a.stride);
+                if (a.out_score) a.out_score[g][r] = al.score[q];
+                ++q;
+            }
+        }
+        r_at += nr;
+    }
+}
+
+int run(const Args& a, const uint8_t* const* mapq, const mgx_read_model_t* model, double* const* out_log10, uint8_t* const* out_keep) {
+    u64 n_reads = 0;
+    if (int rc = check(a, mapq, model, out_log10, &n_reads)) return rc;
+    const PairhmmView v = pairhmm_view(a.c);
+    HIP_TRY(hipSetDevice(v.device));
+    Realign* st = nullptr;
+    if (int rc = realign_of(v, &st)) return rc;
+    st->stats = mgx_realign_stats_t{};
+    st->stats.n_reads = n_reads;
+    // 1. the cross-product batch and its run
+    RegionBatch rb;
+    if (int rc = regions_begin(a.c, a.n_regions, a.regions, mapq, model, out_log10, &rb)) return rc;
+    if (!rb.batch) { scatter_reads(a, nullptr, nullptr, st, Aligned{}); return 0; }      // no test case: no read is kept
+    const int rc = [&]() -> int {
+        Tables t; Small sm; Pairs pairs; Aligned al;
+        int e;
+        // 2. best haplotype and verbatim search behind the epilogue  3. their 9 bytes per read  4. the matrix, on the d2h stream
+        if ((e = stage_tables(a, n_reads, st, &t)) || (e = launch_best_and_verbatim(a, v, rb, t, st, &sm))) return e;
+        if ((e = regions_queue_download(a.c, rb, v.d2h))) return e;
+        HIP_TRY(hipStreamSynchronize(v.compute));
+        if (v.flags & MGX_PAIRHMM_TIMING) {
+            HIP_TRY(hipEventElapsedTime(&st->stats.ms_best, st->ev[0], st->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&st->stats.ms_verbatim, st->ev[1], st->ev[2]));
+        }
+        // 5. the aligner's offsets  6. its chunks, each fed by the gather
+        if ((e = plan_pairs(a, t, sm, st, &pairs))) return e;
+        al.offset.assign(pairs.n, 0); al.score.assign(pairs.n, 0);
+        if (a.out_cigar) al.cigar.assign(pairs.n * a.stride, 0);
+        if (pairs.n) {
+            GatherCtx gc{st, &rb, &pairs, (v.flags & MGX_PAIRHMM_TIMING) != 0, false};
+            const SwDeviceSource src{rb.done, gather_chunk, &gc};
+            const mgx_sw_input_t in{pairs.n, pairs.ref_off.data(), nullptr, pairs.alt_off.data(), nullptr, pairs.strategy.data()};
+            if ((e = sw_align_from_device(a.sw, &a.params, &in, src, al.offset.data(), a.out_cigar ? al.cigar.data() : nullptr, a.stride, al.score.data()))) return e;
+            float ms = 0;
+            if (gc.pending) { HIP_TRY(hipEventElapsedTime(&ms, st->ev[3], st->ev[4])); st->stats.ms_gather += ms; }
+        }
+        // 7. everything to the per-region outputs
+        HIP_TRY(hipStreamSynchronize(v.d2h));
+        regions_scatter(rb, a.regions, a.n_regions, out_log10, out_keep);
+        scatter_reads(a, &t, &sm, st, al);
+        return 0;
+    }();
+    if (rc) { (void)hipStreamSynchronize(v.compute); (void)hipStreamSynchronize(v.d2h); }     // nothing of the batch in flight when its slab goes back
+    regions_end(a.c, &rb);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgx_realign_regions(mgx_pairhmm_t* c, mgx_sw_t* sw, uint32_t n_regions, const mgx_pairhmm_input_t* regions, const uint8_t* const* mapq,
+                        const mgx_read_model_t* model, const double* const* hap_priority, const mgx_sw_params_t* sw_params, uint8_t strategy,
+                        double* const* out_log10, uint8_t* const* out_keep, int32_t* const* out_best, int32_t* const* out_offset,
+                        char* const* out_cigar, uint32_t cigar_stride, int32_t* const* out_score) {
+    const mgx_sw_params_t to_best_haplotype{10, -15, -30, -5};      // ALIGNMENT_TO_BEST_HAPLOTYPE_SW_PARAMETERS, read/CigarUtils.cpp:15
+    const Args a{c, sw, n_regions, regions, hap_priority, sw_params ? *sw_params : to_best_haplotype, strategy,
+                 out_best, out_offset, out_cigar, cigar_stride, out_score};
+    return run(a, mapq, model, out_log10, out_keep);
+}
+
+int mgx_realign_stats(mgx_pairhmm_t* c, mgx_realign_stats_t* out) {
+    if (!c || !out) { set_error("NULL argument"); return -EINVAL; }
+    const PairhmmView v = pairhmm_view(c);
+    *out = v.ext->p ? static_cast<Realign*>(v.ext->p)->stats : mgx_realign_stats_t{};
+    return 0;
+}
+
+}  // extern "C"

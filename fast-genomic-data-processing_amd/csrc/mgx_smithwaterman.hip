@@ -41,6 +41,7 @@
 
 #include "../../include/mgx_smithwaterman.h"
 #include "mgx_common.h"
+#include "mgx_realign_internal.h"
 #include "sw_layout.h"
 
 using mgx::set_error;
@@ -702,8 +703,10 @@ struct Chunk {
 };
 struct Outputs { int32_t* offset; char* cigar; u32 stride; int32_t* score; int cap_override; };      // the caller's, indexed by input pair
 Lens pair_lens(const mgx_sw_input_t* in, u64 p) { return mgx_sw_layout::pair_lens(in->ref_off, in->alt_off, p); }
+using mgx_internal::SwDeviceSource;
 struct Stager {                   // the helper threads of stage_sequences: upload_jobs joins them, and so does every way out before it
     std::thread t[2]; std::atomic<int> err{0}; bool apart = false;
+    bool on_device = false;       // gather_sequences: the sequences are queued on the stream already
     void join() { for (auto& x : t) if (x.joinable()) x.join(); }
     ~Stager() { join(); }
 };
@@ -724,6 +727,16 @@ int stage_sequences(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, Stager&
     st.t[1] = std::thread(stage, c->d_s2.p, pin + k.a1, in->alt + k.base2, (size_t)k.n2);
     return 0;
 }
+// The same stage for sequences that lie in device memory (mgx_internal::sw_align_from_device): the stream waits for their owner,
+// and the owner's gather writes them where the upload would have; pinned memory keeps its layout, the jobs behind the (unused) sequences.
+int gather_sequences(mgx_sw* c, const SwDeviceSource& src, const Chunk& k, Stager& st) {
+    const size_t total = k.a1 + k.a2 + max_jobs(k.n) * sizeof(SwJob);
+    int rc;
+    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = c->d_s1.reserve(k.n1 + 16)) || (rc = c->d_s2.reserve(k.n2 + 16))) return rc;
+    st.on_device = true;
+    if (src.ready) HIP_TRY(hipStreamWaitEvent(c->stream, src.ready, 0));
+    return src.gather(src.user, c->stream, k.lo, k.hi, c->d_s1.p, c->d_s2.p);
+}
 // the jobs in launch order and their places in the arenas (sw_layout.h), built in place behind the sequences in pinned memory
 Layout lay_out(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const Chunk& k, const Knobs& knobs, SwJob* jobs) {
     const bool paired = knobs.paired >= 0 ? knobs.paired != 0 : k.n >= kPairedFrom;
@@ -741,7 +754,7 @@ int upload_jobs(mgx_sw* c, const Chunk& k, Stager& st, const Layout& L, const Sw
         (rc = c->d_res.reserve(k.n)) || (rc = c->d_cel.reserve((size_t)k.n * 2 * kCompactElems))) return rc;
     st.join();                                    // the helpers have queued the sequences: the jobs follow them on the stream
     if (st.err.load()) { (void)hipGetLastError(); set_error("upload of the sequences failed"); return -EIO; }
-    if (!st.apart) {
+    if (!st.apart && !st.on_device) {
         HIP_TRY(hipMemcpyAsync(c->d_s1.p, c->pin.p, k.n1, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(c->d_s2.p, c->pin.p + k.a1, k.n2, hipMemcpyHostToDevice, s));
     }
@@ -870,14 +883,15 @@ void emit_text(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, const Fetche
     for (u64 x : cells) c->stats.cells += x;
 }
 
-int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const Chunk& k, const Knobs& knobs, const Outputs& out) {
+int run_chunk(mgx_sw* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const Chunk& k, const Knobs& knobs, const Outputs& out,
+              const SwDeviceSource* src) {
     static const bool prof = [] { const char* e = getenv("MGX_SW_PROF"); return e && atoi(e) != 0; }();      // host stage times on stderr
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tp[6] = {now()};
     const SwParams P{params->match, params->mismatch, params->gap_open, params->gap_extend};
     Stager st;
     Fetched f;
-    if (int rc = stage_sequences(c, in, k, st)) return rc;
+    if (int rc = src ? gather_sequences(c, *src, k, st) : stage_sequences(c, in, k, st)) return rc;
     SwJob* const jobs = reinterpret_cast<SwJob*>(c->pin.p + k.a1 + k.a2);
     const Layout L = lay_out(c, params, in, k, knobs, jobs);
     tp[1] = now();
@@ -929,13 +943,14 @@ void mgx_sw_destroy(mgx_sw_t* c) {
 }
 
 static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in,
-                      int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score, int cap_override) {
+                      int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score, int cap_override,
+                      const SwDeviceSource* src = nullptr) {
     if (!c || !params || !in || !out_offset) { set_error("NULL argument"); return -EINVAL; }
     if (out_cigar && cigar_stride < 2) { set_error("cigar_stride must be at least 2"); return -EINVAL; }
     c->stats = mgx_sw_stats_t{};
     c->stats.n_pairs = in->n_pairs;
     if (in->n_pairs == 0) return 0;
-    if (!in->ref_off || !in->alt_off || !in->ref || !in->alt || !in->strategy) { set_error("NULL array in input"); return -EINVAL; }
+    if (!in->ref_off || !in->alt_off || (!src && (!in->ref || !in->alt)) || !in->strategy) { set_error("NULL array in input"); return -EINVAL; }
     if (in->n_pairs > 0x7FFFFFFFull) { set_error("more than 2^31-1 pairs in one batch"); return -E2BIG; }
     const int max_ref = (c->flags & MGX_SW_LONG_REF) ? kMaxLen : kMaxRef;
     for (u64 p = 0; p < in->n_pairs; ++p) {
@@ -953,7 +968,7 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
     const Outputs out{out_offset, out_cigar, cigar_stride, out_score, cap_override};
     for (u64 lo = 0, hi; lo < in->n_pairs; lo = hi) {
         hi = chunk_end(in->ref_off, in->alt_off, in->n_pairs, lo, limit);      // by chunk_bound per pair (sw_layout.h)
-        const int rc = run_chunk(c, params, in, Chunk(in, lo, hi), knobs, out);
+        const int rc = run_chunk(c, params, in, Chunk(in, lo, hi), knobs, out, src);
         if (rc) return rc;
     }
     return 0;
@@ -986,3 +1001,12 @@ int mgx_sw_stats(mgx_sw_t* c, mgx_sw_stats_t* out) {
 }
 
 }  // extern "C"
+
+namespace mgx_internal {
+int sw_align_from_device(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const SwDeviceSource& src,
+                         int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score) {
+    if (!src.gather) { set_error("NULL argument"); return -EINVAL; }
+    return align_impl(c, params, in, out_offset, out_cigar, cigar_stride, out_score, -1, &src);
+}
+SwView sw_view(mgx_sw_t* c) { return SwView{c->device, (c->flags & MGX_SW_LONG_REF) ? kMaxLen : kMaxRef, kMaxLen}; }
+}  // namespace mgx_internal

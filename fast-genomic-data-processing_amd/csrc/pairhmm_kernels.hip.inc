@@ -37,6 +37,8 @@
 
 #include <type_traits>
 
+#include "best_allele_rule.h"
+
 namespace {
 
 struct Job {
@@ -813,6 +815,42 @@ __global__ __launch_bounds__(256) void pairhmm_normalize_filter_rows(double* __r
         const double max_err = fmin(2.0, ceil((double)read_len[r] * max_error_per_base));
         keep[r] = !(best < max_err * -4.0);
     }
+}
+
+// one wavefront per read over its row of normalised log10 values: bestAllelesBreakingTies, i.e. searchBestAllele with
+// canBeReference = true (AlleleLikelihoods.h:92-146) as the two folds of best_allele_rule.h -- lanes stride the row and fold their
+// share, a butterfly of shuffles folds the lanes (both merges are commutative: every lane ends with the row's result).  Row r is
+// values[row_off[r] .. + row_nh[r]); its priorities are priority[pri_off[r] + h] (pri_off == nullptr: row_off), priority == nullptr
+// switches the tie-break off.
+__device__ __forceinline__ mgx_best_allele::Top shfl_xor_(mgx_best_allele::Top t, int off) {
+    return mgx_best_allele::Top{__shfl_xor(t.v, off, 64), (uint32_t)__shfl_xor((int)t.at, off, 64)};
+}
+__device__ __forceinline__ mgx_best_allele::Cand shfl_xor_(mgx_best_allele::Cand c, int off) {
+    return mgx_best_allele::Cand{__shfl_xor(c.pri, off, 64), (uint32_t)__shfl_xor((int)c.at, off, 64), (uint32_t)__shfl_xor((int)c.entered, off, 64)};
+}
+__global__ __launch_bounds__(256) void pairhmm_best_allele_rows(const double* __restrict__ values, const uint32_t* __restrict__ row_off,
+                                                                const uint32_t* __restrict__ row_nh, const double* __restrict__ priority,
+                                                                const uint32_t* __restrict__ pri_off, uint32_t n_rows, int32_t* __restrict__ out_best) {
+    namespace BA = mgx_best_allele;
+    const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= n_rows) return;
+    const uint32_t n_haps = row_nh[r];
+    const double* row = values + row_off[r];
+    BA::Top top = BA::top_identity();
+    for (uint32_t h = lane; h < n_haps; h += 64) top = BA::merge(top, BA::top_of(row[h], h));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) top = BA::merge(top, shfl_xor_(top, off));
+    uint32_t best = top.at == BA::kNone ? 0u : top.at;
+    if (priority && n_haps > 1) {
+        const double* pri = priority + (pri_off ? pri_off[r] : row_off[r]);
+        BA::Cand cand = BA::cand_identity();
+        for (uint32_t h = lane; h < n_haps; h += 64) cand = BA::merge(cand, BA::cand_of(top, BA::top_of(row[h], h).v, pri[h], h));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cand = BA::merge(cand, shfl_xor_(cand, off));
+        best = BA::result(top, pri[top.at], cand);
+    }
+    if (lane == 0) out_best[r] = (int32_t)best;
 }
 
 using KernelFn = void (*)(KernelArgs);

@@ -208,6 +208,24 @@ SMITHWATERMAN_SYMBOLS = {
 SYMBOLS.update(SMITHWATERMAN_SYMBOLS)
 
 
+# ---- include/mgx_realign.h ------------------------------------------------------------------------
+REALIGN_NOT_ALIGNED = -2 ** 31
+
+
+class RealignStats(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("n_verbatim", C.c_uint64), ("n_sw_pairs", C.c_uint64),
+                ("ms_best", C.c_float), ("ms_verbatim", C.c_float), ("ms_gather", C.c_float)]
+
+
+REALIGN_SYMBOLS = {
+    "mgx_pairhmm_best_alleles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_realign_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwParams),
+                                      C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mgx_realign_stats": (C.c_int, [C.c_void_p, C.POINTER(RealignStats)]),
+}
+SYMBOLS.update(REALIGN_SYMBOLS)
+
+
 # ---- include/mgx_bgzf.h ---------------------------------------------------------------------------
 class BgzfStats(C.Structure):
     _fields_ = [("n_blocks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("n_stored", C.c_uint64),

@@ -17,8 +17,9 @@
  * (PairWiseSW.h:31-66), the choice of the best end cell among equal scores in anti-diagonal order
  * (:256-285), the four overhang strategies, the back-trace state machine and the CIGAR text with
  * its capacity rule (:299-445; an element whose text would not fit the buffer is skipped).
- * The shortcut of SWNativeAlignerWrapper (alt found verbatim in ref -> "<altLength>M") stays host
- * code in the caller.
+ * The shortcut of SWNativeAlignerWrapper (alt found verbatim in ref -> "<altLength>M") is not part
+ * of these calls; mgx_realign_regions (mgx_realign.h) applies it on the device for reads against
+ * their best haplotype, any other caller keeps it as host code.
  *
  * Sequences are compared byte by byte (no base decoding), lengths are 1..2048 for ref and 1..32767
  * for alt; longer references are rejected with -E2BIG.  A context created with MGX_SW_LONG_REF takes
