@@ -1,6 +1,6 @@
 // bam_record_core.h -- the rules of a BAM alignment record (SAMv1 4.2) that BAM input needs, one text for
 // the host implementation (bam_host.cpp, which the CPU tests run under AddressSanitizer + UBSan) and for the device
-// kernels (mgx_bam.hip): when a record is valid, and what sorting and duplicate marking need from it (mgx_bam_key_t).
+// kernels (mgx_bam.hip, mgx_sam.hip): when a record is valid, and what sorting and duplicate marking need from it (mgx_bam_key_t).
 //
 // Plain C++, no library call.  Records sit at any byte offset: every multi-byte field is assembled from bytes.
 // The key rules restate base_quality_score / unclipped_five_prime / tile_x_y / token_to_u16 of sortdedup_pack.cpp, which
@@ -160,12 +160,10 @@ MGX_HD inline bool same_name(const uint8_t* a, const uint8_t* b) {
     return true;
 }
 
-// The whole key of the valid record at p; prev = the record before it in the call, or nullptr.
-MGX_HD inline void record_key(const uint8_t* p, const uint8_t* prev, mgx_bam_key_t* k) {
-    const Fixed f = read_fixed(p);
-    const uint8_t* name = p + kFixed;
-    const uint8_t* cig = name + f.l_read_name;
-    const uint8_t* qual = cig + 4ull * f.n_cigar + ((uint64_t)f.l_seq + 1) / 2;
+// The key of a valid record from its fixed part, name and CIGAR, with the two fields whose computation differs between
+// the callers handed in: the device kernel sums the qualities and compares the names eight lanes to a record.  (Hidden:
+// out of the library's symbol list where a compiler leaves it out of line.)
+__attribute__((visibility("hidden"))) MGX_HD inline void key_from(const Fixed& f, const uint8_t* name, const uint8_t* cig, uint16_t score, uint8_t same_qname, mgx_bam_key_t* k) {
     uint8_t redo = 0;
     int64_t d5, ref;
     cigar_keys(cig, f.n_cigar, (f.flag & 0x10u) == 0, f.l_seq, &d5, &ref, &redo);
@@ -173,11 +171,18 @@ MGX_HD inline void record_key(const uint8_t* p, const uint8_t* prev, mgx_bam_key
     name_keys(name, f.l_read_name - 1, t, &redo);
     k->d5 = d5; k->tid = f.tid; k->pos = f.pos;
     k->end = (int32_t)((int64_t)f.pos + (ref > 0 ? ref : 1));
-    k->flag = (uint16_t)f.flag;
-    k->score = score_bytes(qual, 0, (uint32_t)f.l_seq);
+    k->flag = (uint16_t)f.flag; k->score = score;
     k->tile = t[0]; k->x = t[1]; k->y = t[2];
-    k->same_qname = prev && same_name(p, prev) ? 1 : 0;
-    k->redo = redo;
+    k->same_qname = same_qname; k->redo = redo;
+}
+
+// The whole key of the valid record at p; prev = the record before it in the call, or nullptr.
+MGX_HD inline void record_key(const uint8_t* p, const uint8_t* prev, mgx_bam_key_t* k) {
+    const Fixed f = read_fixed(p);
+    const uint8_t* name = p + kFixed;
+    const uint8_t* cig = name + f.l_read_name;
+    const uint8_t* qual = cig + 4ull * f.n_cigar + ((uint64_t)f.l_seq + 1) / 2;
+    key_from(f, name, cig, score_bytes(qual, 0, (uint32_t)f.l_seq), prev && same_name(p, prev) ? 1 : 0, k);
 }
 
 }  // namespace mgx_bam

@@ -22,7 +22,8 @@
 // to do returns at once).
 //
 // Keys.  k_bam_keys: eight lanes per record read the qualities in 8-byte pieces and compare the name with the previous
-// record's, then reduce across the group; the group's first lane walks the CIGAR and the name's tokens.
+// record's, then reduce across the group; the group's first lane takes the rest of the key from key_from of
+// bam_record_core.h, as the host and SAM text input do.
 //
 // Corrupt input is a returned error (the host walk's message), never a fault: every read lies below n, every LDS index
 // below the staged range, every slot index below the tile's slot count.
@@ -35,22 +36,13 @@
 #include <cstring>
 #include <mutex>
 #include <new>
-#include <string>
 
 #include "../../include/mgx_bam.h"
 #include "bam_record_core.h"
 #include "mgx_bgzf_ctx.h"
-#include "mgx_common.h"
+#include "mgx_hip_util.h"
 
 using mgx::set_error;
-
-extern "C" const char* mgx_last_error(void);
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -EIO; } \
-    } while (0)
 
 namespace {
 
@@ -64,7 +56,7 @@ constexpr u32 kHalo = 320;                 // >= kMaxNameEnd: a record that star
 constexpr u32 kDefaultTile = 16384;     // measured: DESIGN.md 4.8 (index 1.8 ms per 512 MiB; 4096: 4.0, 1024: 14.2, 32768: 1.9)
 constexpr u32 kMinTile = 256, kMaxTile = 32768;
 constexpr u32 kRounds = 4;                 // stitch passes before the serial finish
-constexpr u32 kStitch = 256;               // threads (and tiles per step) of the stitch
+constexpr u32 kStitch = mgx_hip::kScanBlock;       // threads (and tiles per step) of the stitch
 constexpr u64 kNone = ~0ull;
 constexpr u32 kStEnd = 1;                  // the walk met a record that does not count: the chain ends at `exit`
 constexpr u32 kStErr = 0x100;              // ... an invalid record at `exit`: | Rule
@@ -133,16 +125,7 @@ __global__ __launch_bounds__(64) void k_bam_tiles(BamArgs a, int rewalk) {
         }
         __syncthreads();                                       // the LDS served the tile before
         for (u32 i = lane * 16; i < staged; i += 64 * 16) {
-            const u64 g = base + i;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (g + 16 <= a.n) v = *(const uint4*)(a.data + g);
-            else if (g < a.n) {                                // the last bytes of the data: zeros behind them
-                u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (u32 k = 0; k < 16; ++k) if (g + k < a.n) w[k / 4] |= (u32)a.data[g + k] << (8 * (k % 4));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            lds4[i / 16] = v;
+            lds4[i / 16] = mgx_hip::load16_below(a.data, base + i, a.n);      // the last bytes of the data: zeros behind them
         }
         __syncthreads();
         u64 entry = kNone;
@@ -229,15 +212,8 @@ __global__ __launch_bounds__(kStitch) void k_bam_stitch(BamArgs a) {
         }
         __syncthreads();
         if (fast && tid == 0) S.cur = e[min(kStitch, a.n_tiles - t0) - 1];
-        scan[tid] = eff[tid];
-        __syncthreads();
-        for (u32 d = 1; d < kStitch; d <<= 1) {
-            const u32 v = tid >= d ? scan[tid - d] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        if (valid) { a.eff[t] = eff[tid]; a.tbase[t] = S.total + scan[tid] - eff[tid]; }
+        const u32 before = mgx_hip::block_scan_exclusive(eff[tid], scan);
+        if (valid) { a.eff[t] = eff[tid]; a.tbase[t] = S.total + before; }
         __syncthreads();
         if (tid == 0) S.total += scan[kStitch - 1];
         __syncthreads();
@@ -316,19 +292,10 @@ __global__ __launch_bounds__(256) void k_bam_keys(BamArgs a) {
             eq &= (u32)__shfl_xor((int)eq, o, 64);
         }
         if (gl == 0) {
-            u8 redo = 0;
-            int64_t d5, ref;
-            cigar_keys(cig, f.n_cigar, (f.flag & 0x10u) == 0, f.l_seq, &d5, &ref, &redo);
-            u16 t[3];
-            name_keys(name, f.l_read_name - 1, t, &redo);
             mgx_bam_key_t k;
-            k.d5 = d5; k.tid = f.tid; k.pos = f.pos;
-            k.end = (int32_t)((int64_t)f.pos + (ref > 0 ? ref : 1));
-            k.flag = (u16)f.flag; k.score = (u16)score;
-            k.tile = t[0]; k.x = t[1]; k.y = t[2];
-            k.same_qname = (u8)eq; k.redo = redo;
+            key_from(f, name, cig, (u16)score, (u8)eq, &k);
             a.keys[i] = k;
-            if (redo) atomicAdd(&a.res->n_redo, 1u);
+            if (k.redo) atomicAdd(&a.res->n_redo, 1u);
         }
     }
 }
@@ -339,6 +306,7 @@ struct mgx_bam_batch {
     mgx_bgzf_inflate* inflate = nullptr;
     u64 cap = 0, max_records = 0; int32_t n_ref = 0;
     u32 tile = kDefaultTile, slots = 0, max_tiles = 0;
+    mgx_hip::Owner own;                                        // of every buffer and event below
     u8* h_in = nullptr; u8* d_in = nullptr;                    // a buffer of its own, when not attached
     BamArgs a{};                                               // the device arrays
     BamResult* h_res = nullptr; u64* h_rec_off = nullptr; mgx_bam_key_t* h_keys = nullptr;     // pinned
@@ -352,12 +320,7 @@ extern "C" {
 void mgx_bam_batch_destroy(mgx_bgzf_t* c, mgx_bam_batch_t* b) {
     if (!b) return;
     if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy); }
-    (void)hipHostFree(b->h_in); (void)hipHostFree(b->h_res); (void)hipHostFree(b->h_rec_off); (void)hipHostFree(b->h_keys);
-    (void)hipFree(b->d_in);
-    for (void* p : {(void*)b->a.guess, (void*)b->a.exit, (void*)b->a.entry, (void*)b->a.cnt, (void*)b->a.st, (void*)b->a.eff, (void*)b->a.tbase,
-                    (void*)b->a.list, (void*)b->a.slot, (void*)b->a.res, (void*)b->a.rec_off, (void*)b->a.keys}) (void)hipFree(p);
-    for (hipEvent_t e : {b->ev0, b->ev1, b->ev2, b->ev_res, b->ev_done}) if (e) (void)hipEventDestroy(e);
-    delete b;
+    delete b;                                                  // its owner frees
 }
 
 int mgx_bam_batch_create(mgx_bgzf_t* c, mgx_bgzf_inflate_t* inflate, uint64_t byte_capacity, uint64_t max_records, int32_t n_ref, mgx_bam_batch_t** out) {
@@ -379,19 +342,15 @@ int mgx_bam_batch_create(mgx_bgzf_t* c, mgx_bgzf_inflate_t* inflate, uint64_t by
     b->inflate = inflate; b->cap = byte_capacity; b->max_records = max_records; b->n_ref = n_ref;
     b->tile = tile; b->slots = tile / kMinRecord + 1; b->max_tiles = (u32)((byte_capacity + tile - 1) / tile);
     const size_t nt = std::max<u32>(b->max_tiles, 1), nr = std::max<u64>(max_records, 1);
-    bool ok = true;
-    auto dev = [&](auto** p, size_t bytes) { ok = ok && hipMalloc((void**)p, bytes) == hipSuccess; };
-    auto pin = [&](auto** p, size_t bytes) { ok = ok && hipHostMalloc((void**)p, bytes, hipHostMallocDefault) == hipSuccess; };
-    if (!inflate) { pin(&b->h_in, byte_capacity + 16); dev(&b->d_in, byte_capacity + 16); }
-    dev(&b->a.guess, nt * 8); dev(&b->a.exit, nt * 8); dev(&b->a.entry, nt * 8);
-    dev(&b->a.cnt, nt * 4); dev(&b->a.st, nt * 4); dev(&b->a.eff, nt * 4); dev(&b->a.tbase, nt * 4); dev(&b->a.list, nt * 4);
-    dev(&b->a.slot, nt * b->slots * 4); dev(&b->a.res, sizeof(BamResult));
-    dev(&b->a.rec_off, nr * 8); dev(&b->a.keys, nr * sizeof(mgx_bam_key_t));
-    pin(&b->h_res, sizeof(BamResult)); pin(&b->h_rec_off, nr * 8); pin(&b->h_keys, nr * sizeof(mgx_bam_key_t));
-    ok = ok && hipEventCreate(&b->ev0) == hipSuccess && hipEventCreate(&b->ev1) == hipSuccess && hipEventCreate(&b->ev2) == hipSuccess &&
-         hipEventCreateWithFlags(&b->ev_res, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
+    mgx_hip::Owner& m = b->own;
+    if (!inflate) { m.pin(&b->h_in, byte_capacity + 16); m.device(&b->d_in, byte_capacity + 16); }
+    m.device(&b->a.guess, nt * 8); m.device(&b->a.exit, nt * 8); m.device(&b->a.entry, nt * 8);
+    m.device(&b->a.cnt, nt * 4); m.device(&b->a.st, nt * 4); m.device(&b->a.eff, nt * 4); m.device(&b->a.tbase, nt * 4); m.device(&b->a.list, nt * 4);
+    m.device(&b->a.slot, nt * b->slots * 4); m.device(&b->a.res, sizeof(BamResult));
+    m.device(&b->a.rec_off, nr * 8); m.device(&b->a.keys, nr * sizeof(mgx_bam_key_t));
+    m.pin(&b->h_res, sizeof(BamResult)); m.pin(&b->h_rec_off, nr * 8); m.pin(&b->h_keys, nr * sizeof(mgx_bam_key_t));
+    m.event(&b->ev0); m.event(&b->ev1); m.event(&b->ev2); m.event(&b->ev_res, hipEventDisableTiming); m.event(&b->ev_done, hipEventDisableTiming);
+    if (!m.ok()) {
         set_error("allocation failed for a BAM batch of %llu bytes, %llu records", (unsigned long long)byte_capacity, (unsigned long long)max_records);
         mgx_bam_batch_destroy(c, b);
         return -ENOMEM;
@@ -483,10 +442,7 @@ int mgx_bam_scan(mgx_bgzf_t* c, const uint8_t* data, uint64_t n, uint64_t first,
         rc = mgx_bam_batch_wait(c, b, &ro, &k, n_records, next);
         if ((rc == 0 || rc == -EBADMSG) && *n_records) { memcpy(rec_off, ro, *n_records * 8); memcpy(keys, k, *n_records * sizeof(mgx_bam_key_t)); }
     }
-    const std::string msg = rc ? mgx_last_error() : "";
-    mgx_bam_batch_destroy(c, b);
-    if (rc) set_error("%s", msg.c_str());
-    return rc;
+    return mgx_hip::keep_error(rc, [&] { mgx_bam_batch_destroy(c, b); });
 }
 
 int mgx_bam_stats(mgx_bgzf_t* c, mgx_bam_stats_t* out) {

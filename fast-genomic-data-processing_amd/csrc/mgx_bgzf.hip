@@ -20,13 +20,11 @@
 //      modulo the CRC polynomial.
 // A finished block (18-byte BGZF header, payload, CRC, ISIZE) lands in a 64 KB slot; a scan over the sizes and a
 // copy kernel pack the slots back to back for ONE device-to-host copy.
+// The compressor only: the record store that feeds it from HBM is mgx_store.hip, through mgx_bgzf_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
 #include <cerrno>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -34,19 +32,11 @@
 #include <memory>
 #include <mutex>
 #include <new>
-#include <vector>
 
 #include "../../include/mgx_bgzf.h"
-#include "mgx_bgzf_ctx.h"
-#include "mgx_common.h"
+#include "mgx_bgzf_internal.h"
 
 using mgx::set_error;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -EIO; } \
-    } while (0)
 
 namespace {
 
@@ -870,83 +860,83 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const u8* slots, const u32* s
     }
 }
 
-// ---- the record store: records resident in HBM, emitted in sorted order ------------------------------------------
-constexpr u32 kScanTile = 4096;
-// slen[q] = 4 + len[order[q]] summed per tile of 4096 records
-__global__ __launch_bounds__(256) void k_store_tile_sums(const u32* order, const u32* len, u64 n, u64* tile_sum) {
-    __shared__ u64 part[256];
-    const u64 base = (u64)blockIdx.x * kScanTile;
-    u64 s = 0;
-    for (u32 i = threadIdx.x; i < kScanTile; i += 256) { const u64 q = base + i; if (q < n) s += 4u + len[order[q]]; }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) { if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off]; __syncthreads(); }
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = part[0];
-}
-__global__ __launch_bounds__(1024) void k_store_scan_tiles(u64* tile_sum, u32 n_tiles, u64* total) {      // one workgroup, in place, exclusive
-    __shared__ u64 part[1024];
-    const u32 per = (n_tiles + 1023) / 1024;
-    const u32 lo = min(n_tiles, threadIdx.x * per), hi = min(n_tiles, lo + per);
-    u64 s = 0;
-    for (u32 i = lo; i < hi; ++i) s += tile_sum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { u64 run = 0; for (int i = 0; i < 1024; ++i) { const u64 v = part[i]; part[i] = run; run += v; } *total = run; }
-    __syncthreads();
-    u64 run = part[threadIdx.x];
-    for (u32 i = lo; i < hi; ++i) { const u64 v = tile_sum[i]; tile_sum[i] = run; run += v; }
-}
-// uoff[q] = offset of record q (its block_size field) in the uncompressed stream
-__global__ __launch_bounds__(256) void k_store_offsets(const u32* order, const u32* len, u64 n, const u64* tile_base, u64* uoff) {
-    __shared__ u64 part[256];
-    const u64 base = (u64)blockIdx.x * kScanTile + (u64)threadIdx.x * 16u;
-    u32 l[16];
-    u64 s = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { const u64 q = base + i; l[i] = q < n ? 4u + len[order[q]] : 0u; s += l[i]; }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { u64 run = tile_base[blockIdx.x]; for (int i = 0; i < 256; ++i) { const u64 v = part[i]; part[i] = run; run += v; } }
-    __syncthreads();
-    u64 run = part[threadIdx.x];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { const u64 q = base + i; if (q < n) uoff[q] = run; run += l[i]; }
-}
-// One wavefront per record q in [q0, q1): block_size + bytes to their place in the window [win0, win0 + win_bytes) of the
-// stream; a duplicate gets FLAG |= 0x400 (byte 15 of the record, bit 2) on the way.
-__global__ __launch_bounds__(256) void k_store_gather(const u64* addr, const u32* len, const u32* order, const u8* dup, const u64* uoff,
-                                                      u64 q0, u64 q1, u64 win0, u64 win_bytes, u8* dst) {
-    const u64 q = q0 + (u64)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (q >= q1) return;
-    const u32 lane = threadIdx.x & 63u;
-    const u32 r = order[q];
-    const u32 n = len[r];
-    const u8* src = reinterpret_cast<const u8*>(addr[r]);
-    const u64 at = uoff[q];
-    const bool is_dup = dup[r] != 0;
-    for (u32 i = lane; i < n + 4u; i += 64u) {
-        const u64 o = at + i;
-        if (o < win0 || o >= win0 + win_bytes) continue;
-        u8 v;
-        if (i < 4) v = (u8)(n >> (8 * i));
-        else { v = src[i - 4]; if (is_dup && i == 4u + 15u) v |= 0x04; }
-        dst[o - win0] = v;
-    }
-}
-
 }  // namespace
 
-struct mgx_bgzf_batch {
-    u64 in_cap = 0; u32 max_blocks = 0;
-    u8* h_in = nullptr; u64* h_off = nullptr;          // pinned, filled by the caller
-    u8* h_out = nullptr; u64* h_out_off = nullptr;     // pinned, results
-    u8* d_in = nullptr; u64* d_off = nullptr; u8* d_slots = nullptr; u32* d_sizes = nullptr; u64* d_out_off = nullptr;
-    u64 out_cap = 0;
-    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_p0 = nullptr, ev_out = nullptr, ev_in = nullptr;
-    u8* h_out_dev = nullptr;                          // the pinned output buffer as the device addresses it
-    u32 n_blocks = 0; u64 n_in = 0;
-    bool submitted = false;
-};
+// ---- what the record store shares with the C ABI below (mgx_bgzf_internal.h) ----------------------------------------
+int mgx_internal::bgzf_batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint32_t max_blocks, bool pinned_input, mgx_bgzf_batch_t** out) {
+    if (!c || !out) { set_error("NULL argument"); return -EINVAL; }
+    *out = nullptr;
+    if (max_blocks == 0) { set_error("max_blocks is 0"); return -EINVAL; }
+    in_capacity = std::min<u64>(in_capacity, (u64)max_blocks * kMaxIn);
+    if (const int prc = mgx_bgzf_prepare(c)) return prc;
+    HIP_TRY(hipSetDevice(c->device));
+    mgx_bgzf_batch* b = new (std::nothrow) mgx_bgzf_batch;
+    if (!b) { set_error("out of memory"); return -ENOMEM; }
+    b->in_cap = in_capacity; b->max_blocks = max_blocks;
+    b->out_cap = mgx_bgzf_bound(in_capacity, max_blocks);
+    const size_t off_bytes = ((size_t)max_blocks + 1) * sizeof(u64);
+    mgx_hip::Owner& m = b->own;
+    if (pinned_input) m.pin(&b->h_in, in_capacity + 8);
+    m.pin(&b->h_off, off_bytes); m.pin(&b->h_out, b->out_cap); m.pin(&b->h_out_off, off_bytes);
+    m.device(&b->d_in, in_capacity + 8); m.device(&b->d_off, off_bytes); m.device(&b->d_slots, (size_t)max_blocks * kSlot);
+    m.device(&b->d_sizes, (size_t)max_blocks * sizeof(u32)); m.device(&b->d_out_off, off_bytes);
+    if (m.ok()) m.note(hipHostGetDevicePointer((void**)&b->h_out_dev, b->h_out, 0), "hipHostGetDevicePointer");
+    m.event(&b->ev_k0); m.event(&b->ev_k1); m.event(&b->ev_p0); m.event(&b->ev_out); m.event(&b->ev_in, hipEventDisableTiming);
+    if (!m.ok()) {
+        set_error("%s failed for a batch of %llu bytes / %u blocks", m.failed, (unsigned long long)in_capacity, max_blocks);
+        mgx_bgzf_batch_destroy(c, b);
+        return -ENOMEM;
+    }
+    b->h_off[0] = 0;
+    *out = b;
+    return 0;
+}
+
+// input_resident: the batch's device input buffer was filled by a kernel on the context's stream (the record store)
+int mgx_internal::bgzf_batch_submit(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, uint32_t n_blocks, bool input_resident) {
+    if (!c || !b) { set_error("NULL argument"); return -EINVAL; }
+    if (n_blocks > b->max_blocks) { set_error("%u blocks in a batch made for %u", n_blocks, b->max_blocks); return -EINVAL; }
+    if (b->h_off[0] != 0) { set_error("offsets[0] must be 0"); return -EINVAL; }
+    for (u32 i = 0; i < n_blocks; ++i) {
+        if (b->h_off[i + 1] < b->h_off[i] || b->h_off[i + 1] - b->h_off[i] > kMaxIn) {
+            set_error("block %u: [%llu, %llu) is not a piece of at most %u bytes", i, (unsigned long long)b->h_off[i], (unsigned long long)b->h_off[i + 1], kMaxIn);
+            return -EINVAL;
+        }
+    }
+    const u64 n_in = b->h_off[n_blocks];
+    if (n_in > b->in_cap) { set_error("%llu input bytes in a batch made for %llu", (unsigned long long)n_in, (unsigned long long)b->in_cap); return -EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    b->n_blocks = n_blocks; b->n_in = n_in; b->submitted = true;
+    if (n_blocks == 0) { b->h_out_off[0] = 0; return 0; }
+    hipStream_t s = c->stream;
+    if (!input_resident) {
+        // the input goes up on its own stream: on the kernel stream it would wait for the deflate kernels of the batches
+        // submitted before (d_in was last read by this batch's previous kernels, which its last wait() has seen finish)
+        HIP_TRY(hipMemcpyAsync(b->d_in, b->h_in, n_in, hipMemcpyHostToDevice, c->up));
+        HIP_TRY(hipEventRecord(b->ev_in, c->up));
+        HIP_TRY(hipStreamWaitEvent(s, b->ev_in, 0));
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_off, b->h_off, ((size_t)n_blocks + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
+    DeflateArgs a{};
+    a.in = b->d_in; a.off = b->d_off; a.n_blocks = n_blocks; a.slots = b->d_slots; a.sizes = b->d_sizes;
+    a.scratch = c->d_scratch; a.n_stored = c->d_n_stored; a.lazy = c->lazy; a.cost_base = c->cost_base; a.cost_rle = c->cost_rle; a.prof = c->d_prof;
+    HIP_TRY(hipEventRecord(b->ev_k0, s));
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(std::min(c->grid, n_blocks)), dim3(kNT), sizeof(Lds), s, a);
+    HIP_TRY(hipEventRecord(b->ev_k1, s));
+    // The finished blocks are packed STRAIGHT INTO THE PINNED OUTPUT BUFFER by the pack kernel, on the copy stream behind this
+    // batch's deflate kernel only: no packed copy in HBM and no device-to-host copy behind it (round 2's was carried out by
+    // a blit kernel that took 4.3 ms beside the next batch's deflate kernel and slowed that one from 3.0 to 4.1 ms:
+    // 20 GB/s pinned to pinned; tools trace in profiles/r03_bgzf_pipeline_trace.txt), and the next batch's deflate kernel
+    // does not queue behind the packing.
+    HIP_TRY(hipStreamWaitEvent(c->copy, b->ev_k1, 0));
+    HIP_TRY(hipEventRecord(b->ev_p0, c->copy));
+    hipLaunchKernelGGL(k_bgzf_offsets, dim3(1), dim3(256), 0, c->copy, b->d_sizes, n_blocks, b->d_out_off);
+    hipLaunchKernelGGL(k_bgzf_pack, dim3(std::min<u32>(n_blocks, (u32)c->n_cu)), dim3(256), 0, c->copy, b->d_slots, b->d_sizes, b->d_out_off, b->h_out_dev, n_blocks);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_out_off, b->d_out_off, ((size_t)n_blocks + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->copy));
+    HIP_TRY(hipEventRecord(b->ev_out, c->copy));
+    return 0;
+}
 
 extern "C" {
 
@@ -1041,101 +1031,17 @@ void mgx_bgzf_destroy(mgx_bgzf_t* c) {
 void mgx_bgzf_batch_destroy(mgx_bgzf_t* c, mgx_bgzf_batch_t* b) {
     if (!b) return;
     if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy); }
-    (void)hipHostFree(b->h_in); (void)hipHostFree(b->h_off); (void)hipHostFree(b->h_out); (void)hipHostFree(b->h_out_off);
-    (void)hipFree(b->d_in); (void)hipFree(b->d_off); (void)hipFree(b->d_slots); (void)hipFree(b->d_sizes); (void)hipFree(b->d_out_off);
-    if (b->ev_k0) (void)hipEventDestroy(b->ev_k0);
-    if (b->ev_k1) (void)hipEventDestroy(b->ev_k1);
-    if (b->ev_p0) (void)hipEventDestroy(b->ev_p0);
-    if (b->ev_out) (void)hipEventDestroy(b->ev_out);
-    if (b->ev_in) (void)hipEventDestroy(b->ev_in);
-    delete b;
+    delete b;                                          // its owner frees
 }
 
-static int batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint32_t max_blocks, bool pinned_input, mgx_bgzf_batch_t** out);
 int mgx_bgzf_batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint32_t max_blocks, mgx_bgzf_batch_t** out) {
-    return batch_create(c, in_capacity, max_blocks, true, out);
-}
-static int batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint32_t max_blocks, bool pinned_input, mgx_bgzf_batch_t** out) {
-    if (!c || !out) { set_error("NULL argument"); return -EINVAL; }
-    *out = nullptr;
-    if (max_blocks == 0) { set_error("max_blocks is 0"); return -EINVAL; }
-    in_capacity = std::min<u64>(in_capacity, (u64)max_blocks * kMaxIn);
-    if (const int prc = mgx_bgzf_prepare(c)) return prc;
-    HIP_TRY(hipSetDevice(c->device));
-    mgx_bgzf_batch* b = new (std::nothrow) mgx_bgzf_batch;
-    if (!b) { set_error("out of memory"); return -ENOMEM; }
-    b->in_cap = in_capacity; b->max_blocks = max_blocks;
-    b->out_cap = mgx_bgzf_bound(in_capacity, max_blocks);
-    auto fail = [&](const char* what) { set_error("%s failed for a batch of %llu bytes / %u blocks", what, (unsigned long long)in_capacity, max_blocks); mgx_bgzf_batch_destroy(c, b); return -ENOMEM; };
-    if (pinned_input && hipHostMalloc((void**)&b->h_in, in_capacity + 8, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_off, ((size_t)max_blocks + 1) * sizeof(u64), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_out, b->out_cap, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_out_off, ((size_t)max_blocks + 1) * sizeof(u64), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipMalloc((void**)&b->d_in, in_capacity + 8) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_off, ((size_t)max_blocks + 1) * sizeof(u64)) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_slots, (size_t)max_blocks * kSlot) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_sizes, (size_t)max_blocks * sizeof(u32)) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_out_off, ((size_t)max_blocks + 1) * sizeof(u64)) != hipSuccess) return fail("hipMalloc");
-    if (hipHostGetDevicePointer((void**)&b->h_out_dev, b->h_out, 0) != hipSuccess) return fail("hipHostGetDevicePointer");
-    if (hipEventCreate(&b->ev_k0) != hipSuccess || hipEventCreate(&b->ev_k1) != hipSuccess ||
-        hipEventCreate(&b->ev_p0) != hipSuccess ||
-        hipEventCreate(&b->ev_out) != hipSuccess ||
-        hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate");
-    b->h_off[0] = 0;
-    *out = b;
-    return 0;
+    return mgx_internal::bgzf_batch_create(c, in_capacity, max_blocks, true, out);
 }
 
 uint8_t* mgx_bgzf_batch_input(mgx_bgzf_batch_t* b) { return b ? b->h_in : nullptr; }
 uint64_t* mgx_bgzf_batch_offsets(mgx_bgzf_batch_t* b) { return b ? b->h_off : nullptr; }
 
-static int batch_submit(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, uint32_t n_blocks, bool input_resident);
-int mgx_bgzf_batch_submit(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, uint32_t n_blocks) { return batch_submit(c, b, n_blocks, false); }
-// input_resident: the batch's device input buffer was filled by a kernel on the context's stream (the record store)
-static int batch_submit(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, uint32_t n_blocks, bool input_resident) {
-    if (!c || !b) { set_error("NULL argument"); return -EINVAL; }
-    if (n_blocks > b->max_blocks) { set_error("%u blocks in a batch made for %u", n_blocks, b->max_blocks); return -EINVAL; }
-    if (b->h_off[0] != 0) { set_error("offsets[0] must be 0"); return -EINVAL; }
-    for (u32 i = 0; i < n_blocks; ++i) {
-        if (b->h_off[i + 1] < b->h_off[i] || b->h_off[i + 1] - b->h_off[i] > kMaxIn) {
-            set_error("block %u: [%llu, %llu) is not a piece of at most %u bytes", i, (unsigned long long)b->h_off[i], (unsigned long long)b->h_off[i + 1], kMaxIn);
-            return -EINVAL;
-        }
-    }
-    const u64 n_in = b->h_off[n_blocks];
-    if (n_in > b->in_cap) { set_error("%llu input bytes in a batch made for %llu", (unsigned long long)n_in, (unsigned long long)b->in_cap); return -EINVAL; }
-    HIP_TRY(hipSetDevice(c->device));
-    b->n_blocks = n_blocks; b->n_in = n_in; b->submitted = true;
-    if (n_blocks == 0) { b->h_out_off[0] = 0; return 0; }
-    hipStream_t s = c->stream;
-    if (!input_resident) {
-        // the input goes up on its own stream: on the kernel stream it would wait for the deflate kernels of the batches
-        // submitted before (d_in was last read by this batch's previous kernels, which its last wait() has seen finish)
-        HIP_TRY(hipMemcpyAsync(b->d_in, b->h_in, n_in, hipMemcpyHostToDevice, c->up));
-        HIP_TRY(hipEventRecord(b->ev_in, c->up));
-        HIP_TRY(hipStreamWaitEvent(s, b->ev_in, 0));
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_off, b->h_off, ((size_t)n_blocks + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
-    DeflateArgs a{};
-    a.in = b->d_in; a.off = b->d_off; a.n_blocks = n_blocks; a.slots = b->d_slots; a.sizes = b->d_sizes;
-    a.scratch = c->d_scratch; a.n_stored = c->d_n_stored; a.lazy = c->lazy; a.cost_base = c->cost_base; a.cost_rle = c->cost_rle; a.prof = c->d_prof;
-    HIP_TRY(hipEventRecord(b->ev_k0, s));
-    hipLaunchKernelGGL(k_bgzf_deflate, dim3(std::min(c->grid, n_blocks)), dim3(kNT), sizeof(Lds), s, a);
-    HIP_TRY(hipEventRecord(b->ev_k1, s));
-    // The finished blocks are packed STRAIGHT INTO THE PINNED OUTPUT BUFFER by the pack kernel, on the copy stream behind this
-    // batch's deflate kernel only: no packed copy in HBM and no device-to-host copy behind it (round 2's was carried out by
-    // a blit kernel that took 4.3 ms beside the next batch's deflate kernel and slowed that one from 3.0 to 4.1 ms:
-    // 20 GB/s pinned to pinned; tools trace in profiles/r03_bgzf_pipeline_trace.txt), and the next batch's deflate kernel
-    // does not queue behind the packing.
-    HIP_TRY(hipStreamWaitEvent(c->copy, b->ev_k1, 0));
-    HIP_TRY(hipEventRecord(b->ev_p0, c->copy));
-    hipLaunchKernelGGL(k_bgzf_offsets, dim3(1), dim3(256), 0, c->copy, b->d_sizes, n_blocks, b->d_out_off);
-    hipLaunchKernelGGL(k_bgzf_pack, dim3(std::min<u32>(n_blocks, (u32)c->n_cu)), dim3(256), 0, c->copy, b->d_slots, b->d_sizes, b->d_out_off, b->h_out_dev, n_blocks);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_out_off, b->d_out_off, ((size_t)n_blocks + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->copy));
-    HIP_TRY(hipEventRecord(b->ev_out, c->copy));
-    return 0;
-}
+int mgx_bgzf_batch_submit(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, uint32_t n_blocks) { return mgx_internal::bgzf_batch_submit(c, b, n_blocks, false); }
 
 int mgx_bgzf_batch_wait(mgx_bgzf_t* c, mgx_bgzf_batch_t* b, const uint8_t** out, const uint64_t** out_offsets) {
     if (!c || !b || !out || !out_offsets) { set_error("NULL argument"); return -EINVAL; }
@@ -1200,214 +1106,6 @@ int mgx_bgzf_compress(mgx_bgzf_t* c, const uint8_t* in, const uint64_t* offsets,
     if (!rc) rc = drain(k);
     if (!rc) rc = drain(k ^ 1);
     for (int i = 0; i < 2; ++i) mgx_bgzf_batch_destroy(c, bt[i]);
-    return rc;
-}
-
-// ---- record store ---------------------------------------------------------------------------------------------------
-struct mgx_bgzf_store {
-    mgx_bgzf* ctx = nullptr;
-    std::mutex mu;
-    std::vector<u8*> chunks;
-    u64 cur_off = 0, cur_cap = 0, total = 0;
-    // put() stages through pinned buffers of its own (a copy from pageable memory is slow and serialises the callers)
-    // and copies on streams of its own, never on the null stream (which would wait for every blocking stream of the process)
-    static constexpr int kStage = 24;
-    static constexpr size_t kStageBytes = 4u << 20;
-    hipStream_t copy[kStage] = {};
-    u8* stage[kStage] = {};                    // pinned, allocated by the first put that takes the slot (in parallel, off create's path)
-    std::mutex stage_mu; std::condition_variable stage_cv;
-    std::vector<int> stage_free;
-};
-
-int mgx_bgzf_store_create(mgx_bgzf_t* c, mgx_bgzf_store_t** out) {
-    if (!c || !out) { set_error("NULL argument"); return -EINVAL; }
-    *out = nullptr;
-    mgx_bgzf_store* st = new (std::nothrow) mgx_bgzf_store;
-    if (!st) { set_error("out of memory"); return -ENOMEM; }
-    st->ctx = c;
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) {
-        set_error("record store: %s", hipGetErrorString(e));
-        mgx_bgzf_store_destroy(st);
-        return -EIO;
-    }
-    // a slot's stream and pinned buffer are made by the first put that takes the slot: in parallel on the callers'
-    // threads instead of 24 stream creations and 96 MB of page pinning in front of the first put
-    for (int i = 0; i < mgx_bgzf_store::kStage; ++i) st->stage_free.push_back(mgx_bgzf_store::kStage - 1 - i);
-    *out = st;
-    return 0;
-}
-
-// Allocates HBM for about `bytes` more record bytes now (1 GB pieces), so that the puts of the first slices do not wait
-// for hipMalloc one after the other.
-int mgx_bgzf_store_reserve(mgx_bgzf_store_t* st, uint64_t bytes) {
-    if (!st) { set_error("NULL argument"); return -EINVAL; }
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    std::lock_guard<std::mutex> g(st->mu);
-    if (!st->chunks.empty() || bytes == 0) return 0;
-    const u64 cap = std::min<u64>(std::max<u64>((bytes + 15) & ~15ull, 64ull << 20), 256ull << 20);      // a first piece that is quick to map
-    u8* p = nullptr;
-    if (hipMalloc((void**)&p, cap) != hipSuccess) { set_error("hipMalloc of %llu bytes for the record store failed", (unsigned long long)cap); return -ENOMEM; }
-    st->chunks.push_back(p); st->cur_off = 0; st->cur_cap = cap;
-    return 0;
-}
-
-void mgx_bgzf_store_destroy(mgx_bgzf_store_t* st) {
-    if (!st) return;
-    (void)hipSetDevice(st->ctx->device);
-    for (u8* p : st->chunks) (void)hipFree(p);
-    for (auto& sc : st->copy) if (sc) (void)hipStreamDestroy(sc);
-    for (auto& p : st->stage) if (p) (void)hipHostFree(p);
-    delete st;
-}
-
-// n bytes of the store's HBM (1 GB pieces; a put never straddles two), 16-byte aligned
-static int store_alloc(mgx_bgzf_store* st, u64 n, u8** dst) {
-    std::lock_guard<std::mutex> g(st->mu);
-    const u64 need = (n + 15) & ~15ull;
-    if (st->cur_off + need > st->cur_cap) {
-        const u64 cap = std::max<u64>(need, 1ull << 30);
-        u8* p = nullptr;
-        if (hipMalloc((void**)&p, cap) != hipSuccess) { set_error("hipMalloc of %llu bytes for the record store failed (%llu bytes stored)", (unsigned long long)cap, (unsigned long long)st->total); return -ENOMEM; }
-        st->chunks.push_back(p); st->cur_off = 0; st->cur_cap = cap;
-    }
-    *dst = st->chunks.back() + st->cur_off;
-    st->cur_off += need; st->total += n;
-    return 0;
-}
-
-static int store_take_slot(mgx_bgzf_store* st) {
-    std::unique_lock<std::mutex> lk(st->stage_mu);
-    st->stage_cv.wait(lk, [&] { return !st->stage_free.empty(); });
-    const int k = st->stage_free.back(); st->stage_free.pop_back();
-    return k;
-}
-
-static void store_give_slot(mgx_bgzf_store* st, int k) {
-    { std::lock_guard<std::mutex> g(st->stage_mu); st->stage_free.push_back(k); }
-    st->stage_cv.notify_one();
-}
-
-int mgx_bgzf_store_put_device(mgx_bgzf_store_t* st, uint64_t device_ptr, uint64_t n, uint64_t* addr) {
-    if (!st || !addr || (n && !device_ptr)) { set_error("NULL argument"); return -EINVAL; }
-    if (n == 0) { *addr = 0; return 0; }
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    u8* dst;
-    if (const int rc = store_alloc(st, n, &dst)) return rc;
-    const int k = store_take_slot(st);             // for the slot's stream: nothing is staged
-    hipError_t e = hipSuccess;
-    if (!st->copy[k]) e = hipStreamCreateWithFlags(&st->copy[k], hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, (const void*)(uintptr_t)device_ptr, n, hipMemcpyDeviceToDevice, st->copy[k]);
-    if (e == hipSuccess) e = hipStreamSynchronize(st->copy[k]);
-    store_give_slot(st, k);
-    if (e != hipSuccess) { set_error("copy of %llu device bytes to the record store: %s", (unsigned long long)n, hipGetErrorString(e)); return -EIO; }
-    *addr = (uint64_t)(uintptr_t)dst;
-    return 0;
-}
-
-int mgx_bgzf_store_put(mgx_bgzf_store_t* st, const uint8_t* bytes, uint64_t n, uint64_t* addr) {
-    if (!st || !addr || (n && !bytes)) { set_error("NULL argument"); return -EINVAL; }
-    if (n == 0) { *addr = 0; return 0; }           // nothing to store (a slice of blank lines); no chunk is touched
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    u8* dst;
-    if (const int rc = store_alloc(st, n, &dst)) return rc;
-    for (u64 done = 0; done < n;) {
-        const int k = store_take_slot(st);
-        const u64 piece = std::min<u64>(mgx_bgzf_store::kStageBytes, n - done);
-        hipError_t e = hipSuccess;
-        if (!st->copy[k]) e = hipStreamCreateWithFlags(&st->copy[k], hipStreamNonBlocking);                                     // this slot's first use
-        if (e == hipSuccess && !st->stage[k]) e = hipHostMalloc((void**)&st->stage[k], mgx_bgzf_store::kStageBytes, hipHostMallocDefault);
-        if (e == hipSuccess) {
-            memcpy(st->stage[k], bytes + done, piece);
-            e = hipMemcpyAsync(dst + done, st->stage[k], piece, hipMemcpyHostToDevice, st->copy[k]);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st->copy[k]);
-        store_give_slot(st, k);
-        if (e != hipSuccess) { set_error("copy of %llu bytes to the record store: %s", (unsigned long long)piece, hipGetErrorString(e)); return -EIO; }
-        done += piece;
-    }
-    *addr = (uint64_t)(uintptr_t)dst;
-    return 0;
-}
-
-int mgx_bgzf_store_emit(mgx_bgzf_store_t* st, uint64_t n, const uint32_t* order, const uint8_t* dup, const uint64_t* addr, const uint32_t* len,
-                        mgx_bgzf_sink_t sink, void* user, uint64_t* uoff_out) {
-    if (!st || !sink || !uoff_out || (n && (!order || !dup || !addr || !len))) { set_error("NULL argument"); return -EINVAL; }
-    mgx_bgzf* c = st->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool trace = getenv("MGX_BGZF_TRACE") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto now = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
-    uoff_out[0] = 0;
-    if (n == 0) return 0;
-    if (n > 0xFFFFFFF0ull) { set_error("more than 2^32 records"); return -E2BIG; }
-    hipStream_t s = c->stream;
-    u32 *d_order = nullptr, *d_len = nullptr; u8* d_dup = nullptr; u64 *d_addr = nullptr, *d_uoff = nullptr, *d_tiles = nullptr;
-    const u32 n_tiles = (u32)((n + kScanTile - 1) / kScanTile);
-    int rc = 0;
-    mgx_bgzf_batch_t* bt[3] = {nullptr, nullptr, nullptr};
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(d_order); (void)hipFree(d_len); (void)hipFree(d_dup); (void)hipFree(d_addr); (void)hipFree(d_uoff); (void)hipFree(d_tiles);
-        for (auto* b : bt) if (b) mgx_bgzf_batch_destroy(c, b);
-    };
-#define STORE_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); cleanup(); return -EIO; } } while (0)
-    STORE_TRY(hipMalloc((void**)&d_order, n * sizeof(u32)));
-    STORE_TRY(hipMalloc((void**)&d_len, n * sizeof(u32)));
-    STORE_TRY(hipMalloc((void**)&d_dup, n));
-    STORE_TRY(hipMalloc((void**)&d_addr, n * sizeof(u64)));
-    STORE_TRY(hipMalloc((void**)&d_uoff, (n + 1) * sizeof(u64)));
-    STORE_TRY(hipMalloc((void**)&d_tiles, ((size_t)n_tiles + 1) * sizeof(u64)));
-    STORE_TRY(hipMemcpyAsync(d_order, order, n * sizeof(u32), hipMemcpyHostToDevice, s));
-    STORE_TRY(hipMemcpyAsync(d_len, len, n * sizeof(u32), hipMemcpyHostToDevice, s));
-    STORE_TRY(hipMemcpyAsync(d_dup, dup, n, hipMemcpyHostToDevice, s));
-    STORE_TRY(hipMemcpyAsync(d_addr, addr, n * sizeof(u64), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_store_tile_sums, dim3(n_tiles), dim3(256), 0, s, d_order, d_len, n, d_tiles);
-    hipLaunchKernelGGL(k_store_scan_tiles, dim3(1), dim3(1024), 0, s, d_tiles, n_tiles, d_uoff + n);
-    hipLaunchKernelGGL(k_store_offsets, dim3(n_tiles), dim3(256), 0, s, d_order, d_len, n, d_tiles, d_uoff);
-    STORE_TRY(hipGetLastError());
-    STORE_TRY(hipMemcpyAsync(uoff_out, d_uoff, (n + 1) * sizeof(u64), hipMemcpyDeviceToHost, s));
-    STORE_TRY(hipStreamSynchronize(s));
-    const u64 total = uoff_out[n];
-    double t_wait = 0, t_sink = 0;
-    if (trace) fprintf(stderr, "  store_emit: arrays on the device, offsets scanned and back: %.3f s\n", now());
-    constexpr u32 kPer = 1024;                                    // blocks per batch (67 MB of the stream)
-    const u64 win = (u64)kPer * kMaxIn;
-    const u64 n_win = (total + win - 1) / win;
-    for (int i = 0; i < 3 && !rc && (u64)i < n_win; ++i) rc = batch_create(c, win, kPer, false, &bt[i]);
-    if (rc) { cleanup(); return rc; }
-    if (trace) fprintf(stderr, "  store_emit: batches allocated: %.3f s\n", now());
-    auto collect = [&](u64 k) -> int {
-        const uint8_t* o; const uint64_t* oo;
-        mgx_bgzf_batch_t* b = bt[k % 3];
-        const double t0 = now();
-        const int r = mgx_bgzf_batch_wait(c, b, &o, &oo);
-        if (r) return r;
-        const double t1 = now();
-        const int sr = sink(user, o, oo[b->n_blocks], b->n_blocks, oo);
-        t_wait += t1 - t0; t_sink += now() - t1;
-        if (sr) { set_error("the sink returned %d", sr); return -EIO; }
-        return 0;
-    };
-    u64 q_lo = 0;
-    for (u64 k = 0; k < n_win && !rc; ++k) {
-        if (k >= 3) rc = collect(k - 3);
-        if (rc) break;
-        mgx_bgzf_batch_t* b = bt[k % 3];
-        const u64 w0 = k * win, wb = std::min(win, total - w0);
-        // records that touch [w0, w0 + wb): from the one holding byte w0 to the last one starting before the window's end
-        while (q_lo + 1 <= n && uoff_out[q_lo + 1] <= w0) ++q_lo;
-        const u64 q_hi = (u64)(std::lower_bound(uoff_out + q_lo, uoff_out + n, w0 + wb) - uoff_out);
-        const u32 nb = (u32)((wb + kMaxIn - 1) / kMaxIn);
-        for (u32 i = 0; i <= nb; ++i) b->h_off[i] = std::min<u64>((u64)i * kMaxIn, wb);
-        if (q_hi > q_lo)
-            hipLaunchKernelGGL(k_store_gather, dim3((u32)((q_hi - q_lo + 3) / 4)), dim3(256), 0, s, d_addr, d_len, d_order, d_dup, d_uoff, q_lo, q_hi, w0, wb, b->d_in);
-        rc = batch_submit(c, b, nb, true);
-    }
-    for (u64 k = n_win >= 3 ? n_win - 3 : 0; k < n_win && !rc; ++k) rc = collect(k);
-    if (trace) fprintf(stderr, "  store_emit: %llu windows done: %.3f s (waiting for the device %.3f s, in the sink %.3f s)\n", (unsigned long long)n_win, now(), t_wait, t_sink);
-#undef STORE_TRY
-    cleanup();
     return rc;
 }
 

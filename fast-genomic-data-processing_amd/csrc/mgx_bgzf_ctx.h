@@ -1,11 +1,12 @@
 // mgx_bgzf_ctx.h -- the BGZF context (include/mgx_bgzf.h) as its translation units see it: the compressor
-// (mgx_bgzf.hip), the inflater (mgx_bgzf_inflate.hip) and BAM input (mgx_bam.hip) share its device and streams, and BAM
-// input reads an inflate batch's output where the inflate kernel left it.
+// (mgx_bgzf.hip), the record store (mgx_store.hip), the inflater (mgx_bgzf_inflate.hip), BAM input (mgx_bam.hip) and SAM
+// text input (mgx_sam.hip) share its device and streams, and BAM input reads an inflate batch's output where the inflate
+// kernel left it.  What the record store reaches of the compressor's batches is in mgx_bgzf_internal.h.
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
 #include <mutex>
+
+#include "mgx_hip_util.h"
 
 struct mgx_bgzf {
     int device = 0;
@@ -37,6 +38,7 @@ struct mgx_bgzf {
 
 struct mgx_bgzf_inflate {
     uint64_t in_cap = 0, out_cap = 0; uint32_t max_blocks = 0;
+    mgx_hip::Owner own;                        // of every buffer and event below
     uint8_t* h_in = nullptr; uint64_t* h_off = nullptr; uint8_t* h_out = nullptr; uint32_t* h_status = nullptr;      // pinned
     uint8_t* d_in = nullptr; uint64_t* d_off = nullptr; uint8_t* d_out = nullptr; uint32_t* d_status = nullptr;
     hipEvent_t ev_in = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr;

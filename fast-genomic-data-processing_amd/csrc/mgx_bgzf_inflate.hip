@@ -32,15 +32,8 @@
 #include "../../include/mgx_bgzf.h"
 #include "bgzf_inflate_core.h"
 #include "mgx_bgzf_ctx.h"
-#include "mgx_common.h"
 
 using mgx::set_error;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -EIO; } \
-    } while (0)
 
 namespace {
 
@@ -191,10 +184,7 @@ extern "C" {
 void mgx_bgzf_inflate_batch_destroy(mgx_bgzf_t* c, mgx_bgzf_inflate_t* b) {
     if (!b) return;
     if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy); }
-    (void)hipHostFree(b->h_in); (void)hipHostFree(b->h_off); (void)hipHostFree(b->h_out); (void)hipHostFree(b->h_status);
-    (void)hipFree(b->d_in); (void)hipFree(b->d_off); (void)hipFree(b->d_out); (void)hipFree(b->d_status);
-    for (hipEvent_t e : {b->ev_in, b->ev_k0, b->ev_k1, b->ev_done}) if (e) (void)hipEventDestroy(e);
-    delete b;
+    delete b;                                              // its owner frees
 }
 
 int mgx_bgzf_inflate_batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint64_t out_capacity, uint32_t max_blocks, mgx_bgzf_inflate_t** out) {
@@ -207,22 +197,16 @@ int mgx_bgzf_inflate_batch_create(mgx_bgzf_t* c, uint64_t in_capacity, uint64_t 
     mgx_bgzf_inflate* b = new (std::nothrow) mgx_bgzf_inflate;
     if (!b) { set_error("out of memory"); return -ENOMEM; }
     b->in_cap = in_capacity; b->out_cap = out_capacity; b->max_blocks = max_blocks;
-    auto fail = [&](const char* what) {
-        set_error("%s failed for an inflate batch of %llu / %llu bytes, %u blocks", what, (unsigned long long)in_capacity, (unsigned long long)out_capacity, max_blocks);
+    const size_t off_bytes = 2 * ((size_t)max_blocks + 1) * sizeof(u64);
+    mgx_hip::Owner& m = b->own;
+    m.pin(&b->h_in, in_capacity + 8); m.pin(&b->h_off, off_bytes); m.pin(&b->h_out, out_capacity + 8); m.pin(&b->h_status, (size_t)max_blocks * sizeof(u32));
+    m.device(&b->d_in, in_capacity + 8); m.device(&b->d_off, off_bytes); m.device(&b->d_out, out_capacity + 8); m.device(&b->d_status, (size_t)max_blocks * sizeof(u32));
+    m.event(&b->ev_in, hipEventDisableTiming); m.event(&b->ev_k0); m.event(&b->ev_k1); m.event(&b->ev_done, hipEventDisableTiming);
+    if (!m.ok()) {
+        set_error("%s failed for an inflate batch of %llu / %llu bytes, %u blocks", m.failed, (unsigned long long)in_capacity, (unsigned long long)out_capacity, max_blocks);
         mgx_bgzf_inflate_batch_destroy(c, b);
         return -ENOMEM;
-    };
-    const size_t off_bytes = 2 * ((size_t)max_blocks + 1) * sizeof(u64);
-    if (hipHostMalloc((void**)&b->h_in, in_capacity + 8, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_off, off_bytes, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_out, out_capacity + 8, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void**)&b->h_status, (size_t)max_blocks * sizeof(u32), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipMalloc((void**)&b->d_in, in_capacity + 8) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_off, off_bytes) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_out, out_capacity + 8) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&b->d_status, (size_t)max_blocks * sizeof(u32)) != hipSuccess) return fail("hipMalloc");
-    if (hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreate(&b->ev_k0) != hipSuccess ||
-        hipEventCreate(&b->ev_k1) != hipSuccess || hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate");
+    }
     b->h_off[0] = 0; b->h_off[max_blocks + 1] = 0;
     *out = b;
     return 0;

@@ -2,7 +2,7 @@
 // BAM records with their sort / duplicate keys, by the rule set of sam_line_core.h, which the host implementation
 // (sam_host.cpp) compiles too and which defines the result.
 //
-// The phases of a submit, each a launch (the scans three), enqueued without a host round trip; no kernel waits for
+// The phases of a submit, each a launch (the scans three: mgx_scan.h), enqueued without a host round trip; no kernel waits for
 // another workgroup:
 //   k_sam_lines (count)   one wavefront per tile of MGX_SAM_TILE bytes, 16 bytes per lane and step (1 KiB per wavefront
 //                         load).  A lane sees the two bytes before and the byte after its 16 through its neighbours'
@@ -32,24 +32,15 @@
 #include <cstring>
 #include <mutex>
 #include <new>
-#include <string>
 
 #include "../../include/mgx_sam.h"
 #include "bam_record_core.h"
 #include "mgx_bgzf_ctx.h"
-#include "mgx_common.h"
+#include "mgx_scan.h"
 #include "sam_host.h"
 #include "sam_line_core.h"
 
 using mgx::set_error;
-
-extern "C" const char* mgx_last_error(void);
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -EIO; } \
-    } while (0)
 
 namespace {
 
@@ -57,12 +48,12 @@ typedef uint8_t u8;
 typedef uint32_t u32;
 typedef uint64_t u64;
 using namespace mgx_sam;
+using namespace mgx_hip;
 
 constexpr u32 kDefaultTile = 16384, kMinTile = 256, kMaxTile = 32768;      // not measured against each other
 constexpr u32 kGroup = 16;                 // lanes per line (eight were not measured against it)
 constexpr u32 kBlock = 256, kGroups = kBlock / kGroup;
 constexpr u32 kStage16 = (kMaxLine + 15 + 15) / 16 + 1;                     // 16-byte pieces of a staged line at any alignment
-constexpr u32 kScanPer = 16, kScanChunk = kBlock * kScanPer;               // elements per thread / per workgroup of a scan
 
 struct SamResult { u64 n_lines, n_ends, n_out; u32 n_declined, pad; };
 
@@ -93,14 +84,7 @@ __global__ __launch_bounds__(64) void k_sam_lines(SamArgs a, int pass) {
         if (pass) { const u64 b = a.tile_base[t]; at_start = b & 0xFFFFFFFFu; at_end = b >> 32; }
         for (u32 s = 0; s < a.tile; s += 64 * 16) {
             const u64 g = base + s + (u64)lane * 16;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (g + 16 <= a.n) v = *(const uint4*)(a.text + g);
-            else if (g < a.n) {
-                u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (u32 k = 0; k < 16; ++k) if (g + k < a.n) w[k / 4] |= (u32)a.text[g + k] << (8 * (k % 4));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
+            const uint4 v = load16_below(a.text, g, a.n);
             u32 before = (u32)__shfl_up((int)v.w, 1, 64), after = (u32)__shfl_down((int)v.x, 1, 64);
             if (lane == 0) before = (g >= 4 && g <= a.n) ? *(const u32*)(a.text + g - 4) : 0u;    // g is a multiple of 16: bytes [g - 4, g) lie below n
             if (lane == 63) after = g + 16 < a.n ? (u32)a.text[g + 16] : 0u;
@@ -138,82 +122,6 @@ __global__ __launch_bounds__(64) void k_sam_lines(SamArgs a, int pass) {
     }
 }
 
-// ---- exclusive scan of v[0, n) into out[0, n], n = min(*n_dev, n_max) (n_dev may be NULL), in three launches -----------
-__device__ u64 scan_count(const u64* n_dev, u64 n_max) { return n_dev ? min(*n_dev, n_max) : n_max; }
-
-__device__ u64 block_sum(u64 v, u64* sh) {                     // sh: kBlock words; returns the sum to every thread
-    const u32 tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (u32 d = kBlock / 2; d >= 1; d >>= 1) { if (tid < d) sh[tid] += sh[tid + d]; __syncthreads(); }
-    const u64 r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_scan_sums(const T* v, const u64* n_dev, u64 n_max, u64* part) {
-    __shared__ u64 sh[kBlock];
-    const u64 n = scan_count(n_dev, n_max);
-    const u64 lo = (u64)blockIdx.x * kScanChunk;
-    if (lo >= n && blockIdx.x) return;                         // uniform
-    u64 s = 0;
-    for (u32 k = 0; k < kScanPer; ++k) { const u64 i = lo + (u64)threadIdx.x * kScanPer + k; if (i < n) s += v[i]; }
-    const u64 r = block_sum(s, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_parts(const u64* n_dev, u64 n_max, u64* part) {      // one workgroup, in place, exclusive
-    __shared__ u64 sh[kBlock];
-    __shared__ u64 carry;
-    const u64 n = scan_count(n_dev, n_max);
-    const u64 n_parts = (n + kScanChunk - 1) / kScanChunk;
-    const u32 tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (u64 p0 = 0; p0 < n_parts; p0 += kBlock) {
-        const u64 i = p0 + tid;
-        const u64 mine = i < n_parts ? part[i] : 0;
-        sh[tid] = mine;
-        __syncthreads();
-        for (u32 d = 1; d < kBlock; d <<= 1) {
-            const u64 o = tid >= d ? sh[tid - d] : 0;
-            __syncthreads();
-            sh[tid] += o;
-            __syncthreads();
-        }
-        if (i < n_parts) part[i] = carry + sh[tid] - mine;
-        __syncthreads();
-        if (tid == 0) carry += sh[kBlock - 1];
-        __syncthreads();
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_scan_write(const T* v, const u64* n_dev, u64 n_max, const u64* part, u64* out) {
-    __shared__ u64 sh[kBlock];
-    const u64 n = scan_count(n_dev, n_max);
-    const u64 lo = (u64)blockIdx.x * kScanChunk;
-    if (n == 0) { if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = 0; return; }
-    if (lo >= n) return;                                       // uniform
-    const u32 tid = threadIdx.x;
-    u64 x[kScanPer], s = 0;
-    for (u32 k = 0; k < kScanPer; ++k) { const u64 i = lo + (u64)tid * kScanPer + k; x[k] = i < n ? (u64)v[i] : 0; s += x[k]; }
-    sh[tid] = s;
-    __syncthreads();
-    for (u32 d = 1; d < kBlock; d <<= 1) {
-        const u64 o = tid >= d ? sh[tid - d] : 0;
-        __syncthreads();
-        sh[tid] += o;
-        __syncthreads();
-    }
-    u64 run = part[blockIdx.x] + sh[tid] - s;
-    for (u32 k = 0; k < kScanPer; ++k) {
-        const u64 i = lo + (u64)tid * kScanPer + k;
-        if (i < n) { out[i] = run; run += x[k]; if (i + 1 == n) out[n] = run; }
-    }
-}
-
 // the tile scan's total is the number of lines
 __global__ void k_sam_counts(SamArgs a) {
     if (threadIdx.x || blockIdx.x) return;
@@ -233,14 +141,7 @@ __device__ u32 stage_line(const SamArgs& a, u64 off, u32 len, uint4* S, u32 gl) 
     const u32 o = (u32)(off - a0);
     for (u32 c = gl * 16; c < o + len; c += kGroup * 16) {
         const u64 g = a0 + c;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (g + 16 <= a.n) v = *(const uint4*)(a.text + g);
-        else if (g < a.n) {
-            u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (u32 k = 0; k < 16; ++k) if (g + k < a.n) w[k / 4] |= (u32)a.text[g + k] << (8 * (k % 4));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+        const uint4 v = load16_below(a.text, g, a.n);
         S[c / 16] = v;                                         // c / 16 < kStage16: c < 15 + kMaxLine
     }
     return o;
@@ -318,6 +219,7 @@ struct mgx_sam_batch {
     u64 cap = 0, max_records = 0, out_cap = 0;
     u32 tile = kDefaultTile, max_tiles = 0;
     hipStream_t stream = nullptr;
+    mgx_hip::Owner own;                                        // of every buffer and event below
     u8* h_in = nullptr; u8* d_in = nullptr; u32* d_table = nullptr;
     SamArgs a{};
     SamResult* h_res = nullptr; u64* h_line_off = nullptr; u32* h_line_len = nullptr; u64* h_rec_off = nullptr; mgx_bam_key_t* h_keys = nullptr;
@@ -333,10 +235,7 @@ void mgx_sam_batch_destroy(mgx_bgzf_t* c, mgx_sam_batch_t* b) {
     if (!b) return;
     if (c) (void)hipSetDevice(c->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (void* p : {(void*)b->h_in, (void*)b->h_res, (void*)b->h_line_off, (void*)b->h_line_len, (void*)b->h_rec_off, (void*)b->h_keys, (void*)b->h_out}) (void)hipHostFree(p);
-    for (void* p : {(void*)b->d_in, (void*)b->d_table, (void*)b->a.tile_cnt, (void*)b->a.tile_base, (void*)b->a.part, (void*)b->a.line_off, (void*)b->a.line_end,
-                    (void*)b->a.line_len, (void*)b->a.size, (void*)b->a.rec_off, (void*)b->a.out, (void*)b->a.keys, (void*)b->a.res}) (void)hipFree(p);
-    for (hipEvent_t e : {b->ev0, b->ev1, b->ev2, b->ev3, b->ev_res}) if (e) (void)hipEventDestroy(e);
+    b->own.release();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -360,20 +259,17 @@ int mgx_sam_batch_create(mgx_bgzf_t* c, const mgx_sam_table_t* table, uint64_t t
     b->max_tiles = (u32)(text_capacity / tile + 1);            // position n is one: see k_sam_lines
     const size_t nt = b->max_tiles, nr = std::max<u64>(max_records, 1);
     const size_t n_part = std::max(nt, nr) / kScanChunk + 2;
-    bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
-    auto dev = [&](auto** p, size_t bytes) { ok = ok && hipMalloc((void**)p, bytes) == hipSuccess; };
-    auto pin = [&](auto** p, size_t bytes) { ok = ok && hipHostMalloc((void**)p, bytes, hipHostMallocDefault) == hipSuccess; };
-    pin(&b->h_in, text_capacity + 16); dev(&b->d_in, text_capacity + 16);
-    dev(&b->d_table, table->blob.size() * 4);
-    dev(&b->a.tile_cnt, nt * 8); dev(&b->a.tile_base, (nt + 1) * 8); dev(&b->a.part, n_part * 8);
-    dev(&b->a.line_off, nr * 8); dev(&b->a.line_end, nr * 8); dev(&b->a.line_len, nr * 4); dev(&b->a.size, nr * 4); dev(&b->a.rec_off, (nr + 1) * 8);
-    dev(&b->a.out, b->out_cap + 16); dev(&b->a.keys, nr * sizeof(mgx_bam_key_t)); dev(&b->a.res, sizeof(SamResult));
-    pin(&b->h_res, sizeof(SamResult)); pin(&b->h_line_off, nr * 8); pin(&b->h_line_len, nr * 4); pin(&b->h_rec_off, (nr + 1) * 8); pin(&b->h_keys, nr * sizeof(mgx_bam_key_t));
-    ok = ok && hipEventCreate(&b->ev0) == hipSuccess && hipEventCreate(&b->ev1) == hipSuccess && hipEventCreate(&b->ev2) == hipSuccess &&
-         hipEventCreate(&b->ev3) == hipSuccess && hipEventCreateWithFlags(&b->ev_res, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMemcpy(b->d_table, table->blob.data(), table->blob.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
+    mgx_hip::Owner& m = b->own;
+    m.note(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking), "hipStreamCreate");
+    m.pin(&b->h_in, text_capacity + 16); m.device(&b->d_in, text_capacity + 16);
+    m.device(&b->d_table, table->blob.size() * 4);
+    m.device(&b->a.tile_cnt, nt * 8); m.device(&b->a.tile_base, (nt + 1) * 8); m.device(&b->a.part, n_part * 8);
+    m.device(&b->a.line_off, nr * 8); m.device(&b->a.line_end, nr * 8); m.device(&b->a.line_len, nr * 4); m.device(&b->a.size, nr * 4); m.device(&b->a.rec_off, (nr + 1) * 8);
+    m.device(&b->a.out, b->out_cap + 16); m.device(&b->a.keys, nr * sizeof(mgx_bam_key_t)); m.device(&b->a.res, sizeof(SamResult));
+    m.pin(&b->h_res, sizeof(SamResult)); m.pin(&b->h_line_off, nr * 8); m.pin(&b->h_line_len, nr * 4); m.pin(&b->h_rec_off, (nr + 1) * 8); m.pin(&b->h_keys, nr * sizeof(mgx_bam_key_t));
+    m.event(&b->ev0); m.event(&b->ev1); m.event(&b->ev2); m.event(&b->ev3); m.event(&b->ev_res, hipEventDisableTiming);
+    if (m.ok()) m.note(hipMemcpy(b->d_table, table->blob.data(), table->blob.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    if (!m.ok()) {
         set_error("allocation failed for a SAM batch of %llu bytes, %llu lines", (unsigned long long)text_capacity, (unsigned long long)max_records);
         mgx_sam_batch_destroy(c, b);
         return -ENOMEM;
@@ -400,20 +296,13 @@ int mgx_sam_batch_submit(mgx_bgzf_t* c, mgx_sam_batch_t* b, uint64_t n_bytes) {
     HIP_TRY(hipMemsetAsync(a.res, 0, sizeof(SamResult), s));
     HIP_TRY(hipEventRecord(b->ev0, s));
     const u32 wide = (u32)c->n_cu * 8;
-    const u64* n_lines = &a.res->n_lines;
     hipLaunchKernelGGL(k_sam_lines, dim3(std::min(a.n_tiles, wide * 4)), dim3(64), 0, s, a, 0);
-    const u32 tile_blocks = a.n_tiles / kScanChunk + 1;
-    hipLaunchKernelGGL(k_scan_sums<u64>, dim3(tile_blocks), dim3(kBlock), 0, s, (const u64*)a.tile_cnt, (const u64*)nullptr, (u64)a.n_tiles, a.part);
-    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(kBlock), 0, s, (const u64*)nullptr, (u64)a.n_tiles, a.part);
-    hipLaunchKernelGGL(k_scan_write<u64>, dim3(tile_blocks), dim3(kBlock), 0, s, (const u64*)a.tile_cnt, (const u64*)nullptr, (u64)a.n_tiles, (const u64*)a.part, a.tile_base);
+    scan_exclusive(s, ScanArray<u64>{a.tile_cnt}, nullptr, a.n_tiles, a.part, a.tile_base);
     hipLaunchKernelGGL(k_sam_counts, dim3(1), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_sam_lines, dim3(std::min(a.n_tiles, wide * 4)), dim3(64), 0, s, a, 1);
     HIP_TRY(hipEventRecord(b->ev1, s));
-    const u32 rec_blocks = (u32)(b->max_records / kScanChunk + 1);
     hipLaunchKernelGGL(k_sam_line, dim3(wide), dim3(kBlock), 0, s, a, 0);
-    hipLaunchKernelGGL(k_scan_sums<u32>, dim3(rec_blocks), dim3(kBlock), 0, s, (const u32*)a.size, n_lines, (u64)b->max_records, a.part);
-    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(kBlock), 0, s, n_lines, (u64)b->max_records, a.part);
-    hipLaunchKernelGGL(k_scan_write<u32>, dim3(rec_blocks), dim3(kBlock), 0, s, (const u32*)a.size, n_lines, (u64)b->max_records, (const u64*)a.part, a.rec_off);
+    scan_exclusive(s, ScanArray<u32>{a.size}, &a.res->n_lines, b->max_records, a.part, a.rec_off);
     hipLaunchKernelGGL(k_sam_total, dim3(1), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_sam_line, dim3(wide), dim3(kBlock), 0, s, a, 1);
     HIP_TRY(hipEventRecord(b->ev2, s));
@@ -453,8 +342,8 @@ int mgx_sam_batch_wait(mgx_bgzf_t* c, mgx_sam_batch_t* b, const uint64_t** line_
     hipStream_t s = b->stream;
     const u64 n = r.n_lines;
     if (bam && r.n_out && !b->h_out) {
-        if (hipHostMalloc((void**)&b->h_out, b->out_cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); b->h_out = nullptr;
+        if (!b->own.pin(&b->h_out, b->out_cap)) {
+            b->own.err = hipSuccess; b->h_out = nullptr;       // a later wait may try again
             set_error("pinned allocation of %llu bytes for a SAM batch's records failed", (unsigned long long)b->out_cap);
             return -ENOMEM;
         }
@@ -493,10 +382,7 @@ int mgx_sam_encode(mgx_bgzf_t* c, const mgx_sam_table_t* table, const uint8_t* t
             *n_declined = b->h_res->n_declined;
         }
     }
-    const std::string msg = rc ? mgx_last_error() : "";
-    mgx_sam_batch_destroy(c, b);
-    if (rc) set_error("%s", msg.c_str());
-    return rc;
+    return mgx_hip::keep_error(rc, [&] { mgx_sam_batch_destroy(c, b); });
 }
 
 int mgx_sam_stats(mgx_bgzf_t* c, mgx_sam_stats_t* out) {

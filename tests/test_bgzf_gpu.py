@@ -183,6 +183,40 @@ def test_record_store_emits_the_sorted_marked_stream(comp, pkg, n, seed, len_ran
         assert d.decompress(blk[18:-8]) + d.flush() == bytes(want[b * 0xff00:(b + 1) * 0xff00])
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 256 * 4096 + 1])
+def test_record_store_at_the_seams_of_the_offset_scan(comp, pkg, n):
+    """uoff is a scan over 4 + len[order[q]] in chunks of 4096 records, the chunks' sums scanned 256 at a time: one chunk
+    one short, met and passed, and the first size with a second round of 256 sums.  Records of 16 to 24 bytes, one put,
+    one window."""
+    rng = np.random.default_rng(n)
+    lens = rng.integers(16, 25, n).astype(np.uint32)
+    off = np.concatenate([[0], np.cumsum(lens.astype(np.int64))])
+    data = rng.integers(0, 256, int(off[-1]), dtype=np.uint8)
+    data[off[:-1] + 15] &= 0xfb
+    store = pkg.BgzfStore(comp)
+    addr = store.put(data) + off[:-1].astype(np.uint64)
+    order = rng.permutation(n).astype(np.uint32)
+    dup = (rng.random(n) < 0.2).astype(np.uint8)
+    blocks, block_at, uoff = store.emit(order, dup, addr, lens)
+    store.close()
+    want_off = np.concatenate([[0], np.cumsum(4 + lens[order].astype(np.int64))])
+    assert np.array_equal(uoff.astype(np.int64), want_off)
+    got = np.frombuffer(gzip.decompress(blocks + pkg.bgzf.EOF_BLOCK), dtype=np.uint8)
+    assert len(got) == want_off[-1] and len(block_at) - 1 == (len(got) + 0xff00 - 1) // 0xff00 <= 1024
+
+    def record(q):
+        r = int(order[q])
+        rec = data[off[r]:off[r + 1]].copy()
+        if dup[r]:
+            rec[15] |= 4
+        return struct.pack("<I", len(rec)) + rec.tobytes()
+    if n < 5000:
+        assert got.tobytes() == b"".join(record(q) for q in range(n))
+    else:
+        for q in np.concatenate([rng.integers(0, n, 20_000), np.arange(5), np.arange(n - 5, n)]):
+            assert got[want_off[q]:want_off[q + 1]].tobytes() == record(q), q
+
+
 def test_record_store_over_several_windows(comp, pkg):
     """~260 MB of stream: four windows of 1024 blocks, three in flight -- the rotation of the batches and the records
     that straddle two windows"""

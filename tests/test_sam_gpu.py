@@ -147,6 +147,51 @@ def test_tile_seams_of_the_line_finder(pkg, monkeypatch, tile):
     e.close()
 
 
+@pytest.fixture(scope="module")
+def long_body(pkg, synthetic):
+    """the synthetic alignment text, repeated until it has more than 4097 lines and 4096 tiles of 256 bytes, and its line starts"""
+    names, body, _ = synthetic
+    off, _ = pkg.sam.lines_host(body)
+    while len(off) <= 4097 or len(body) < 4096 * 256:
+        body = body + body
+        off, _ = pkg.sam.lines_host(body)
+    return names, body, off
+
+
+@pytest.mark.parametrize("count", [4095, 4096, 4097])
+def test_line_counts_at_the_seams_of_the_record_scan(pkg, long_body, count):
+    """4096 sizes are one workgroup's chunk of the scan over the records: the chunk one short, met and passed, with max_lines
+    (the scan's bound) equal to the count; one line more than max_lines is E2BIG"""
+    names, body, off = long_body
+    text = body[:int(off[count])]
+    host = pkg.sam.encode_rules(names, text, max_lines=count)
+    assert len(host.keys) == count
+    e = pkg.SamEncoder(names)
+    assert_same(e.encode(text, max_lines=count), host, count)
+    with pytest.raises(pkg.MgxError, match="-7"):                    # E2BIG
+        e.encode(text, max_lines=count - 1)
+    e.close()
+
+
+@pytest.mark.parametrize("tiles,rest", [(4095, 255), (4096, 0), (4097, 1)])
+def test_tile_counts_at_the_seams_of_the_tile_scan(pkg, monkeypatch, long_body, tiles, rest):
+    """the scan over the tiles' counts at its chunk of 4096: text cut at a line end and padded with newlines (which the line
+    finder skips) to a byte length that gives exactly that many tiles of 256 bytes"""
+    monkeypatch.setenv("MGX_SAM_TILE", "256")
+    names, body, off = long_body
+    n = (tiles - 1) * 256 + rest
+    assert n // 256 + 1 == tiles and n <= len(body)
+    cut = int(off[np.searchsorted(off, n, side="right") - 1])        # the last line start at or before n: the text ends in front of it
+    text = body[:cut] + b"\n" * (n - cut)
+    assert len(text) == n
+    host = pkg.sam.encode_rules(names, text)
+    assert len(host.keys) > 1000
+    e = pkg.SamEncoder(names)
+    assert_same(e.encode(text, max_lines=len(host.keys)), host, tiles)
+    assert e.stats()["n_tiles"] == tiles
+    e.close()
+
+
 def test_edge_list_and_lane_group_seams(pkg, enc):
     edges = sc.edge_lines()
     mixed = []
