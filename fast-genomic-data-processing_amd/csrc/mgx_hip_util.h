@@ -1,6 +1,7 @@
-// mgx_hip_util.h -- what the I/O translation units (mgx_bgzf.hip, mgx_store.hip, mgx_bgzf_inflate.hip, mgx_bam.hip,
-// mgx_sam.hip) share, each piece once: the HIP error check, the owner of a batch's buffers and events, the guarded
-// 16-byte load, the workgroup scan and the error message kept across a destroy.  Internal to libmgx.so, HIP only.
+// mgx_hip_util.h -- what the HIP translation units share, each piece once: the HIP error check (HIP_TRY: all of them) and, for
+// the I/O units (mgx_bgzf.hip, mgx_store.hip, mgx_bgzf_inflate.hip, mgx_bam.hip, mgx_sam.hip), the owner of a batch's buffers
+// and events, the guarded 16-byte load, the workgroup scan and the error message kept across a destroy.  Internal to
+// libmgx.so, HIP only.
 #pragma once
 #include <hip/hip_runtime.h>
 

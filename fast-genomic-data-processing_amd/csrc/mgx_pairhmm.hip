@@ -11,7 +11,6 @@
 #include <atomic>
 #include <cerrno>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,45 +24,18 @@
 
 #include "../../include/mgx_pairhmm.h"
 #include "../../include/mgx_realign.h"
-#include "mgx_common.h"
+#include "mgx_hip_util.h"
 #include "mgx_realign_internal.h"
 #include "mgx_tables.h"
 #include "pairhmm_pack.h"
+#include "pairhmm_plan.h"
 #include "pairhmm_wire.h"
 #include "pairhmm_kernels.hip.inc"
 
 using mgx::set_error;
+using namespace mgx_hmm_plan;
 
 namespace {
-
-// Row classes: a read of R rows is owned by G lanes with RPL = ceil(R / G) rows each.  Few rows per lane waste
-// issue slots on the per-step overhead (3 DPP moves, the haplotype byte, loop control are paid per step, not per
-// cell), many lanes waste steps on fill/drain (G - 1 per pair) and lanes on padding (up to G - 1 rows), so short
-// reads take narrow groups: G = 4 up to 32 bases, G = 8 up to 64, G = 16 up to 192 (1..12 rows per lane: the
-// common 100-151 bp reads), G = 64 with 4..16 rows per lane beyond that (up to 1024 bases).
-// (Giving 8 lanes up to 16 rows each -- reads up to 128 bases -- was measured and lost: 128 x 256 test cases 6019 ->
-// 5642 GCUPS, ragged 4429 -> 3835; profiles/r02_pairhmm_g8_rows.txt.)
-constexpr int kNarrowMaxRPL = 8, kG8MaxRPL = 8, kG16MaxRPL = 12, kG64MinRPL = 4, kG64MaxRPL = 16;
-constexpr int kMaxRowsG4 = 4 * kNarrowMaxRPL, kMaxRowsG8 = 8 * kG8MaxRPL;
-constexpr int kMaxRowsG16 = 16 * kG16MaxRPL;
-constexpr int kMaxRowsG64 = 64 * kG64MaxRPL;
-// Longer reads are strip-mined: 64 lanes x 16 rows per strip, the strips sweep the haplotype one after the other
-// (pairhmm_fwd_strip).  The limit below only keeps row indices and the boundary scratch in 32 bits.
-constexpr int kMaxRowsStrip = 1 << 20;
-constexpr int kStripMarkRPL = kG64MaxRPL + 1;      // shape_of's RPL value for the strip-mined class
-constexpr uint32_t kMaxLdsPerBlock = 64 * 1024;
-
-struct Bin {
-    int G = 0, RPL = 0;              // fp32 kernel shape
-    int Gd = 0, RPLd = 0;            // fp64 re-run kernel shape (fewer registers per row class)
-    uint32_t job_begin = 0, job_count = 0;
-    uint32_t max_h = 0;
-    uint64_t cells = 0, alg_bytes = 0;
-    // launch geometry
-    uint32_t block = 256, lds_stride = 0, grid_f32 = 0, grid_f64 = 0, grid_f64_all = 0, grid_nhap = 0;
-    bool strip = false;              // reads longer than 1024 bases: the strip-mined kernel, one test case per workgroup
-};
-
 
 // One device allocation + (for batches up to kStageLimit) a pinned host mirror of the same size.
 // Slabs are recycled through the context, so a stream of region-sized batches does no hipMalloc.
@@ -72,7 +44,6 @@ struct Slab {
     uint8_t* pin = nullptr;     // mirrors the first pin_cap bytes only: inputs and results, never device scratch
     size_t cap = 0, pin_cap = 0;
 };
-constexpr size_t kStageLimit = 256u << 20;
 constexpr size_t kMaxEventSets = 64;       // runs whose kernel durations a timed batch remembers
 constexpr size_t kMinSlab = 1u << 20;
 }  // namespace
@@ -81,12 +52,6 @@ struct mgx_pairhmm {
     int device = 0;
     unsigned flags = 0;
     hipStream_t compute = nullptr, copy = nullptr, d2h = nullptr;   // kernels | uploads | result downloads
-    // a batch with several read-length classes launches one kernel per class: they are dealt to the compute
-    // stream and these side streams so that the drain of one launch overlaps the body of the others
-    static constexpr int kAux = 3;
-    hipStream_t aux[kAux] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[kAux] = {nullptr, nullptr, nullptr};
-    int n_streams = 1;
     float* d_ph2pr_f = nullptr; float* d_mm_f = nullptr; float* d_div3_f = nullptr; float* d_ratio_f = nullptr;
     double* d_ph2pr_d = nullptr; double* d_mm_d = nullptr; double* d_div3_d = nullptr; double* d_ratio_d = nullptr;
     float log10_initial_f = 0; double log10_initial_d = 0;
@@ -100,28 +65,13 @@ struct mgx_pairhmm {
 struct mgx_pairhmm_batch {
     uint64_t n_pairs = 0;
     std::vector<Bin> bins;
-    // everything lives in one slab: [jobs | bases | qual | ins | del | gcp | hap] is written once
-    // (one H2D copy when staged through the pinned mirror), [out | used] is read back with one
-    // D2H copy, [rerun_list | rerun_count] is device scratch.  In the wire form the written prefix is
-    // [jobs | bases4 | qual | ins | del | gcp | hap4] and the six arrays are expanded into device scratch.
-    Slab slab;
-    size_t in_bytes = 0, o_out = 0, o_used = 0, result_bytes = 0;
-    uint64_t read_bytes = 0, hap_bytes = 0;      // lengths of the five read arrays and of the haplotype array
-    uint8_t *d_bases = nullptr, *d_qual = nullptr, *d_ins = nullptr, *d_del = nullptr,
-            *d_gcp = nullptr, *d_hap = nullptr, *d_used = nullptr;
-    Job* d_jobs = nullptr;
-    uint32_t* d_rerun_list = nullptr;
-    uint32_t* d_rerun_count = nullptr;
-    uint32_t* d_nhap_list = nullptr;   // N-haplotype test cases of the four-code launches, every class at its job_begin
-    double* d_out = nullptr;
+    Slab slab;                                   // everything lives in one slab ...
+    SlabLayout lay;                              // ... laid out by the plan (SlabLayout, pairhmm_plan.h): inputs | results | device scratch
+    template <typename T = uint8_t> T* dev(size_t off) const { return (T*)(slab.dev + off); }
+    uint32_t* rerun_list() const { return dev<uint32_t>(lay.rlist); }
+    uint32_t* counters() const { return dev<uint32_t>(lay.rcount); }
     std::vector<Job> host_jobs;    // only kept for unstaged (very large) batches
     // whole-region form (mgx_pairhmm_regions): normalise / filter epilogue over every read's row of the output
-    bool has_model = false;
-    uint32_t n_reads = 0;
-    uint64_t* d_read_len = nullptr;
-    uint8_t* d_keep = nullptr;
-    uint32_t *d_row_off = nullptr, *d_row_nh = nullptr;   // per read: where its row starts and how many haplotypes it holds
-    size_t o_keep = 0;
     double log10_rate = 0, max_err = 0;
     hipEvent_t uploaded = nullptr;
     // timing: a ring of event sets, one set per run (4 per bin: f32 start/stop, f64 start/stop), so that
@@ -146,16 +96,6 @@ BatchPtr new_batch() {
     return BatchPtr(new (std::nothrow) mgx_pairhmm_batch, [](mgx_pairhmm_batch* p) { mgx_pairhmm_batch_destroy(nullptr, p); });
 }
 
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,     \
-                      __LINE__);                                                           \
-            return -EIO;                                                                   \
-        }                                                                                  \
-    } while (0)
-
 template <typename T>
 int upload(T** dst, const void* src, size_t bytes, hipStream_t s) {
     *dst = nullptr;
@@ -165,96 +105,12 @@ int upload(T** dst, const void* src, size_t bytes, hipStream_t s) {
     return 0;
 }
 
-// (G, RPL) class of a read of R rows; G = 0 if unsupported.  MGX_PAIRHMM_MIN_G=16 switches the narrow groups off.
-inline void shape_of(uint32_t R, int* G, int* RPL) {
-    static const int min_g = [] { const char* e = getenv("MGX_PAIRHMM_MIN_G"); const int v = e ? atoi(e) : 4; return v; }();
-    const uint32_t g8_rows = (uint32_t)kMaxRowsG8;
-    if (R <= (uint32_t)kMaxRowsG4 && min_g <= 4) { *G = 4; *RPL = (int)((R + 3) / 4); }
-    else if (R <= g8_rows && min_g <= 8) { *G = 8; *RPL = (int)((R + 7) / 8); }
-    else if (R <= (uint32_t)kMaxRowsG16) { *G = 16; *RPL = (int)((R + 15) / 16); }
-    else if (R <= (uint32_t)kMaxRowsG64) { *G = 64; *RPL = std::max(kG64MinRPL, (int)((R + 63) / 64)); }
-    else if (R <= (uint32_t)kMaxRowsStrip) { *G = 64; *RPL = kStripMarkRPL; }
-    else { *G = 0; *RPL = 0; }
-}
-// dynamic LDS of one block: per-wavefront emission table (fp32 only, `codes` columns) + per-group haplotype codes
-inline uint32_t lds_bytes(const Bin& bin, bool f32, int codes = kMaxCodes) {
-    const uint32_t waves = bin.block / 64u, groups = bin.block / (uint32_t)(f32 ? bin.G : bin.Gd);
-    const uint32_t etab = f32 ? (uint32_t)((bin.RPL + 1) / 2) * (uint32_t)codes * 512u : 0u;
-    return waves * etab + groups * bin.lds_stride;
-}
-// bins in order of (G, RPL): [G=4: 1..8][G=8: 1..8][G=16: 1..12][G=64: 4..16]
-constexpr int kBinG8 = kNarrowMaxRPL, kBinG16 = kBinG8 + kG8MaxRPL, kBinG64 = kBinG16 + kG16MaxRPL;
-constexpr int kBinStrip = kBinG64 + (kG64MaxRPL - kG64MinRPL + 1);      // the strip-mined class comes last
-constexpr int kBins = kBinStrip + 1;
-inline int bin_index(int G, int RPL) {
-    if (G == 64 && RPL == kStripMarkRPL) return kBinStrip;
-    return G == 4 ? RPL - 1 : G == 8 ? kBinG8 + RPL - 1 : G == 16 ? kBinG16 + RPL - 1 : kBinG64 + RPL - kG64MinRPL;
-}
-inline void bin_shape(int k, Bin* b) {
-    if (k == kBinStrip) { b->G = 64; b->RPL = kG64MaxRPL; b->Gd = 64; b->RPLd = kG64MaxRPL; b->strip = true; return; }
-    if (k < kBinG8) { b->G = 4; b->RPL = k + 1; }
-    else if (k < kBinG16) { b->G = 8; b->RPL = k - kBinG8 + 1; }
-    else if (k < kBinG64) { b->G = 16; b->RPL = k - kBinG16 + 1; }
-    else { b->G = 64; b->RPL = k - kBinG64 + kG64MinRPL; }
-    // the fp64 kernel keeps twice the registers per row: beyond 8 rows per lane of 16 it runs one
-    // pair per wavefront instead
-    if (b->G == 16 && b->RPL > 8) { b->Gd = 64; b->RPLd = (16 * b->RPL + 63) / 64; }
-    else { b->Gd = b->G; b->RPLd = b->RPL; }
-}
-constexpr uint64_t kMergeBelow = 4096;
-// device counters of a batch: [0, kBins) every class's own fp64 re-run list, 62 the exact tier's list, 63 the narrow
-// classes' shared fp64 list, [kNhapCount, kNhapCount + kBins) every class's N-haplotype list
-constexpr int kNhapCount = 64, kCounters = 128;
-static_assert(kBins <= 62 && kNhapCount + kBins <= kCounters, "counter slots");
-
-// launch geometry of a bin once job_count and max_h are known
-int finalize_bin(Bin& bin, int n_cu) {
-    // LDS per group: G pad + codes + G pad + prefetch slack (see the kernel's staging loop)
-    bin.lds_stride = (bin.max_h + 2u * (uint32_t)std::max(bin.G, bin.Gd) + 8u + 15u) & ~15u;
-    bin.block = 64;                   // one wavefront per workgroup: finest LDS/VGPR packing per CU, no cross-wave
-                                      // barriers; in-process A/B at 1 M pairs: 5.48 ms (64), 5.65 (128), 5.46 (256)
-    if (const char* e = getenv("MGX_PAIRHMM_BLOCK")) { const int v = atoi(e); if (v == 64 || v == 128 || v == 256) bin.block = (uint32_t)v; }
-    while (bin.block > 64u && lds_bytes(bin, true) > kMaxLdsPerBlock) bin.block /= 2;
-    if (lds_bytes(bin, true) > 160u * 1024u) {
-        set_error("haplotype of %u bases does not fit the LDS staging buffer", bin.max_h);
-        return -E2BIG;
-    }
-    if (bin.strip) {
-        // one test case per workgroup, a bounded grid walking the job list: the boundary rows between strips live in
-        // a scratch array indexed by workgroup
-        bin.block = 64;
-        bin.grid_f32 = bin.grid_f64 = bin.grid_f64_all = std::min<uint32_t>(bin.job_count, (uint32_t)n_cu * 4u);
-        return 0;
-    }
-    const uint32_t gpb = bin.block / bin.G, gpbd = bin.block / bin.Gd;
-    bin.grid_f32 = (bin.job_count + gpb - 1) / gpb;
-    bin.grid_f64_all = (bin.job_count + gpbd - 1) / gpbd;
-    bin.grid_f64 = std::min<uint32_t>(bin.grid_f64_all, (uint32_t)n_cu * 8u);
-    bin.grid_nhap = std::min<uint32_t>(bin.grid_f32, (uint32_t)n_cu * 8u);
-    return 0;
-}
-// fold sparsely populated bins into the next larger row class of the same group width
-void merge_small_bins(uint64_t (&count)[kBins], int (&remap)[kBins]) {
-    for (int k = 0; k < kBins; ++k) remap[k] = k;
-    for (int k = 0; k + 1 < kBins; ++k) {
-        if (k + 1 == kBinG8 || k + 1 == kBinG16 || k + 1 == kBinG64 || k + 1 == kBinStrip) continue;   // never across a group-width boundary
-        if (count[k] && count[k] < kMergeBelow) { count[k + 1] += count[k]; count[k] = 0; remap[k] = k + 1; }
-    }
-    for (int k = 0; k < kBins; ++k) { int t = k; while (remap[t] != t) t = remap[t]; remap[k] = t; }
-}
-
-constexpr size_t kSlabAlign = 256;          // every array of a slab starts on a multiple of this and owns the bytes up to the next
-inline size_t align_up(size_t x, size_t a = kSlabAlign) { return (x + a - 1) / a * a; }
-
 // ---- the wire form's device side (pairhmm_wire.h): one launch on the copy stream, right behind the H2D copy, turns
 // [bases4 | qual | ins | del | gcp | hap4] back into the six byte arrays the PairHMM kernels read.  The grid is laid
 // over the concatenated work of the six arrays; which array a workgroup serves is uniform over it.  One thread
 // produces 8 output bytes with one 8-byte store: of a bit stream it reads the group's w bytes at byte offset w t, of
 // nibble codes 4 bytes, which two byte permutes map through "ACTGN".  No LDS, nothing shared between threads.
-constexpr uint32_t kExpandBlock = 256;
-// the last thread of an array stores its full 8 bytes, up to 7 past the array's length: they fall into the array's own
-// slab slot, which align_up rounds to a multiple of 8
-static_assert(kSlabAlign % 8 == 0, "pairhmm_expand_wire stores whole 8-byte groups into slab slots");
+// (the grid: expand_grid in pairhmm_plan.h)
 struct ExpandWireArgs {
     const uint8_t* src[6];       // bases4, qual, ins, del, gcp, hap4
     uint8_t* dst[6];             // bases, qual, ins, del, gcp, hap
@@ -337,22 +193,20 @@ void release_slab(mgx_pairhmm* c, Slab sl) {
 
 using mgx::validate;
 
+template <typename T>
+int host_table(int which, const T** out) {
+    const auto& t = mgx::tables<T>();
+    if (which == 0) { *out = t.ph2pr.data(); return mgx::kPh2prSize; }
+    if (which == 1) { *out = t.mm.data(); return mgx::kMmSize; }
+    return -EINVAL;
+}
+
 }  // namespace
 
 extern "C" {
 
-int mgx_pairhmm_table_f32(int which, const float** out) {
-    const auto& t = mgx::tables<float>();
-    if (which == 0) { *out = t.ph2pr.data(); return mgx::kPh2prSize; }
-    if (which == 1) { *out = t.mm.data(); return mgx::kMmSize; }
-    return -EINVAL;
-}
-int mgx_pairhmm_table_f64(int which, const double** out) {
-    const auto& t = mgx::tables<double>();
-    if (which == 0) { *out = t.ph2pr.data(); return mgx::kPh2prSize; }
-    if (which == 1) { *out = t.mm.data(); return mgx::kMmSize; }
-    return -EINVAL;
-}
+int mgx_pairhmm_table_f32(int which, const float** out) { return host_table(which, out); }
+int mgx_pairhmm_table_f64(int which, const double** out) { return host_table(which, out); }
 
 int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
@@ -393,20 +247,6 @@ int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
     }
     HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&c->d2h, hipStreamNonBlocking));
-    {
-        const unsigned pat = (flags >> 8) & 0xFFu;
-        const char* e = getenv("MGX_PAIRHMM_STREAMS");
-        // default 1: measured on an MI355X (profiles/r02_pairhmm_streams_ab.txt) two streams gain 2 % on resident ragged
-        // batches (4529 -> 4610 GCUPS) but lose 20 % for region batches through a 4-lane queue (3089 -> 2431: lanes x
-        // streams oversubscribe the device); three and four streams lose everywhere (ragged 3865 / 3895)
-        c->n_streams = e ? std::max(1, std::min(1 + mgx_pairhmm::kAux, atoi(e))) : 1;
-        if (pat != 0 && pat != 0xFFu) c->n_streams = 1;          // a CU-masked context keeps to its masked stream
-        for (int a = 0; a + 1 < c->n_streams; ++a) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->aux[a], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_join[a], hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    }
     const auto& tf = mgx::tables<float>();
     const auto& td = mgx::tables<double>();
     int rc;
@@ -437,8 +277,6 @@ void mgx_pairhmm_destroy(mgx_pairhmm_t* c) {
     if (c->compute) (void)hipStreamDestroy(c->compute);
     if (c->copy) (void)hipStreamDestroy(c->copy);
     if (c->d2h) (void)hipStreamDestroy(c->d2h);
-    for (int a = 0; a < mgx_pairhmm::kAux; ++a) { if (c->aux[a]) (void)hipStreamDestroy(c->aux[a]); if (c->ev_join[a]) (void)hipEventDestroy(c->ev_join[a]); }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     delete c;
 }
 
@@ -461,95 +299,22 @@ void mgx_pairhmm_batch_destroy(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
 
 namespace {
 
-// Where the arrays of a batch lie in its slab.  The inputs are written once (one H2D copy when staged through the
-// pinned mirror), [out | used | keep] is read back with one D2H copy, what follows is device scratch.  The pair-list
-// form writes its jobs on the host, first in the mirror; the cross-product form uploads the tables that the device
-// enumerates them from and keeps the jobs in scratch.
-struct SlabLayout {
-    // sizes: set by the caller
-    uint64_t n = 0, n_reads = 0, n_haps = 0, n_regions = 0, read_bytes = 0, hap_bytes = 0;
-    bool cross = false, model = false;
-    // offsets: set by lay_out_slab (the results' offsets go to the batch: o_out, o_used, o_keep)
-    size_t rtab = 0, rreg = 0, rpre = 0, gtab = 0, htab = 0;      // cross-product form: what the jobs are enumerated from
-    size_t jobs = 0, bases = 0, qual = 0, ins = 0, del = 0, gcp = 0, hap = 0;
-    size_t mapq = 0, rlen = 0, roff = 0, rnh = 0;                 // with a read model: per read, for the model and the epilogue
-    size_t rlist = 0, nlist = 0, rcount = 0;
-    size_t pin_bytes = 0;                                         // the pinned mirror covers the inputs and the results only
-    bool staged = true;
-    // the wire form (pair-list batches of a context with MGX_PAIRHMM_WIRE): the uploaded prefix is [jobs | bases4 | qual |
-    // ins | del | gcp | hap4] at these offsets, and bases ... hap above lie in device scratch
-    bool wire = false;
-    mgx::wire::Widths ww;
-    size_t w_bases4 = 0, w_qual = 0, w_ins = 0, w_del = 0, w_gcp = 0, w_hap4 = 0;
-};
+// The plan's two environment knobs.  MGX_PAIRHMM_MIN_G=16 switches the narrow groups off (read once).  MGX_PAIRHMM_BLOCK is the
+// workgroup size of the single-class launches; 64, one wavefront per workgroup, packs LDS and VGPRs finest and needs no
+// cross-wave barriers (in-process A/B at 1 M pairs: 5.48 ms (64), 5.65 (128), 5.46 (256)).
+// (static, as every helper below that is new: in this file's extern "C" block a plain function of an unnamed namespace is exported)
+static int env_min_g() { static const int v = [] { const char* e = getenv("MGX_PAIRHMM_MIN_G"); return e ? atoi(e) : 4; }(); return v; }
+static uint32_t env_block() { const char* e = getenv("MGX_PAIRHMM_BLOCK"); const int v = e ? atoi(e) : 64; return v == 128 || v == 256 ? (uint32_t)v : 64u; }
 
-// Decides the offsets, takes a slab of that size -- with a pinned mirror if always_stage or if inputs and results fit
-// kStageLimit -- and points the batch into it.
-int lay_out_slab(mgx_pairhmm* c, bool always_stage, SlabLayout* L, mgx_pairhmm_batch* b) {
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t at = off; off = align_up(off + bytes); return at; };
-    const uint64_t n = L->n, per_read = L->model ? L->n_reads : 0;
-    if (L->cross) {
-        L->rtab = take(L->n_reads * sizeof(SeqRef));
-        L->rreg = take(L->n_reads * sizeof(uint32_t));
-        L->rpre = take((L->n_reads + 1) * sizeof(uint32_t));
-        L->gtab = take(L->n_regions * sizeof(RegionRef));
-        L->htab = take(L->n_haps * sizeof(SeqRef));
-    } else {
-        L->jobs = take(n * sizeof(Job));
-    }
-    auto take_expanded = [&] {
-        L->bases = take(L->read_bytes);
-        L->qual = take(L->read_bytes);
-        L->ins = take(L->read_bytes);
-        L->del = take(L->read_bytes);
-        L->gcp = take(L->read_bytes);
-        L->hap = take(L->hap_bytes);
-    };
-    // the wire form is for batches that go through the pinned mirror: those the plain form would stage
-    if (L->wire && (L->cross || (!always_stage && align_up(n * sizeof(Job)) + 5 * align_up(L->read_bytes) + align_up(L->hap_bytes) +
-                                                       align_up(n * sizeof(double)) + align_up(n) > kStageLimit))) L->wire = false;
-    if (L->wire) {
-        namespace W = mgx::wire;
-        L->w_bases4 = take(W::nibble_bytes(L->read_bytes));
-        L->w_qual = take(W::stream_bytes(L->read_bytes, L->ww.qual));
-        L->w_ins = take(W::stream_bytes(L->read_bytes, L->ww.ins));
-        L->w_del = take(W::stream_bytes(L->read_bytes, L->ww.del));
-        L->w_gcp = take(W::stream_bytes(L->read_bytes, L->ww.gcp));
-        L->w_hap4 = take(W::nibble_bytes(L->hap_bytes));
-    } else {
-        take_expanded();
-    }
-    L->mapq = take(per_read);
-    L->rlen = take(per_read * sizeof(uint64_t));
-    L->roff = take(per_read * sizeof(uint32_t));
-    L->rnh = take(per_read * sizeof(uint32_t));
-    b->in_bytes = off;
-    b->o_out = take(n * sizeof(double));
-    b->o_used = take(n);
-    b->o_keep = take(per_read);
-    b->result_bytes = off - b->o_out;
-    L->pin_bytes = off;
-    if (L->cross) L->jobs = take(n * sizeof(Job));
-    if (L->wire) take_expanded();                    // what pairhmm_expand_wire writes
-    L->rlist = take(2 * n * sizeof(uint32_t));       // fp64 re-run lists | exact-tier list
-    L->nlist = take(n * sizeof(uint32_t));           // N-haplotype lists of the four-code fp32 launches
-    L->rcount = take(kCounters * sizeof(uint32_t));
-    L->staged = always_stage || L->pin_bytes <= kStageLimit;
-    if (const int rc = acquire_slab(c, off, L->staged ? L->pin_bytes : 0, &b->slab)) return rc;
-    uint8_t* dv = b->slab.dev;
-    b->read_bytes = L->read_bytes; b->hap_bytes = L->hap_bytes;
-    b->d_jobs = (Job*)(dv + L->jobs);
-    b->d_bases = dv + L->bases; b->d_qual = dv + L->qual; b->d_ins = dv + L->ins; b->d_del = dv + L->del;
-    b->d_gcp = dv + L->gcp; b->d_hap = dv + L->hap;
-    b->d_out = (double*)(dv + b->o_out); b->d_used = dv + b->o_used;
-    b->d_rerun_list = (uint32_t*)(dv + L->rlist); b->d_rerun_count = (uint32_t*)(dv + L->rcount);
-    b->d_nhap_list = (uint32_t*)(dv + L->nlist);
-    if (L->model) {
-        b->d_read_len = (uint64_t*)(dv + L->rlen); b->d_keep = dv + b->o_keep;
-        b->d_row_off = (uint32_t*)(dv + L->roff); b->d_row_nh = (uint32_t*)(dv + L->rnh);
-    }
-    return 0;
+// the caller's six sequence arrays, in the order of SlabLayout::seq, wseq and mgx_pairhmm_batch::lay.seq
+static const uint8_t* seq_src(const mgx_pairhmm_input_t* in, int k) {
+    const uint8_t* const src[kSeqArrays] = {in->bases, in->qual, in->ins, in->del, in->gcp, in->hap_bases};
+    return src[k];
+}
+
+// cells and bytes of a batch: the sum over its classes
+static void sum_stats(mgx_pairhmm_batch* b) {
+    for (const Bin& bin : b->bins) { b->stats.cells += bin.cells; b->stats.alg_bytes += bin.alg_bytes; }
 }
 
 // modifyReadQualities + gap continuation penalties as the device applies them (pairhmm_read_model)
@@ -565,139 +330,34 @@ ReadModel make_read_model(const mgx_read_model_t& model) {
     return rm;
 }
 
-// Row F1: the cross-product test cases (pair_read == pair_hap == NULL: every read against every haplotype,
-// out[r * n_haps + h]) of one or several regions in one batch -- one upload, one set of launches, one download.
-// Host work is linear in reads + haplotypes (the test cases are enumerated on the device), so coalescing a
-// thousand small regions costs microseconds, not a pair list.
-struct CrossRead { uint64_t off; uint32_t len, region; uint8_t bin; };
-struct CrossPlan {
-    uint64_t nr = 0, nh = 0, n = 0, read_bytes = 0, hap_bytes = 0;
-    std::vector<CrossRead> reads;          // in global read order: offsets rebased to the batch's concatenated arrays
-    std::vector<RegionRef> regions;
-    std::vector<SeqRef> haps;              // region by region, each in stable order of decreasing length
-    uint32_t max_h = 0;
-    uint64_t reads_in[kBins] = {0}, rstart[kBins + 1] = {0}, jobs_in[kBins] = {0}, cells_in[kBins] = {0}, bytes_in[kBins] = {0};
-};
-
-// totals of the batch, and where every region's [reads][haps] block starts in the output
-int cross_totals(uint32_t n_regions, const mgx_pairhmm_input_t* regs, CrossPlan* p, std::vector<uint64_t>* out_base) {
-    out_base->assign(n_regions + 1, 0);
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        const mgx_pairhmm_input_t& in = regs[g];
-        if (in.pair_read || in.pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
-        p->nr += in.n_reads; p->nh += in.n_haps; p->n += in.n_reads * in.n_haps;
-        if (in.n_reads) p->read_bytes += in.read_off[in.n_reads] - in.read_off[0];
-        if (in.n_haps) p->hap_bytes += in.hap_off[in.n_haps] - in.hap_off[0];
-        (*out_base)[g + 1] = p->n;
-    }
-    if (p->n > 0xFFFFFFF0ull || p->nr > 0xFFFFFFF0ull) { set_error("more than 2^32 test cases in one batch"); return -E2BIG; }
-    return 0;
-}
-
-// read, region and haplotype tables; job counts per read-length class in count[]
-int cross_tables(uint32_t n_regions, const mgx_pairhmm_input_t* regs, const std::vector<uint64_t>& out_base, CrossPlan* p,
-                 uint64_t (&count)[kBins]) {
-    p->reads.resize(p->nr); p->regions.resize(n_regions); p->haps.resize(p->nh);
-    uint64_t r_at = 0, h_at = 0, rb = 0, hb = 0;
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        const mgx_pairhmm_input_t& in = regs[g];
-        RegionRef& R = p->regions[g];
-        R.hap_begin = (uint32_t)h_at; R.n_haps = (uint32_t)in.n_haps; R.read_base = (uint32_t)r_at; R.out_base = (uint32_t)out_base[g];
-        for (uint64_t h = 0; h < in.n_haps; ++h) {
-            const uint64_t H = in.hap_off[h + 1] - in.hap_off[h];
-            if (H == 0) { set_error("region %u: haplotype %llu is empty", g, (unsigned long long)h); return -EINVAL; }
-            if (H > 0x7FFFFFF0ull) { set_error("haplotype too long"); return -E2BIG; }
-            p->haps[h_at + h] = SeqRef{hb + (in.hap_off[h] - in.hap_off[0]), (uint32_t)H, (uint32_t)h};
-            p->max_h = std::max<uint32_t>(p->max_h, (uint32_t)H);
-        }
-        std::stable_sort(p->haps.begin() + h_at, p->haps.begin() + h_at + in.n_haps, [](const SeqRef& a, const SeqRef& b2) { return a.len > b2.len; });
-        for (uint64_t r = 0; r < in.n_reads; ++r) {
-            const uint64_t Rl = in.read_off[r + 1] - in.read_off[r];
-            if (Rl == 0) { set_error("region %u: read %llu is empty", g, (unsigned long long)r); return -EINVAL; }
-            int G, RPL;
-            shape_of((uint32_t)std::min<uint64_t>(Rl, 0xFFFFFFFFull), &G, &RPL);
-            if (G == 0) { set_error("region %u: read of %llu bases exceeds the %d-row limit", g, (unsigned long long)Rl, kMaxRowsStrip); return -E2BIG; }
-            CrossRead& ri = p->reads[r_at + r];
-            ri.off = rb + (in.read_off[r] - in.read_off[0]); ri.len = (uint32_t)Rl; ri.region = g; ri.bin = (uint8_t)bin_index(G, RPL);
-            count[ri.bin] += in.n_haps;
-        }
-        if (in.n_reads) rb += in.read_off[in.n_reads] - in.read_off[0];
-        if (in.n_haps) hb += in.hap_off[in.n_haps] - in.hap_off[0];
-        r_at += in.n_reads; h_at += in.n_haps;
-    }
-    return 0;
-}
-
-// folds the small classes and sums, per class, reads, jobs, cells and bytes
-void cross_bins(CrossPlan* p, uint64_t (&count)[kBins]) {
-    int remap[kBins];
-    merge_small_bins(count, remap);
-    std::vector<uint64_t> sumH(p->regions.size(), 0);
-    for (size_t g = 0; g < p->regions.size(); ++g)
-        for (uint32_t h = 0; h < p->regions[g].n_haps; ++h) sumH[g] += p->haps[p->regions[g].hap_begin + h].len;
-    for (CrossRead& ri : p->reads) {
-        ri.bin = (uint8_t)remap[ri.bin];
-        const RegionRef& R = p->regions[ri.region];
-        p->reads_in[ri.bin]++; p->jobs_in[ri.bin] += R.n_haps; p->cells_in[ri.bin] += (uint64_t)ri.len * sumH[ri.region];
-        p->bytes_in[ri.bin] += 5ull * ri.len * R.n_haps + sumH[ri.region] + 4ull * R.n_haps;
-    }
-    for (int k = 0; k < kBins; ++k) p->rstart[k + 1] = p->rstart[k] + p->reads_in[k];
-}
-
-// the enumeration tables and the sequences, into the pinned mirror
+// the enumeration tables (pairhmm_plan.h) and the sequences, into the pinned mirror
 void cross_stage(const CrossPlan& p, uint32_t n_regions, const mgx_pairhmm_input_t* regs, const SlabLayout& L, uint8_t* pin) {
-    SeqRef* rtab = (SeqRef*)(pin + L.rtab);
-    uint32_t* rreg = (uint32_t*)(pin + L.rreg);
-    uint32_t* rpre = (uint32_t*)(pin + L.rpre);
-    uint64_t cur[kBins];
-    for (int k = 0; k < kBins; ++k) cur[k] = p.rstart[k];
-    for (uint64_t r = 0; r < p.nr; ++r) {          // read table in (class, input) order
-        const CrossRead& ri = p.reads[r];
-        const uint64_t at = cur[ri.bin]++;
-        rtab[at] = SeqRef{ri.off, ri.len, (uint32_t)r};
-        rreg[at] = ri.region;
-    }
-    uint32_t run = 0;
-    for (uint64_t at = 0; at < p.nr; ++at) { rpre[at] = run; run += p.regions[rreg[at]].n_haps; }
-    rpre[p.nr] = run;
+    cross_write_tables(p, (SeqRef*)(pin + L.rtab), (uint32_t*)(pin + L.rreg), (uint32_t*)(pin + L.rpre));
     memcpy(pin + L.gtab, p.regions.data(), n_regions * sizeof(RegionRef));
     memcpy(pin + L.htab, p.haps.data(), p.nh * sizeof(SeqRef));
     size_t rb = 0, hb = 0;
     for (uint32_t g = 0; g < n_regions; ++g) {
         const mgx_pairhmm_input_t& in = regs[g];
-        if (in.n_reads) {
-            const uint64_t o0 = in.read_off[0], len = in.read_off[in.n_reads] - o0;
-            memcpy(pin + L.bases + rb, in.bases + o0, len); memcpy(pin + L.qual + rb, in.qual + o0, len);
-            memcpy(pin + L.ins + rb, in.ins + o0, len);     memcpy(pin + L.del + rb, in.del + o0, len);
-            memcpy(pin + L.gcp + rb, in.gcp + o0, len);
-            rb += len;
+        const uint64_t r0 = in.n_reads ? in.read_off[0] : 0, rlen = in.n_reads ? in.read_off[in.n_reads] - r0 : 0;
+        const uint64_t h0 = in.n_haps ? in.hap_off[0] : 0, hlen = in.n_haps ? in.hap_off[in.n_haps] - h0 : 0;
+        for (int k = 0; k < kSeqArrays; ++k) {
+            if (k == kSeqHap) { if (hlen) memcpy(pin + L.seq[k] + hb, seq_src(&in, k) + h0, hlen); }
+            else if (rlen) memcpy(pin + L.seq[k] + rb, seq_src(&in, k) + r0, rlen);
         }
-        if (in.n_haps) {
-            const uint64_t o0 = in.hap_off[0], len = in.hap_off[in.n_haps] - o0;
-            memcpy(pin + L.hap + hb, in.hap_bases + o0, len);
-            hb += len;
-        }
+        rb += rlen; hb += hlen;
     }
 }
 
 // per read, in global read order: MAPQ, length, and its row of the output
 int cross_stage_model(uint32_t n_regions, const mgx_pairhmm_input_t* regs, const uint8_t* const* mapq,
                       const std::vector<uint64_t>& out_base, const SlabLayout& L, uint8_t* pin) {
-    uint64_t* rlen = (uint64_t*)(pin + L.rlen);
-    uint32_t* roff = (uint32_t*)(pin + L.roff);
-    uint32_t* rnh = (uint32_t*)(pin + L.rnh);
     uint64_t r_at = 0;
     for (uint32_t g = 0; g < n_regions; ++g) {
-        const mgx_pairhmm_input_t& in = regs[g];
-        if (in.n_reads && !mapq[g]) { set_error("region %u: mapq is NULL", g); return -EINVAL; }
-        for (uint64_t r = 0; r < in.n_reads; ++r) {
-            rlen[r_at + r] = in.read_off[r + 1] - in.read_off[r];
-            roff[r_at + r] = (uint32_t)(out_base[g] + r * in.n_haps);
-            rnh[r_at + r] = (uint32_t)in.n_haps;
-        }
-        if (in.n_reads) memcpy(pin + L.mapq + r_at, mapq[g], in.n_reads);
-        r_at += in.n_reads;
+        if (regs[g].n_reads && !mapq[g]) { set_error("region %u: mapq is NULL", g); return -EINVAL; }
+        if (regs[g].n_reads) memcpy(pin + L.mapq + r_at, mapq[g], regs[g].n_reads);
+        r_at += regs[g].n_reads;
     }
+    cross_write_rows(n_regions, regs, out_base, (uint64_t*)(pin + L.rlen), (uint32_t*)(pin + L.roff), (uint32_t*)(pin + L.rnh));
     return 0;
 }
 
@@ -710,43 +370,29 @@ int create_cross(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t
     b->stats.n_pairs = p.n;
     if (p.n == 0) return 0;
     uint64_t count[kBins] = {0};
-    if ((rc = cross_tables(n_regions, regs, *out_base, &p, count))) return rc;
-    cross_bins(&p, count);
-    SlabLayout L;
+    if ((rc = cross_tables(n_regions, regs, *out_base, env_min_g(), &p, count))) return rc;
+    if ((rc = cross_bins(&p, count, c->n_cu, env_block(), &b->bins))) return rc;      // before anything is enqueued
+    sum_stats(b);
+    SlabLayout& L = b->lay;
     L.n = p.n; L.n_reads = p.nr; L.n_haps = p.nh; L.n_regions = n_regions; L.read_bytes = p.read_bytes; L.hap_bytes = p.hap_bytes;
     L.cross = true; L.model = model != nullptr;
-    if ((rc = lay_out_slab(c, true, &L, b))) return rc;
+    plan_slab(true, &L);
+    if ((rc = acquire_slab(c, L.total, L.pin_bytes, &b->slab))) return rc;
     uint8_t* dv = b->slab.dev; uint8_t* pin = b->slab.pin;
     cross_stage(p, n_regions, regs, L, pin);
     hipStream_t s = c->copy;
     if (model) {
         if ((rc = cross_stage_model(n_regions, regs, mapq, *out_base, L, pin))) return rc;
-        b->has_model = true; b->n_reads = (uint32_t)p.nr;
         b->log10_rate = model->log10_mismapping_rate; b->max_err = model->max_error_per_base;
     }
-    HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dv, pin, b->lay.in_bytes, hipMemcpyHostToDevice, s));
     if (model)      // modifyReadQualities + gap continuation penalties, in place on the uploaded arrays
-        hipLaunchKernelGGL(pairhmm_read_model, dim3((uint32_t)p.nr), dim3(128), 0, s, (const SeqRef*)(dv + L.rtab),
-                           b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, (const uint8_t*)(dv + L.mapq), make_read_model(*model));
-    uint64_t job_begin = 0;
-    for (int k = 0; k < kBins; ++k) {
-        if (!p.reads_in[k]) continue;
-        Bin bin;
-        bin_shape(k, &bin);
-        bin.job_begin = (uint32_t)job_begin;
-        bin.job_count = (uint32_t)p.jobs_in[k];
-        bin.max_h = p.max_h;
-        bin.cells = p.cells_in[k];
-        bin.alg_bytes = p.bytes_in[k];
-        if ((rc = finalize_bin(bin, c->n_cu))) return rc;
-        b->stats.cells += bin.cells; b->stats.alg_bytes += bin.alg_bytes;
-        b->bins.push_back(bin);
-        job_begin += bin.job_count;
-    }
+        hipLaunchKernelGGL(pairhmm_read_model, dim3((uint32_t)p.nr), dim3(128), 0, s, (const SeqRef*)(dv + L.rtab), b->dev(b->lay.seq[kSeqBases]),
+                           b->dev(b->lay.seq[kSeqQual]), b->dev(b->lay.seq[kSeqIns]), b->dev(b->lay.seq[kSeqDel]), b->dev(b->lay.seq[kSeqGcp]), (const uint8_t*)(dv + L.mapq), make_read_model(*model));
     // one enumeration launch for all bins: jobs are laid out in read-table order, which is bin order
     hipLaunchKernelGGL(pairhmm_make_jobs_multi, dim3((uint32_t)((p.n + 255) / 256)), dim3(256), 0, s, (const SeqRef*)(dv + L.rtab),
                        (const uint32_t*)(dv + L.rreg), (const uint32_t*)(dv + L.rpre), (uint32_t)p.nr, (const RegionRef*)(dv + L.gtab),
-                       (const SeqRef*)(dv + L.htab), (uint32_t)p.n, b->d_jobs);
+                       (const SeqRef*)(dv + L.htab), (uint32_t)p.n, b->dev<Job>(b->lay.jobs));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(b->uploaded, s));
@@ -757,39 +403,33 @@ int create_cross(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t
 // (the gather and the bit-packing are one pass; the widths come from create_pairs' pre-pass).
 void stage_wire(const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, const SlabLayout& L, uint8_t* pin) {
     namespace W = mgx::wire;
+    uint8_t* dst[kSeqArrays];
+    for (int k = 0; k < kSeqArrays; ++k) dst[k] = pin + L.wseq[k];
     if (plan || L.read_bytes + L.hap_bytes < (32u << 20)) {
-        W::pack_arrays(in, plan, L.ww, pin + L.w_bases4, pin + L.w_qual, pin + L.w_ins, pin + L.w_del, pin + L.w_gcp, pin + L.w_hap4);
+        W::pack_arrays(in, plan, L.ww, dst[kSeqBases], dst[kSeqQual], dst[kSeqIns], dst[kSeqDel], dst[kSeqGcp], dst[kSeqHap]);
         return;
     }
     // a large one-shot batch: one thread per array, as the plain form stages it
-    std::thread th[6];
-    th[0] = std::thread([=] { W::pack_nibbles(in, plan, true, pin + L.w_bases4); });
-    th[1] = std::thread([=] { W::pack_stream(in, plan, in->qual, L.ww.qual, pin + L.w_qual); });
-    th[2] = std::thread([=] { W::pack_stream(in, plan, in->ins, L.ww.ins, pin + L.w_ins); });
-    th[3] = std::thread([=] { W::pack_stream(in, plan, in->del, L.ww.del, pin + L.w_del); });
-    th[4] = std::thread([=] { if (L.ww.gcp) W::pack_stream(in, plan, in->gcp, L.ww.gcp, pin + L.w_gcp); });
-    th[5] = std::thread([=] { W::pack_nibbles(in, plan, false, pin + L.w_hap4); });
+    std::thread th[kSeqArrays];
+    for (int k = 0; k < kSeqArrays; ++k) {
+        const uint32_t w = L.wire_width(k);
+        uint8_t* const to = dst[k];
+        th[k] = std::thread([=] {
+            if (w == 4) W::pack_nibbles(in, plan, k == kSeqBases, to);
+            else if (w) W::pack_stream(in, plan, seq_src(in, k), w, to);       // w == 0: a constant gcp travels in the widths
+        });
+    }
     for (auto& t : th) t.join();
 }
 
-// pairhmm_expand_wire behind the copy, on the same stream: d_bases ... d_hap are whole before `uploaded` is recorded
+// pairhmm_expand_wire behind the copy, on the same stream: the six arrays are whole before `uploaded` is recorded
 int launch_expand_wire(hipStream_t s, const SlabLayout& L, mgx_pairhmm_batch* b) {
     ExpandWireArgs a{};
-    const size_t src[6] = {L.w_bases4, L.w_qual, L.w_ins, L.w_del, L.w_gcp, L.w_hap4};
-    uint8_t* const dst[6] = {b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, b->d_hap};
-    const uint32_t w[6] = {4, L.ww.qual, L.ww.ins, L.ww.del, L.ww.gcp, 4};
-    uint64_t blocks = 0;
-    for (int k = 0; k < 6; ++k) {
-        a.src[k] = b->slab.dev + src[k]; a.dst[k] = dst[k]; a.w[k] = w[k];
-        a.n[k] = k == 5 ? L.hap_bytes : L.read_bytes;
-        a.block_first[k] = (uint32_t)blocks;
-        blocks += ((a.n[k] + 7) / 8 + kExpandBlock - 1) / kExpandBlock;
-        if (blocks > 0x7FFFFFFFull) { set_error("batch too large for one expansion launch"); return -E2BIG; }
-    }
-    a.block_first[6] = (uint32_t)blocks;
+    if (const int rc = expand_grid(L, a.n, a.w, a.block_first)) return rc;
+    for (int k = 0; k < kSeqArrays; ++k) { a.src[k] = b->slab.dev + L.wseq[k]; a.dst[k] = b->dev(b->lay.seq[k]); }
     a.fill = L.ww.gcp_const;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(pairhmm_expand_wire, dim3((uint32_t)blocks), dim3(kExpandBlock), 0, s, a);
+    if (a.block_first[kSeqArrays] == 0) return 0;
+    hipLaunchKernelGGL(pairhmm_expand_wire, dim3(a.block_first[kSeqArrays]), dim3(kExpandBlock), 0, s, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -797,39 +437,33 @@ int launch_expand_wire(hipStream_t s, const SlabLayout& L, mgx_pairhmm_batch* b)
 // Upload of a pair-list batch: one copy out of the pinned mirror, or (very large batches) one per array.
 int upload_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, const SlabLayout& L, const Job* jobs,
                  mgx_pairhmm_batch* b) {
-    const uint64_t read_bytes = L.read_bytes, hap_bytes = L.hap_bytes;
     uint8_t* dv = b->slab.dev;
+    uint8_t* pin = b->slab.pin;
     hipStream_t s = c->copy;
     if (L.wire) {
-        stage_wire(in, plan, L, b->slab.pin);
-        HIP_TRY(hipMemcpyAsync(dv, b->slab.pin, b->in_bytes, hipMemcpyHostToDevice, s));
+        stage_wire(in, plan, L, pin);
+        HIP_TRY(hipMemcpyAsync(dv, pin, b->lay.in_bytes, hipMemcpyHostToDevice, s));
         if (const int rc = launch_expand_wire(s, L, b)) return rc;
     } else if (L.staged) {
-        uint8_t* pin = b->slab.pin;
         if (plan) {
-            mgx::pack_copy(in, *plan, pin + L.bases, pin + L.qual, pin + L.ins, pin + L.del, pin + L.gcp, pin + L.hap);
-        } else if (read_bytes + hap_bytes < (32u << 20)) {
-            memcpy(pin + L.bases, in->bases, read_bytes); memcpy(pin + L.qual, in->qual, read_bytes);
-            memcpy(pin + L.ins, in->ins, read_bytes);     memcpy(pin + L.del, in->del, read_bytes);
-            memcpy(pin + L.gcp, in->gcp, read_bytes);     memcpy(pin + L.hap, in->hap_bases, hap_bytes);
+            mgx::pack_copy(in, *plan, pin + L.seq[kSeqBases], pin + L.seq[kSeqQual], pin + L.seq[kSeqIns], pin + L.seq[kSeqDel],
+                           pin + L.seq[kSeqGcp], pin + L.seq[kSeqHap]);
         } else {
             // a large one-shot batch: the six arrays are staged by six threads (one core copies ~10 GB/s)
-            const void* src[6] = {in->bases, in->qual, in->ins, in->del, in->gcp, in->hap_bases};
-            uint8_t* dst[6] = {pin + L.bases, pin + L.qual, pin + L.ins, pin + L.del, pin + L.gcp, pin + L.hap};
-            const size_t len[6] = {(size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)read_bytes, (size_t)hap_bytes};
-            std::thread th[6];
-            for (int k = 0; k < 6; ++k) th[k] = std::thread([=] { memcpy(dst[k], src[k], len[k]); });
-            for (auto& t : th) t.join();
+            const bool threaded = L.read_bytes + L.hap_bytes >= (32u << 20);
+            std::thread th[kSeqArrays];
+            for (int k = 0; k < kSeqArrays; ++k) {
+                uint8_t* const to = pin + L.seq[k];
+                const size_t len = L.seq_len(k);
+                if (threaded) th[k] = std::thread([=] { memcpy(to, seq_src(in, k), len); });
+                else memcpy(to, seq_src(in, k), len);
+            }
+            if (threaded) for (auto& t : th) t.join();
         }
-        HIP_TRY(hipMemcpyAsync(dv, pin, b->in_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dv, pin, b->lay.in_bytes, hipMemcpyHostToDevice, s));
     } else {
-        HIP_TRY(hipMemcpyAsync(b->d_jobs, jobs, L.n * sizeof(Job), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_bases, in->bases, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_qual, in->qual, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_ins, in->ins, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_del, in->del, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_gcp, in->gcp, read_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->d_hap, in->hap_bases, hap_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->dev<Job>(b->lay.jobs), jobs, L.n * sizeof(Job), hipMemcpyHostToDevice, s));
+        for (int k = 0; k < kSeqArrays; ++k) HIP_TRY(hipMemcpyAsync(b->dev(b->lay.seq[k]), seq_src(in, k), L.seq_len(k), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));          // the caller's buffers may go away after we return
         b->host_jobs.clear(); b->host_jobs.shrink_to_fit();
     }
@@ -842,92 +476,29 @@ int upload_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::Pac
 // they are.  plan != nullptr: test cases [plan->lo, plan->hi) of `in`, only the sequences they reference
 // (gathered by the packer, pairhmm_pack.h) -- the form the host work queue uploads.
 int create_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::PackPlan* plan, mgx_pairhmm_batch* b) {
-    const uint64_t n = plan ? plan->hi - plan->lo : in->n_pairs;
-    const uint32_t* pr = plan ? plan->pair_read.data() : in->pair_read;
-    const uint32_t* ph = plan ? plan->pair_hap.data() : in->pair_hap;
-    const uint64_t* roff = plan ? plan->roff.data() : in->read_off;
-    const uint64_t* hoff = plan ? plan->hoff.data() : in->hap_off;
-    const uint64_t n_reads = plan ? plan->lread.size() : in->n_reads, n_haps = plan ? plan->lhap.size() : in->n_haps;
+    PairView v;
+    v.n = plan ? plan->hi - plan->lo : in->n_pairs;
+    v.pr = plan ? plan->pair_read.data() : in->pair_read;
+    v.ph = plan ? plan->pair_hap.data() : in->pair_hap;
+    v.roff = plan ? plan->roff.data() : in->read_off;
+    v.hoff = plan ? plan->hoff.data() : in->hap_off;
+    v.n_reads = plan ? plan->lread.size() : in->n_reads; v.n_haps = plan ? plan->lhap.size() : in->n_haps;
     int rc;
-    b->n_pairs = n;
-    b->stats.n_pairs = n;
-
-    // ---- bin by (G, RPL), then counting-sort every bin by haplotype length -------------
-    std::vector<uint32_t> bin_of(n);
-    uint64_t count[kBins] = {0};
-    uint32_t max_h = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t r = pr[i], h = ph[i];
-        if (r >= n_reads || h >= n_haps) { set_error("test case %llu: index out of range", (unsigned long long)i); return -EINVAL; }
-        const uint64_t R = roff[r + 1] - roff[r];
-        const uint64_t H = hoff[h + 1] - hoff[h];
-        if (R == 0 || H == 0) { set_error("test case %llu: empty read or haplotype", (unsigned long long)i); return -EINVAL; }
-        int G, RPL;
-        shape_of((uint32_t)std::min<uint64_t>(R, 0xFFFFFFFFull), &G, &RPL);
-        if (G == 0) { set_error("test case %llu: read of %llu bases exceeds the %d-row limit", (unsigned long long)i, (unsigned long long)R, kMaxRowsStrip); return -E2BIG; }
-        if (H > 0x7FFFFFF0ull) { set_error("haplotype too long"); return -E2BIG; }
-        const int bi = bin_index(G, RPL);
-        bin_of[i] = (uint32_t)bi;
-        count[bi]++;
-        max_h = std::max<uint32_t>(max_h, (uint32_t)H);
-        b->stats.cells += R * H;
-        b->stats.alg_bytes += 5 * R + H + 4;
-    }
-    // A bin with few jobs is folded into the next larger row class of the same group width (any
-    // RPL >= ceil(R/G) is valid, it only leaves lanes unused): a region-sized batch then needs one
-    // fp32 + one fp64 launch instead of one pair per read-length class.
-    {
-        int remap[kBins];
-        merge_small_bins(count, remap);
-        for (uint64_t i = 0; i < n; ++i) bin_of[i] = (uint32_t)remap[bin_of[i]];
-    }
-    // ---- one slab for everything; layout decided before the jobs are written so that they can be
-    //      built directly in the pinned mirror
-    SlabLayout L;
-    L.n = n; L.n_reads = n_reads; L.n_haps = n_haps; L.read_bytes = roff[n_reads]; L.hap_bytes = hoff[n_haps];
+    b->n_pairs = v.n;
+    b->stats.n_pairs = v.n;
+    PairClasses pc;
+    if ((rc = classify_pairs(v, env_min_g(), &pc))) return rc;
+    // one slab for everything; the layout is decided before the jobs are written so that they can be built directly in
+    // the pinned mirror
+    SlabLayout& L = b->lay;
+    L.n = v.n; L.n_reads = v.n_reads; L.n_haps = v.n_haps; L.read_bytes = v.roff[v.n_reads]; L.hap_bytes = v.hoff[v.n_haps];
     if (c->wire) { L.wire = true; L.ww = mgx::wire::scan_widths(in, plan); }      // the widths decide the layout
-    if ((rc = lay_out_slab(c, plan != nullptr, &L, b))) return rc;
-    if (!L.staged) b->host_jobs.resize(n);
+    plan_slab(plan != nullptr, &L);
+    if ((rc = acquire_slab(c, L.total, L.staged ? L.pin_bytes : 0, &b->slab))) return rc;
+    if (!L.staged) b->host_jobs.resize(v.n);
     Job* jobs = L.staged ? (Job*)(b->slab.pin + L.jobs) : b->host_jobs.data();
-    {
-        // key = (bin, H descending): counting sort on H inside each bin keeps the wavefront's groups
-        // (consecutive jobs) at near-equal step counts, and longest first means the last workgroups of a
-        // launch -- its drain -- are the shortest jobs.
-        std::vector<uint64_t> bin_start(kBins + 1, 0);
-        for (int k = 0; k < kBins; ++k) bin_start[k + 1] = bin_start[k] + count[k];
-        std::vector<std::vector<uint32_t>> hist(kBins);
-        for (int k = 0; k < kBins; ++k) if (count[k]) hist[k].assign((size_t)max_h + 2, 0);
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint32_t h = ph[i];
-            const uint32_t H = (uint32_t)(hoff[h + 1] - hoff[h]);
-            hist[bin_of[i]][(max_h - H) + 1]++;
-        }
-        for (int k = 0; k < kBins; ++k)
-            for (size_t x = 1; x < hist[k].size(); ++x) hist[k][x] += hist[k][x - 1];
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint32_t r = pr[i], h = ph[i];
-            const uint32_t R = (uint32_t)(roff[r + 1] - roff[r]);
-            const uint32_t H = (uint32_t)(hoff[h + 1] - hoff[h]);
-            const int k = (int)bin_of[i];
-            Job& jb = jobs[bin_start[k] + hist[k][max_h - H]++];
-            jb.read_off = roff[r]; jb.hap_off = hoff[h];
-            jb.R = R; jb.H = H; jb.pair = (uint32_t)i; jb.pad_ = 0;
-        }
-        for (int k = 0; k < kBins; ++k) {
-            if (!count[k]) continue;
-            Bin bin;
-            bin_shape(k, &bin);
-            bin.job_begin = (uint32_t)bin_start[k];
-            bin.job_count = (uint32_t)count[k];
-            for (uint64_t q = bin_start[k]; q < bin_start[k + 1]; ++q) {
-                bin.max_h = std::max(bin.max_h, jobs[q].H);
-                bin.cells += (uint64_t)jobs[q].R * jobs[q].H;
-                bin.alg_bytes += 5ull * jobs[q].R + jobs[q].H + 4;
-            }
-            if ((rc = finalize_bin(bin, c->n_cu))) return rc;
-            b->bins.push_back(bin);
-        }
-    }
+    if ((rc = sort_pairs(v, pc, c->n_cu, env_block(), jobs, &b->bins))) return rc;
+    sum_stats(b);
     return upload_pairs(c, in, plan, L, jobs, b);
 }
 
@@ -952,14 +523,6 @@ int mgx_pairhmm_batch_create(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in,
 
 namespace {
 
-constexpr int kSharedCount = 63;      // counter slot of the narrow classes' shared fp64 re-run list
-constexpr int kExactCount = 62;       // ... and of the exact tier's list (second half of d_rerun_list)
-
-// Re-runs in double precision: the "narrow" classes (at most 16 lanes x 8 rows: every read up to 128 bases) append
-// to ONE list (their jobs are a prefix of the job array) that ONE fp64 launch of the 16 x RPLd shape processes --
-// a test case's value does not depend on the shape that computes it; wider classes keep a list and a launch each.
-inline bool is_narrow(const Bin& bn) { return bn.G <= 16 && bn.G * bn.RPL <= 16 * kNarrowMaxRPL; }
-
 // what the steps of one mgx_pairhmm_batch_run share
 struct Run {
     mgx_pairhmm* c = nullptr;
@@ -967,11 +530,9 @@ struct Run {
     hipStream_t s = nullptr;                   // the compute stream
     bool timing = false, force_f64 = false;
     hipEvent_t* ev = nullptr;                  // this run's event set (timing only)
-    int n_str = 1;                             // streams the classes are dealt to
     KernelArgs base{};                         // the arguments every launch starts from
     std::vector<char> in_multi;                // classes that a multi-class launch has computed
-    size_t first_narrow = 0;                   // books the shared fp64 launch; bins.size() if there is no narrow class
-    uint32_t n_narrow_jobs = 0, narrow_max_h = 0, narrow_rows = 0;
+    NarrowExtent narrow;                       // what the shared fp64 launch covers; narrow.first books it
 };
 
 // boundary rows of the strip-mined class and of the exact tier: one array per context, grown on demand
@@ -998,122 +559,85 @@ int pick_event_set(Run& r) {
     return 0;
 }
 
-// the compute stream waits for the upload, the counters and flags are cleared, the side streams fork
+// the compute stream waits for the upload, the counters and flags are cleared
 int begin_run(Run& r) {
     mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
     if (b->uploaded) HIP_TRY(hipStreamWaitEvent(r.s, b->uploaded, 0));
-    HIP_TRY(hipMemsetAsync(b->d_rerun_count, 0, kCounters * sizeof(uint32_t), r.s));
-    HIP_TRY(hipMemsetAsync(b->d_used, 0, b->n_pairs, r.s));
-    r.n_str = (int)std::min<size_t>((size_t)c->n_streams, b->bins.size());
-    if (r.n_str > 1) {
-        HIP_TRY(hipEventRecord(c->ev_fork, r.s));
-        for (int q = 0; q + 1 < r.n_str; ++q) HIP_TRY(hipStreamWaitEvent(c->aux[q], c->ev_fork, 0));
-    }
+    HIP_TRY(hipMemsetAsync(b->counters(), 0, kCounters * sizeof(uint32_t), r.s));
+    HIP_TRY(hipMemsetAsync(b->dev(b->lay.o_used), 0, b->n_pairs, r.s));
     KernelArgs& base = r.base;
-    base.jobs = b->d_jobs;
-    base.bases = b->d_bases; base.qual = b->d_qual; base.ins = b->d_ins; base.del = b->d_del;
-    base.gcp = b->d_gcp; base.hap_bases = b->d_hap;
-    base.out_log10 = b->d_out; base.used_f64 = b->d_used;
-    base.nhap_list = b->d_nhap_list; base.nhap_count = b->d_rerun_count + kNhapCount;
+    base.jobs = b->dev<Job>(b->lay.jobs);
+    base.bases = b->dev(b->lay.seq[kSeqBases]); base.qual = b->dev(b->lay.seq[kSeqQual]); base.ins = b->dev(b->lay.seq[kSeqIns]); base.del = b->dev(b->lay.seq[kSeqDel]);
+    base.gcp = b->dev(b->lay.seq[kSeqGcp]); base.hap_bases = b->dev(b->lay.seq[kSeqHap]);
+    base.out_log10 = b->dev<double>(b->lay.o_out); base.used_f64 = b->dev(b->lay.o_used);
+    base.nhap_list = b->dev<uint32_t>(b->lay.nlist); base.nhap_count = b->counters() + kNhapCount;
     base.log10_initial_f = c->log10_initial_f;
     base.log10_initial_d = c->log10_initial_d;
     return 0;
 }
 
-// extent of the narrow classes: what the shared fp64 launch has to cover
-void survey_narrow(Run& r) {
-    const std::vector<Bin>& bins = r.b->bins;
-    r.first_narrow = bins.size();
-    for (size_t k = 0; k < bins.size(); ++k) {
-        const Bin& bn = bins[k];
-        if (!is_narrow(bn)) continue;
-        if (r.first_narrow == bins.size()) r.first_narrow = k;
-        r.n_narrow_jobs = std::max(r.n_narrow_jobs, bn.job_begin + bn.job_count);
-        r.narrow_max_h = std::max(r.narrow_max_h, bn.max_h);
-        r.narrow_rows = std::max(r.narrow_rows, (uint32_t)(bn.G * bn.RPL));
-    }
-}
-
 // an fp64 launch over a job list or a class; what it leaves near the flush-to-zero threshold goes to the exact tier's list
-int launch_f64(const Run& r, KernelArgs a, int Gd, int RPLd, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t sk) {
+int launch_f64(const Run& r, KernelArgs a, int Gd, int RPLd, uint32_t grid, uint32_t block, uint32_t lds) {
     const mgx_pairhmm* c = r.c;
     a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
-    a.rerun_list = r.b->d_rerun_list + r.b->n_pairs; a.rerun_count = r.b->d_rerun_count + kExactCount;      // job_list / n_dyn are set: the fp64 tier appends here
+    a.rerun_list = r.b->rerun_list() + r.b->n_pairs; a.rerun_count = r.b->counters() + kExactCount;      // job_list / n_dyn are set: the fp64 tier appends here
     KernelFn f = a.strip_scratch ? (KernelFn)pairhmm_fwd_strip<double> : pick_kernel<double>(Gd, RPLd);
     if (!f) { set_error("no fp64 kernel for G=%d RPL=%d", Gd, RPLd); return -ENOSYS; }
-    hipLaunchKernelGGL(f, dim3(grid), dim3(block), lds, sk, a);
+    hipLaunchKernelGGL(f, dim3(grid), dim3(block), lds, r.s, a);
     return 0;
 }
 
 // one multi-class launch over the classes `set` (lane-width set gset), booked on the member with the most cells
-int launch_multi(Run& r, int gset, std::vector<size_t>& set) {
+int launch_multi(Run& r, int gset, const MultiSet& ms) {
     mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
-    // most rows per lane first (the costliest workgroups), wider groups first among equals
-    std::stable_sort(set.begin(), set.end(), [&](size_t x, size_t y) {
-        const Bin &bx = b->bins[x], &by = b->bins[y];
-        return bx.RPL != by.RPL ? bx.RPL > by.RPL : bx.G > by.G;
-    });
+    const std::vector<size_t>& set = ms.members;
     MultiArgs m{};
     m.a = r.base;
-    m.a.rerun_list = b->d_rerun_list; m.a.rerun_count = b->d_rerun_count + kSharedCount;
+    m.a.rerun_list = b->rerun_list(); m.a.rerun_count = b->counters() + kSharedCount;
     m.a.job_list = nullptr; m.a.n_dyn = nullptr;
     m.a.ph2pr = c->d_ph2pr_f; m.a.mm = c->d_mm_f; m.a.ph2pr_div3 = c->d_div3_f; m.a.gap_ratio = c->d_ratio_f;
     m.n_bins = (uint32_t)set.size();
-    uint32_t blocks = 0, lds = 0;
     size_t book = set[0];
     uint64_t cells = 0, bytes = 0;
     for (size_t q = 0; q < set.size(); ++q) {
         const Bin& bn = b->bins[set[q]];
-        m.block_first[q] = blocks; blocks += bn.grid_f32;
         m.job_first[q] = bn.job_begin; m.job_count[q] = bn.job_count; m.lds_stride[q] = bn.lds_stride;
         m.G[q] = (uint8_t)bn.G; m.RPL[q] = (uint8_t)bn.RPL; m.bin[q] = (uint8_t)set[q];
-        lds = std::max(lds, lds_bytes(bn, true, 4));
         if (bn.cells > b->bins[book].cells) book = set[q];
         cells += bn.cells; bytes += bn.alg_bytes;
         r.in_multi[set[q]] = 1;
         b->acct_cells[set[q]] = 0; b->acct_bytes[set[q]] = 0;
     }
-    m.block_first[set.size()] = blocks;
+    memcpy(m.block_first, ms.block_first, sizeof m.block_first);
     b->acct_cells[book] = cells; b->acct_bytes[book] = bytes; b->acct_multi[book] = (int8_t)(1 + gset);
     if (r.timing) for (size_t q : set) if (q != book) { HIP_TRY(hipEventRecord(r.ev[4 * q + 0], r.s)); HIP_TRY(hipEventRecord(r.ev[4 * q + 1], r.s)); }
     if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * book + 0], r.s));
-    if (gset == 0) hipLaunchKernelGGL(pairhmm_fwd_multi<0>, dim3(blocks), dim3(64), lds, r.s, m);
-    else           hipLaunchKernelGGL(pairhmm_fwd_multi<1>, dim3(blocks), dim3(64), lds, r.s, m);
+    if (gset == 0) hipLaunchKernelGGL(pairhmm_fwd_multi<0>, dim3(ms.block_first[set.size()]), dim3(64), ms.lds, r.s, m);
+    else           hipLaunchKernelGGL(pairhmm_fwd_multi<1>, dim3(ms.block_first[set.size()]), dim3(64), ms.lds, r.s, m);
     if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * book + 1], r.s));
     return 0;
 }
 
-// Several narrow classes: one multi-class launch per lane-width set instead of one launch per class.
-// Only SMALL classes share a launch: measured on an MI355X (profiles/r02_pairhmm_multi_ab.txt) the common launch
-// costs every class the register budget of the hungriest one (131-149 VGPRs: 3 wavefronts per SIMD; 4 when forced,
-// with spills), which outweighs the saved drains for classes that fill the device on their own (ragged 1 M test
-// cases, nine classes of ~29 000 workgroups: 4462 -> 4343 GCUPS) but not for classes of a few thousand workgroups
-// (reads of 20-32 bases: 2764 -> 3009; region-sized batches).  MGX_PAIRHMM_MULTI=0 keeps the per-class launches; any
-// other value is the default.  (The same build forced to 4 wavefronts per SIMD, and sharing a launch among all narrow
-// classes whatever their size, were measured too and lost: DESIGN.md 3.5.)
+// Several small narrow classes: one multi-class launch per lane-width set instead of one launch per class (multi_set,
+// pairhmm_plan.h).  MGX_PAIRHMM_MULTI=0 keeps the per-class launches; any other value is the default.
 int launch_multi_classes(Run& r) {
     mgx_pairhmm_batch* b = r.b;
     static const bool multi_ok = [] { const char* e = getenv("MGX_PAIRHMM_MULTI"); return !e || atoi(e) != 0; }();
-    const uint32_t multi_below = (uint32_t)r.c->n_cu * 64u;     // workgroups; ~5 device fills
     r.in_multi.assign(b->bins.size(), 0);
     b->acct_cells.assign(b->bins.size(), 0); b->acct_bytes.assign(b->bins.size(), 0); b->acct_multi.assign(b->bins.size(), 0);
     for (size_t k = 0; k < b->bins.size(); ++k) { b->acct_cells[k] = b->bins[k].cells; b->acct_bytes[k] = b->bins[k].alg_bytes; }
     if (!multi_ok || r.force_f64) return 0;
     for (int gset = 0; gset < 2; ++gset) {
-        std::vector<size_t> set;
-        for (size_t k = 0; k < b->bins.size(); ++k) {
-            const Bin& bn = b->bins[k];
-            if (is_narrow(bn) && bn.RPL <= kNarrowMaxRPL && bn.block == 64 && bn.grid_f32 < multi_below && (gset == 0 ? bn.G == 16 : bn.G < 16)) set.push_back(k);
-        }
-        if (set.size() < 2 || set.size() > (size_t)kMultiBins) continue;
-        if (const int rc = launch_multi(r, gset, set)) return rc;
+        const MultiSet ms = multi_set(b->bins, gset, r.c->n_cu);
+        if (ms.members.empty()) continue;
+        if (const int rc = launch_multi(r, gset, ms)) return rc;
     }
     return 0;
 }
 
-// class k on stream sk: its fp32 launch unless a multi-class launch has done it, then the fp64 re-run of its own list
+// class k: its fp32 launch unless a multi-class launch has done it, then the fp64 re-run of its own list
 // (the narrow classes share one, launch_shared_f64)
-int launch_class(Run& r, size_t k, hipStream_t sk) {
+int launch_class(Run& r, size_t k) {
     mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
     hipEvent_t* ev = r.ev;
     const Bin& bin = b->bins[k];
@@ -1124,12 +648,12 @@ int launch_class(Run& r, size_t k, hipStream_t sk) {
         if (const int rc = ensure_strip_scratch(c, (size_t)bin.grid_f32 * 6u * a.strip_stride * sizeof(double))) return rc;
         a.strip_scratch = c->d_strip;
     }
-    a.rerun_list = shared ? b->d_rerun_list : b->d_rerun_list + bin.job_begin;
-    a.rerun_count = b->d_rerun_count + (shared ? kSharedCount : (int)k);
+    a.rerun_list = shared ? b->rerun_list() : b->rerun_list() + bin.job_begin;
+    a.rerun_count = b->counters() + (shared ? kSharedCount : (int)k);
     a.lds_stride = bin.lds_stride;
     a.job_first = bin.job_begin;
-    a.nhap_list = b->d_nhap_list + bin.job_begin;
-    a.nhap_count = b->d_rerun_count + kNhapCount + (int)k;
+    a.nhap_list = b->dev<uint32_t>(b->lay.nlist) + bin.job_begin;
+    a.nhap_count = b->counters() + kNhapCount + (int)k;
     if (!r.force_f64) {
         // four code columns first (the strip-mined class: five), then the class's N-haplotype list with five; both
         // append their underflows to the same fp64 list.  A multi-class launch has done the first of the two.
@@ -1139,58 +663,47 @@ int launch_class(Run& r, size_t k, hipStream_t sk) {
             a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count;
             KernelFn f = bin.strip ? (KernelFn)pairhmm_fwd_strip<float> : pick_kernel<float, 4>(bin.G, bin.RPL);
             if (!f) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
-            if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], sk));
-            hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true, bin.strip ? kMaxCodes : 4), sk, a);
+            if (r.timing) HIP_TRY(hipEventRecord(ev[4 * k + 0], r.s));
+            hipLaunchKernelGGL(f, dim3(bin.grid_f32), dim3(bin.block), lds_bytes(bin, true, bin.strip ? kMaxCodes : 4), r.s, a);
         }
         if (!bin.strip) {
             KernelFn f5 = pick_kernel<float, kMaxCodes>(bin.G, bin.RPL);
             if (!f5) { set_error("no fp32 kernel for G=%d RPL=%d", bin.G, bin.RPL); return -ENOSYS; }
             a.job_list = a.nhap_list; a.n_dyn = a.nhap_count; a.n_static = 0;
-            hipLaunchKernelGGL(f5, dim3(bin.grid_nhap), dim3(bin.block), lds_bytes(bin, true, kMaxCodes), sk, a);
+            hipLaunchKernelGGL(f5, dim3(bin.grid_nhap), dim3(bin.block), lds_bytes(bin, true, kMaxCodes), r.s, a);
         }
-        if (r.timing && first) HIP_TRY(hipEventRecord(ev[4 * k + 1], sk));
+        if (r.timing && first) HIP_TRY(hipEventRecord(ev[4 * k + 1], r.s));
     }
-    const bool books_shared = shared && k == r.first_narrow;      // the shared launch is booked on the first narrow class
-    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 2], sk));
+    const bool books_shared = shared && k == r.narrow.first;      // the shared launch is booked on the first narrow class
+    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 2], r.s));
     if (!shared) {
         if (r.force_f64) { a.job_list = nullptr; a.n_dyn = nullptr; a.n_static = bin.job_count; }
         else { a.job_list = a.rerun_list; a.n_dyn = a.rerun_count; a.n_static = 0; }
-        const int rc = launch_f64(r, a, bin.Gd, bin.RPLd, r.force_f64 ? bin.grid_f64_all : bin.grid_f64, bin.block, lds_bytes(bin, false), sk);
+        const int rc = launch_f64(r, a, bin.Gd, bin.RPLd, r.force_f64 ? bin.grid_f64_all : bin.grid_f64, bin.block, lds_bytes(bin, false));
         if (rc) return rc;
     }
-    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 3], sk));
+    if (r.timing && !books_shared) HIP_TRY(hipEventRecord(ev[4 * k + 3], r.s));
     return 0;
 }
 
-// largest class first, classes dealt round-robin to the compute stream and the side streams, which then join it
+// every class on the compute stream, largest first
 int launch_classes(Run& r) {
-    mgx_pairhmm* c = r.c; mgx_pairhmm_batch* b = r.b;
-    std::vector<size_t> order(b->bins.size());
-    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return b->bins[x].cells > b->bins[y].cells; });
-    for (size_t at = 0; at < order.size(); ++at) {
-        hipStream_t sk = (int)(at % (size_t)r.n_str) == 0 ? r.s : c->aux[at % (size_t)r.n_str - 1];
-        if (r.in_multi[order[at]]) sk = r.s;      // its five-code launch follows the multi-class launch, which ran there
-        if (const int rc = launch_class(r, order[at], sk)) return rc;
-    }
-    for (int q = 0; q + 1 < r.n_str; ++q) {
-        HIP_TRY(hipEventRecord(c->ev_join[q], c->aux[q]));
-        HIP_TRY(hipStreamWaitEvent(r.s, c->ev_join[q], 0));
-    }
+    for (size_t k : class_order(r.b->bins))
+        if (const int rc = launch_class(r, k)) return rc;
     return 0;
 }
 
 // the narrow classes' shared re-run list in one fp64 launch
 int launch_shared_f64(Run& r) {
-    if (!r.n_narrow_jobs || r.force_f64) return 0;
+    const NarrowExtent& nw = r.narrow;
+    if (!nw.n_jobs || r.force_f64) return 0;
     KernelArgs a = r.base;
-    a.job_list = r.b->d_rerun_list; a.n_dyn = r.b->d_rerun_count + kSharedCount; a.n_static = 0; a.job_first = 0;
-    a.lds_stride = (r.narrow_max_h + 2u * 16u + 8u + 15u) & ~15u;
-    const int RPLd = (int)((r.narrow_rows + 15) / 16);
-    const uint32_t grid = std::min<uint32_t>((r.n_narrow_jobs + 3) / 4, (uint32_t)r.c->n_cu * 8u);
-    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * r.first_narrow + 2], r.s));
-    if (const int rc = launch_f64(r, a, 16, RPLd, grid, 64, 4u * a.lds_stride, r.s)) return rc;
-    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * r.first_narrow + 3], r.s));
+    a.job_list = r.b->rerun_list(); a.n_dyn = r.b->counters() + kSharedCount; a.n_static = 0; a.job_first = 0;
+    a.lds_stride = hap_stride(nw.max_h, 16);
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * nw.first + 2], r.s));
+    const uint32_t grid = std::min<uint32_t>((nw.n_jobs + 3) / 4, (uint32_t)r.c->n_cu * 8u);      // 16 lanes: four test cases per workgroup
+    if (const int rc = launch_f64(r, a, 16, (int)((nw.rows + 15) / 16), grid, 64, 4u * a.lds_stride)) return rc;
+    if (r.timing) HIP_TRY(hipEventRecord(r.ev[4 * nw.first + 3], r.s));
     return 0;
 }
 
@@ -1202,9 +715,9 @@ int launch_exact(Run& r) {
     for (const Bin& bn : b->bins) max_h = std::max(max_h, bn.max_h);
     KernelArgs a = r.base;
     a.ph2pr = c->d_ph2pr_d; a.mm = c->d_mm_d; a.ph2pr_div3 = c->d_div3_d; a.gap_ratio = c->d_ratio_d;
-    a.job_list = b->d_rerun_list + b->n_pairs; a.n_dyn = b->d_rerun_count + kExactCount; a.n_static = 0; a.job_first = 0;
+    a.job_list = b->rerun_list() + b->n_pairs; a.n_dyn = b->counters() + kExactCount; a.n_static = 0; a.job_first = 0;
     a.rerun_list = nullptr; a.rerun_count = nullptr;
-    a.lds_stride = (max_h + 2u * 64u + 8u + 15u) & ~15u;
+    a.lds_stride = hap_stride(max_h, 64);
     a.strip_stride = (max_h + 63u) & ~63u;
     const size_t per_wg = 6u * (size_t)a.strip_stride * sizeof(double);
     const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)b->n_pairs, (size_t)c->n_cu * 2u, (size_t)(256u << 20) / per_wg}));
@@ -1217,9 +730,9 @@ int launch_exact(Run& r) {
 // whole-region batches: normalise / filter every read's row of the output
 void launch_epilogue(Run& r) {
     const mgx_pairhmm_batch* b = r.b;
-    if (!b->has_model) return;
-    hipLaunchKernelGGL(pairhmm_normalize_filter_rows, dim3((b->n_reads + 3) / 4), dim3(256), 0, r.s, b->d_out, b->d_read_len,
-                       b->d_row_off, b->d_row_nh, b->n_reads, b->log10_rate, b->max_err, b->d_keep);
+    if (!b->lay.model) return;
+    hipLaunchKernelGGL(pairhmm_normalize_filter_rows, dim3(((uint32_t)b->lay.n_reads + 3) / 4), dim3(256), 0, r.s, b->dev<double>(b->lay.o_out), b->dev<uint64_t>(b->lay.rlen),
+                       b->dev<uint32_t>(b->lay.roff), b->dev<uint32_t>(b->lay.rnh), (uint32_t)b->lay.n_reads, b->log10_rate, b->max_err, b->dev(b->lay.o_keep));
 }
 
 }  // namespace
@@ -1235,7 +748,7 @@ int mgx_pairhmm_batch_run(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
     int rc;
     if ((rc = pick_event_set(r))) return rc;
     if ((rc = begin_run(r))) return rc;
-    survey_narrow(r);
+    r.narrow = survey_narrow(b->bins);
     if ((rc = launch_multi_classes(r))) return rc;
     if ((rc = launch_classes(r))) return rc;
     if ((rc = launch_shared_f64(r))) return rc;
@@ -1252,15 +765,14 @@ int mgx_pairhmm_batch_run(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
 int mgx_pairhmm_batch_read_inputs(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, uint8_t* bases, uint8_t* qual, uint8_t* ins,
                                   uint8_t* del, uint8_t* gcp, uint8_t* hap) {
     if (!c || !b) { set_error("ctx/batch is NULL"); return -EINVAL; }
-    if ((b->read_bytes && (!bases || !qual || !ins || !del || !gcp)) || (b->hap_bytes && !hap)) { set_error("NULL argument"); return -EINVAL; }
+    if ((b->lay.read_bytes && (!bases || !qual || !ins || !del || !gcp)) || (b->lay.hap_bytes && !hap)) { set_error("NULL argument"); return -EINVAL; }
     HIP_TRY(hipSetDevice(c->device));
     if (b->n_pairs == 0) return 0;
     if (b->uploaded) HIP_TRY(hipEventSynchronize(b->uploaded));      // the copy and, in the wire form, the expansion behind it
-    uint8_t* const host[6] = {bases, qual, ins, del, gcp, hap};
-    const uint8_t* const dev[6] = {b->d_bases, b->d_qual, b->d_ins, b->d_del, b->d_gcp, b->d_hap};
-    for (int k = 0; k < 6; ++k) {
-        const uint64_t len = k == 5 ? b->hap_bytes : b->read_bytes;
-        if (len) HIP_TRY(hipMemcpy(host[k], dev[k], len, hipMemcpyDeviceToHost));
+    uint8_t* const host[kSeqArrays] = {bases, qual, ins, del, gcp, hap};
+    for (int k = 0; k < kSeqArrays; ++k) {
+        const uint64_t len = k == kSeqHap ? b->lay.hap_bytes : b->lay.read_bytes;
+        if (len) HIP_TRY(hipMemcpy(host[k], b->dev(b->lay.seq[k]), len, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -1284,11 +796,11 @@ int mgx_pairhmm_batch_stats(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, mgx_pairhm
     st.n_nhap_f32 = 0;
     if (b->ran && b->n_pairs) {
         std::vector<uint32_t> cnt(kCounters);
-        HIP_TRY(hipMemcpy(cnt.data(), b->d_rerun_count, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cnt.data(), b->counters(), kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < b->bins.size(); ++k) st.n_nhap_f32 += cnt[kNhapCount + k];
         for (size_t k = 0; k < b->bins.size(); ++k) st.n_rerun_f64 += force_f64 ? b->bins[k].job_count : cnt[k];
-        if (!force_f64) st.n_rerun_f64 += cnt[63];          // the narrow classes' shared list
-        st.n_exact = cnt[62];
+        if (!force_f64) st.n_rerun_f64 += cnt[kSharedCount];          // the narrow classes' shared list
+        st.n_exact = cnt[kExactCount];
     }
     st.ms_f32 = st.ms_f64 = st.ms_f32_dominant = 0;
     st.dominant_cells = st.dominant_alg_bytes = 0;
@@ -1339,7 +851,7 @@ namespace {
 int fetch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, size_t bytes) {
     hipStream_t s = c->d2h;
     if (b->done) HIP_TRY(hipStreamWaitEvent(s, b->done, 0));
-    HIP_TRY(hipMemcpyAsync(b->slab.pin + b->o_out, b->d_out, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->slab.pin + b->lay.o_out, b->dev<double>(b->lay.o_out), bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -1348,8 +860,8 @@ int fetch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, size_t bytes) {
 // returns it), out of the pinned mirror into the caller's array of each region; keep may be NULL, and so may its entries.
 void scatter_region_results(const mgx_pairhmm_batch* b, const std::vector<uint64_t>& base, const mgx_pairhmm_input_t* regions,
                             uint32_t g0, uint32_t g1, double* const* out, uint8_t* const* keep) {
-    const double* all = (const double*)(b->slab.pin + b->o_out);
-    const uint8_t* kept = b->slab.pin + b->o_keep;
+    const double* all = (const double*)(b->slab.pin + b->lay.o_out);
+    const uint8_t* kept = b->slab.pin + b->lay.o_keep;
     uint64_t r_at = 0;
     for (uint32_t g = g0; g < g1; ++g) {
         const uint64_t a = base[g - g0], e = base[g - g0 + 1];
@@ -1359,17 +871,105 @@ void scatter_region_results(const mgx_pairhmm_batch* b, const std::vector<uint64
     }
 }
 
-// Cuts a list of regions into runs of whole regions of about `limit` test cases: a run ends in front of the region
-// that would take it past the limit (a region larger than the limit is a run of its own).  cut: the boundaries.
-void cut_regions(const mgx_pairhmm_input_t* regions, uint32_t n_regions, uint64_t limit, std::vector<uint32_t>* cut) {
-    cut->assign(1, 0);
-    uint64_t in_run = 0;
+// every region of a whole-region call: valid, in the cross-product form, with an output if it holds test cases (total: of the call)
+static int validate_regions(uint32_t n_regions, const mgx_pairhmm_input_t* regions, double* const* out_log10, uint64_t* total) {
+    *total = 0;
     for (uint32_t g = 0; g < n_regions; ++g) {
+        if (const int rc = validate(&regions[g])) return rc;
+        if (regions[g].pair_read || regions[g].pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
         const uint64_t n = regions[g].n_reads * regions[g].n_haps;
-        if (in_run && in_run + n > limit) { cut->push_back(g); in_run = 0; }
-        in_run += n;
+        if (n && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
+        *total += n;
     }
-    if (n_regions) cut->push_back(n_regions);
+    return 0;
+}
+
+// ---- a stream of batches through lanes: mgx_pairhmm_compute_regions is one lane on the caller's context, the host work
+// queue (below) several, each a host thread with a context of its own
+struct LaneStats {
+    double pack_s = 0, wait_s = 0;
+    uint64_t batches = 0, bytes_h2d = 0, bytes_d2h = 0, cells = 0;
+};
+
+struct QueueRun {
+    const mgx_pairhmm_input_t* in = nullptr;      // pair-stream mode: one long stream, batches are test-case ranges
+    uint64_t lo = 0, hi = 0, n_batches = 0;
+    double* out = nullptr;
+    uint8_t* used = nullptr;
+    // region mode (row F1): many active regions in the cross-product form, batches are runs of whole regions
+    const mgx_pairhmm_input_t* regions = nullptr;
+    double* const* region_out = nullptr;
+    std::vector<uint32_t> chunk;                   // [n_batches + 1] region index boundaries
+    std::atomic<uint64_t> next{0};
+    std::atomic<int> failed{0};
+    std::mutex err_mu;
+    int rc = 0;
+    std::string err;
+    void fail(int code) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (!rc) { rc = code; err = mgx_last_error(); }
+        failed.store(1);
+    }
+    int result() const { if (rc) set_error("%s", err.c_str()); return rc; }      // on the caller's thread, after the lanes have ended
+};
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// One lane on context c: at most `depth` batches in flight, pair-stream batches of batch_pairs test cases.  Per batch:
+// retire the slot's previous batch, create, run; at the end the slots are retired oldest first.
+static void run_lane(mgx_pairhmm* c, uint32_t depth, uint32_t batch_pairs, QueueRun* run, LaneStats* ln) {
+    struct Slot { mgx_pairhmm_batch* b = nullptr; uint64_t lo = 0; uint32_t g0 = 0, g1 = 0; std::vector<uint64_t> base; };
+    std::vector<Slot> slots(depth);
+    mgx::PackPlan plan;
+    if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); run->fail(-EIO); return; }
+    auto retire = [&](Slot& sl) {
+        if (!sl.b) return;
+        const double t0 = now_s();
+        if (!run->failed.load()) {
+            int rc = 0;
+            if (run->regions) {
+                rc = fetch_results(c, sl.b, sl.b->n_pairs * sizeof(double));
+                if (!rc) scatter_region_results(sl.b, sl.base, run->regions, sl.g0, sl.g1, run->region_out, nullptr);
+                ln->bytes_d2h += sl.b->n_pairs * 8;
+            } else {
+                const uint64_t at = sl.lo - run->lo;
+                rc = mgx_pairhmm_batch_results(c, sl.b, run->out + at, run->used ? run->used + at : nullptr);
+                ln->bytes_d2h += sl.b->n_pairs * (run->used ? 9 : 8);
+            }
+            if (rc) run->fail(rc);
+        }
+        mgx_pairhmm_batch_destroy(c, sl.b);
+        sl.b = nullptr;
+        ln->wait_s += now_s() - t0;
+    };
+    size_t turn = 0;
+    while (!run->failed.load()) {
+        const uint64_t k = run->next.fetch_add(1);
+        if (k >= run->n_batches) break;
+        Slot& sl = slots[turn++ % slots.size()];
+        retire(sl);
+        if (run->failed.load()) break;
+        const double t0 = now_s();
+        BatchPtr b = new_batch();
+        int rc = b ? 0 : -ENOMEM;
+        if (!rc && run->regions) {
+            sl.g0 = run->chunk[k]; sl.g1 = run->chunk[k + 1];
+            rc = create_cross(c, sl.g1 - sl.g0, run->regions + sl.g0, b.get(), &sl.base);
+        } else if (!rc) {
+            sl.lo = run->lo + k * batch_pairs;
+            const uint64_t hi = std::min(run->hi, sl.lo + batch_pairs);
+            const uint64_t bad = mgx::pack_plan(run->in, sl.lo, hi, &plan);
+            if (bad) { set_error("test case %llu: index out of range", (unsigned long long)(sl.lo + bad - 1)); run->fail(-EINVAL); break; }
+            rc = create_pairs(c, run->in, &plan, b.get());
+        }
+        ln->pack_s += now_s() - t0;
+        if (!rc && b->n_pairs) rc = mgx_pairhmm_batch_run(c, b.get());
+        if (rc) { run->fail(rc); break; }
+        if (!b->n_pairs) continue;                  // a chunk of empty regions
+        ln->batches++; ln->bytes_h2d += b->lay.in_bytes; ln->cells += b->stats.cells;
+        sl.b = b.release();
+    }
+    for (size_t j = 0; j < slots.size(); ++j) retire(slots[(turn + j) % slots.size()]);    // oldest first
 }
 }  // namespace
 
@@ -1381,12 +981,9 @@ PairhmmView pairhmm_view(mgx_pairhmm_t* c) { return PairhmmView{c->device, c->fl
 
 int regions_begin(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, const uint8_t* const* mapq,
                   const mgx_read_model_t* model, double* const* out_log10, RegionBatch* rb) {
-    if (n_regions == 0) return 0;
     int rc;
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        if ((rc = validate(&regions[g]))) return rc;
-        if (regions[g].n_reads * regions[g].n_haps && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
-    }
+    uint64_t total;
+    if ((rc = validate_regions(n_regions, regions, out_log10, &total)) || total == 0) return rc;
     HIP_TRY(hipSetDevice(c->device));
     BatchPtr b = new_batch();
     if (!b) return -ENOMEM;
@@ -1394,16 +991,16 @@ int regions_begin(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_
     if (b->n_pairs == 0) return 0;
     mgx_pairhmm_batch* raw = b.release();
     if ((rc = mgx_pairhmm_batch_run(c, raw))) { mgx_pairhmm_batch_destroy(c, raw); return rc; }
-    rb->batch = raw; rb->n_pairs = raw->n_pairs; rb->n_reads = raw->n_reads;
-    rb->d_bases = raw->d_bases; rb->d_hap = raw->d_hap; rb->d_keep = raw->d_keep; rb->d_out = raw->d_out;
-    rb->d_row_off = raw->d_row_off; rb->d_row_nh = raw->d_row_nh; rb->done = raw->done;
+    rb->batch = raw; rb->n_pairs = raw->n_pairs; rb->n_reads = raw->lay.model ? (uint32_t)raw->lay.n_reads : 0;
+    rb->d_bases = raw->dev(raw->lay.seq[kSeqBases]); rb->d_hap = raw->dev(raw->lay.seq[kSeqHap]); rb->d_keep = raw->dev(raw->lay.o_keep); rb->d_out = raw->dev<double>(raw->lay.o_out);
+    rb->d_row_off = raw->dev<uint32_t>(raw->lay.roff); rb->d_row_nh = raw->dev<uint32_t>(raw->lay.rnh); rb->done = raw->done;
     return 0;
 }
 
 int regions_queue_download(mgx_pairhmm_t* c, const RegionBatch& rb, hipStream_t s) {
     const mgx_pairhmm_batch* b = rb.batch;
     if (s != c->compute) HIP_TRY(hipStreamWaitEvent(s, b->done, 0));
-    HIP_TRY(hipMemcpyAsync(b->slab.pin + b->o_out, b->d_out, b->result_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->slab.pin + b->lay.o_out, b->dev<double>(b->lay.o_out), b->lay.result_bytes, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -1433,16 +1030,16 @@ int mgx_pairhmm_batch_results(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, double* 
     if (b->n_pairs == 0) return 0;
     if (!out_log10) { set_error("out_log10 is NULL"); return -EINVAL; }
     if (b->slab.pin) {
-        const int rc = fetch_results(c, b, used_f64 ? b->o_used + b->n_pairs - b->o_out : b->n_pairs * sizeof(double));
+        const int rc = fetch_results(c, b, used_f64 ? b->lay.o_used + b->n_pairs - b->lay.o_out : b->n_pairs * sizeof(double));
         if (rc) return rc;
-        memcpy(out_log10, b->slab.pin + b->o_out, b->n_pairs * sizeof(double));
-        if (used_f64) memcpy(used_f64, b->slab.pin + b->o_used, b->n_pairs);
+        memcpy(out_log10, b->slab.pin + b->lay.o_out, b->n_pairs * sizeof(double));
+        if (used_f64) memcpy(used_f64, b->slab.pin + b->lay.o_used, b->n_pairs);
         return 0;
     }
     hipStream_t s = c->d2h;
     if (b->done) HIP_TRY(hipStreamWaitEvent(s, b->done, 0));
-    HIP_TRY(hipMemcpyAsync(out_log10, b->d_out, b->n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (used_f64) HIP_TRY(hipMemcpyAsync(used_f64, b->d_used, b->n_pairs, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_log10, b->dev<double>(b->lay.o_out), b->n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (used_f64) HIP_TRY(hipMemcpyAsync(used_f64, b->dev(b->lay.o_used), b->n_pairs, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -1529,63 +1126,26 @@ int mgx_pairhmm_region(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const ui
 
 int mgx_pairhmm_compute_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, double* const* out_log10) {
     if (!c || (n_regions && (!regions || !out_log10))) { set_error("NULL argument"); return -EINVAL; }
-    if (n_regions == 0) return 0;
-    int rc;
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        if ((rc = validate(&regions[g]))) return rc;
-        if (regions[g].n_reads * regions[g].n_haps && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    // A large call is cut into runs of whole regions of about kChunkPairs (196 608 to 393 216) test cases that go through the context two
-    // at a time: while one chunk computes, the next is flattened and uploaded and the previous one's results are
-    // scattered -- the queue's pipelining (mgx_pairhmm_queue_run_regions) on the caller's thread alone.
-    // (tools/dev_regions_chunk.py, 1000 regions of 40 x 25 on an MI355X: 65 536 test cases per chunk 2 430 GCUPS, 131 072 3 035,
-    // 196 608 3 193, 262 144 2 980-3 190, 524 288 2 610, one chunk 2 090: larger chunks mean larger class launches, fewer of them
-    // mean less of the flattening hidden behind the kernels)
-    // Larger jobs take larger chunks (a sixth of the job, at most 393 216 test cases): 1000 regions of 100 x 50 (5 M test cases)
-    // 3 440 GCUPS with 131 072 per chunk, 3 790 with 196 608, 4 160 with 393 216, 3 960 with 524 288; 200 regions of 300 x 100:
-    // 3 640 / 4 050 / 4 560 / 4 370; 4000 regions of 40 x 25: 3 460 with 196 608, 3 620 with 393 216 (tools/dev_regions_chunk_shapes.py)
-    uint64_t kChunkPairs = 3u << 16;
-    {
-        uint64_t total = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) total += regions[g].n_reads * regions[g].n_haps;
-        kChunkPairs = std::min<uint64_t>(6u << 16, std::max<uint64_t>(kChunkPairs, total / 6));
-    }
-    if (const char* e = getenv("MGX_PAIRHMM_REGION_CHUNK")) { const long long v = atoll(e); if (v > 0) kChunkPairs = (uint64_t)v; }      // A/B
-    std::vector<uint32_t> cut;
-    cut_regions(regions, n_regions, kChunkPairs, &cut);
-    struct InFlight { mgx_pairhmm_batch_t* b = nullptr; uint32_t g0 = 0, g1 = 0; std::vector<uint64_t> base; };
-    InFlight fl[2];
-    auto retire = [&](InFlight& f) -> int {
-        if (!f.b) return 0;
-        const int r = fetch_results(c, f.b, f.b->n_pairs * sizeof(double));
-        if (!r) scatter_region_results(f.b, f.base, regions, f.g0, f.g1, out_log10, nullptr);
-        mgx_pairhmm_batch_destroy(c, f.b);
-        f.b = nullptr;
-        return r;
-    };
-    rc = 0;
-    for (size_t k = 0; k + 1 < cut.size() && !rc; ++k) {
-        InFlight& f = fl[k & 1];
-        rc = retire(f);                                  // the chunk launched two iterations ago
-        if (rc) break;
-        BatchPtr b = new_batch();
-        if (!b) { rc = -ENOMEM; break; }
-        f.g0 = cut[k]; f.g1 = cut[k + 1];
-        if ((rc = create_cross(c, f.g1 - f.g0, regions + f.g0, b.get(), &f.base))) break;
-        if (b->n_pairs == 0) continue;
-        f.b = b.release();
-        rc = mgx_pairhmm_batch_run(c, f.b);
-    }
-    for (int q = 0; q < 2; ++q) { const int r = retire(fl[(cut.size() - 1 + q) & 1]); if (!rc) rc = r; }   // oldest first
-    return rc;
+    uint64_t total;
+    if (const int rc = validate_regions(n_regions, regions, out_log10, &total)) return rc;
+    if (total == 0) return 0;
+    // runs of whole regions of region_chunk_pairs test cases (pairhmm_plan.h), two in flight: the queue's pipelining on the caller's thread
+    uint64_t chunk_pairs = region_chunk_pairs(total);
+    if (const char* e = getenv("MGX_PAIRHMM_REGION_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk_pairs = (uint64_t)v; }      // A/B
+    QueueRun run;
+    run.regions = regions; run.region_out = out_log10;
+    cut_regions(regions, n_regions, chunk_pairs, &run.chunk);
+    run.n_batches = run.chunk.size() - 1;
+    LaneStats st;
+    run_lane(c, 2, 0, &run, &st);
+    return run.result();
 }
 
 // ---------------------------------------------------------------------------------------------
 // Host work queue (BASELINE.json configs[2]).  The reference's worker threads pull the next active
 // region off one atomic index (deepmutect/Mutect2Cpp-master/src/main.cpp:254) and share the tail of the
 // work at the end (main.cpp:302-315, IntelPairHmm.cc:296-330).  Here the unit pulled is a BATCH of test
-// cases: every lane -- a host thread with its own context, i.e. its own streams and recycled pinned
+// cases: every lane (run_lane) -- a host thread with its own context, i.e. its own streams and recycled pinned
 // slabs -- takes the next batch index, plans and packs it (pairhmm_pack.h), uploads, launches and moves on
 // to the next one while the device works; a batch's results are fetched when its slot comes round
 // again, `depth` batches later.  Several lanes per device keep the PCIe link busy (one core packs
@@ -1596,8 +1156,7 @@ struct mgx_pairhmm_queue {
     struct Lane {
         mgx_pairhmm* ctx = nullptr;
         uint32_t dev_slot = 0;
-        double pack_s = 0, wait_s = 0;
-        uint64_t batches = 0, bytes_h2d = 0, bytes_d2h = 0, cells = 0;
+        LaneStats st;
     };
     std::vector<Lane> lanes;
     uint32_t n_devices = 1, depth = 2, batch_pairs = 65536;
@@ -1606,103 +1165,23 @@ struct mgx_pairhmm_queue {
 
 namespace {
 
-struct QueueRun {
-    const mgx_pairhmm_input_t* in = nullptr;      // pair-stream mode: one long stream, batches are test-case ranges
-    uint64_t lo = 0, hi = 0, n_batches = 0;
-    double* out = nullptr;
-    uint8_t* used = nullptr;
-    // region mode (row F1): many active regions in the cross-product form, batches are runs of whole regions
-    const mgx_pairhmm_input_t* regions = nullptr;
-    double* const* region_out = nullptr;
-    std::vector<uint32_t> chunk;                   // [n_batches + 1] region index boundaries
-    std::atomic<uint64_t> next{0};
-    std::atomic<int> failed{0};
-    std::mutex err_mu;
-    int rc = 0;
-    std::string err;
-    void fail(int code) {
-        std::lock_guard<std::mutex> g(err_mu);
-        if (!rc) { rc = code; err = mgx_last_error(); }
-        failed.store(1);
-    }
-};
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-void queue_lane(mgx_pairhmm_queue* q, mgx_pairhmm_queue::Lane* ln, QueueRun* run) {
-    struct Slot { mgx_pairhmm_batch* b = nullptr; uint64_t lo = 0; uint32_t g0 = 0, g1 = 0; std::vector<uint64_t> base; };
-    std::vector<Slot> slots(q->depth);
-    mgx::PackPlan plan;
-    mgx_pairhmm* c = ln->ctx;
-    if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); run->fail(-EIO); return; }
-    auto retire = [&](Slot& sl) {
-        if (!sl.b) return;
-        const double t0 = now_s();
-        if (!run->failed.load()) {
-            int rc = 0;
-            if (run->regions) {
-                rc = fetch_results(c, sl.b, sl.b->n_pairs * sizeof(double));
-                if (!rc) scatter_region_results(sl.b, sl.base, run->regions, sl.g0, sl.g1, run->region_out, nullptr);
-                ln->bytes_d2h += sl.b->n_pairs * 8;
-            } else {
-                const uint64_t at = sl.lo - run->lo;
-                rc = mgx_pairhmm_batch_results(c, sl.b, run->out + at, run->used ? run->used + at : nullptr);
-                ln->bytes_d2h += sl.b->n_pairs * (run->used ? 9 : 8);
-            }
-            if (rc) run->fail(rc);
-        }
-        mgx_pairhmm_batch_destroy(c, sl.b);
-        sl.b = nullptr;
-        ln->wait_s += now_s() - t0;
-    };
-    size_t turn = 0;
-    while (!run->failed.load()) {
-        const uint64_t k = run->next.fetch_add(1);
-        if (k >= run->n_batches) break;
-        Slot& sl = slots[turn++ % slots.size()];
-        retire(sl);
-        if (run->failed.load()) break;
-        const double t0 = now_s();
-        BatchPtr b = new_batch();
-        int rc = b ? 0 : -ENOMEM;
-        if (!rc && run->regions) {
-            sl.g0 = run->chunk[k]; sl.g1 = run->chunk[k + 1];
-            rc = create_cross(c, sl.g1 - sl.g0, run->regions + sl.g0, b.get(), &sl.base);
-        } else if (!rc) {
-            sl.lo = run->lo + k * q->batch_pairs;
-            const uint64_t hi = std::min(run->hi, sl.lo + q->batch_pairs);
-            const uint64_t bad = mgx::pack_plan(run->in, sl.lo, hi, &plan);
-            if (bad) { set_error("test case %llu: index out of range", (unsigned long long)(sl.lo + bad - 1)); run->fail(-EINVAL); break; }
-            rc = create_pairs(c, run->in, &plan, b.get());
-        }
-        ln->pack_s += now_s() - t0;
-        if (!rc && b->n_pairs) rc = mgx_pairhmm_batch_run(c, b.get());
-        if (rc) { run->fail(rc); break; }
-        if (!b->n_pairs) continue;                  // a chunk of empty regions
-        ln->batches++; ln->bytes_h2d += b->in_bytes; ln->cells += b->stats.cells;
-        sl.b = b.release();
-    }
-    for (size_t j = 0; j < slots.size(); ++j) retire(slots[(turn + j) % slots.size()]);    // oldest first
-}
-
 int queue_execute(mgx_pairhmm_queue* q, QueueRun& run, uint64_t n_pairs) {
-    for (auto& ln : q->lanes) { ln.pack_s = ln.wait_s = 0; ln.batches = ln.bytes_h2d = ln.bytes_d2h = ln.cells = 0; }
+    for (auto& ln : q->lanes) ln.st = LaneStats{};
     const double t0 = now_s();
     const size_t n_thr = (size_t)std::min<uint64_t>(q->lanes.size(), run.n_batches);
     std::vector<std::thread> th;
-    for (size_t i = 1; i < n_thr; ++i) th.emplace_back(queue_lane, q, &q->lanes[i], &run);
-    queue_lane(q, &q->lanes[0], &run);               // the caller's thread is lane 0
+    for (size_t i = 1; i < n_thr; ++i) th.emplace_back(run_lane, q->lanes[i].ctx, q->depth, q->batch_pairs, &run, &q->lanes[i].st);
+    run_lane(q->lanes[0].ctx, q->depth, q->batch_pairs, &run, &q->lanes[0].st);               // the caller's thread is lane 0
     for (auto& t : th) t.join();
     q->stats.seconds = now_s() - t0;
     q->stats.n_pairs = n_pairs;
     q->stats.n_batches = run.n_batches;
     for (auto& ln : q->lanes) {
-        q->stats.cells += ln.cells; q->stats.bytes_h2d += ln.bytes_h2d; q->stats.bytes_d2h += ln.bytes_d2h;
-        q->stats.pack_seconds += ln.pack_s; q->stats.wait_seconds += ln.wait_s;
-        q->stats.batches_per_device[ln.dev_slot] += ln.batches;
+        q->stats.cells += ln.st.cells; q->stats.bytes_h2d += ln.st.bytes_h2d; q->stats.bytes_d2h += ln.st.bytes_d2h;
+        q->stats.pack_seconds += ln.st.pack_s; q->stats.wait_seconds += ln.st.wait_s;
+        q->stats.batches_per_device[ln.dev_slot] += ln.st.batches;
     }
-    if (run.rc) { set_error("%s", run.err.c_str()); return run.rc; }
-    return 0;
+    return run.result();
 }
 
 }  // namespace
@@ -1763,15 +1242,8 @@ int mgx_pairhmm_queue_run_regions(mgx_pairhmm_queue_t* q, uint32_t n_regions, co
     q->stats.n_lanes = (uint32_t)q->lanes.size();
     QueueRun run;
     run.regions = regions; run.region_out = out_log10;
-    uint64_t total = 0;
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        int rc = validate(&regions[g]);
-        if (rc) return rc;
-        if (regions[g].pair_read || regions[g].pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
-        const uint64_t n = regions[g].n_reads * regions[g].n_haps;
-        if (n && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
-        total += n;
-    }
+    uint64_t total;
+    if (const int rc = validate_regions(n_regions, regions, out_log10, &total)) return rc;
     cut_regions(regions, n_regions, q->batch_pairs, &run.chunk);      // batches are runs of whole regions holding about batch_pairs test cases
     run.n_batches = run.chunk.size() - 1;
     if (total == 0) return 0;

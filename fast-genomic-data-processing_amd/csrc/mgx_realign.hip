@@ -21,18 +21,12 @@
 #include <vector>
 
 #include "../../include/mgx_realign.h"
-#include "mgx_common.h"
+#include "mgx_hip_util.h"      // HIP_TRY
 #include "mgx_realign_internal.h"
 #include "pairhmm_pack.h"
 
 using mgx::set_error;
 using namespace mgx_internal;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(e_)); return -EIO; } \
-    } while (0)
 
 namespace {
 typedef uint8_t u8; typedef uint32_t u32; typedef uint64_t u64;

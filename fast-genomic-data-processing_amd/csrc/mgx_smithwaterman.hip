@@ -40,17 +40,11 @@
 #include <vector>
 
 #include "../../include/mgx_smithwaterman.h"
-#include "mgx_common.h"
+#include "mgx_hip_util.h"      // HIP_TRY
 #include "mgx_realign_internal.h"
 #include "sw_layout.h"
 
 using mgx::set_error;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(e_)); return -EIO; } \
-    } while (0)
 
 namespace {
 

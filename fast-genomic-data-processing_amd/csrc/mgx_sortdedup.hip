@@ -32,22 +32,12 @@
 #include <vector>
 
 #include "../../include/mgx_sortdedup.h"
-#include "mgx_common.h"
+#include "mgx_hip_util.h"      // HIP_TRY
 #include "sortdedup_stage.h"
 
 using mgx::set_error;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,     \
-                      __LINE__);                                                           \
-            return -EIO;                                                                   \
-        }                                                                                  \
-    } while (0)
 
 using u64 = unsigned long long;   // == uint64_t on this ABI; the type HIP atomics are declared for
 using u32 = uint32_t;

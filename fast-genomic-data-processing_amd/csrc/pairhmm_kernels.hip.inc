@@ -38,18 +38,11 @@
 #include <type_traits>
 
 #include "best_allele_rule.h"
+#include "pairhmm_plan.h"      // Job, SeqRef, RegionRef, kMaxCodes, kMultiBins: what the host writes and these kernels read
 
 namespace {
 
-struct Job {
-    uint64_t read_off;
-    uint64_t hap_off;
-    uint32_t R;
-    uint32_t H;
-    uint32_t pair;
-    uint32_t pad_;
-};
-static_assert(sizeof(Job) == 32, "Job is 32 bytes");
+using namespace mgx_hmm_plan;
 
 struct KernelArgs {
     const Job* jobs;            // jobs of the batch
@@ -164,7 +157,6 @@ template <> struct Prec<double> {
 // the class's N-haplotype list, which the five-column fp32 instantiation of the same class then works through (per
 // test case, never per wavefront: a value does not depend on the batch it is in, nor on which launch computed it --
 // both read the same table entries for A C T G).  fp64 has no table; its CODES stays 5.
-constexpr int kMaxCodes = 5;
 template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return ((RPL + 1) / 2) * CODES * 64 * 8; }
 
 // The recurrence for the jobs of ONE class (G, RPL); `block` / `n_blocks` are the workgroup's index and count among
@@ -626,7 +618,6 @@ __global__ __launch_bounds__(64) void pairhmm_fwd_exact(KernelArgs a) {
 // them -- most rows per lane first, inside a class longest haplotype first -- so the single drain is made of the
 // cheapest jobs.  GSET 0: the 16-lane classes with 1..8 rows per lane; GSET 1: the 8- and 4-lane classes (their
 // 8 / 16 haplotypes per wavefront need more LDS, which would cost the 16-lane classes occupancy in a common launch).
-constexpr int kMultiBins = 16;
 struct MultiArgs {
     KernelArgs a;                              // job_first, n_static and lds_stride are filled in per class
     uint32_t n_bins;
@@ -670,21 +661,6 @@ __global__ __launch_bounds__(256) void pairhmm_fwd_multi(MultiArgs m) {
 // Cross-product batches (every read against every haplotype of a region, the shape
 // VectorLoglessPairHMM builds): job descriptors are generated on the device from two small tables
 // instead of being written one by one on the host.
-struct SeqRef {
-    uint64_t off;
-    uint32_t len;
-    uint32_t id;
-};
-
-// One or several active regions (row F1, SURVEY.md 8f) in ONE batch.  Every read is paired with the
-// haplotypes of its own region; job q belongs to the read whose prefix range holds q, so neighbouring jobs
-// are the same read against haplotypes of similar length.
-struct RegionRef {
-    uint32_t hap_begin;    // first entry of the region's (length-sorted) haplotypes in the hap table
-    uint32_t n_haps;
-    uint32_t read_base;    // global index of the region's first read
-    uint32_t out_base;     // where the region's [reads][haps] block starts in the output
-};
 __global__ __launch_bounds__(256) void pairhmm_make_jobs_multi(const SeqRef* __restrict__ reads, const uint32_t* __restrict__ read_region,
                                                                const uint32_t* __restrict__ job_prefix, uint32_t n_reads,
                                                                const RegionRef* __restrict__ regions, const SeqRef* __restrict__ haps,

@@ -357,3 +357,48 @@ def test_row_classes_region_and_gcp_0_match_the_oracle_with_packed_flag_ignored(
     a.run(); av, au = a.results(with_flags=True); a.close()
     assert np.array_equal(av, bv) and np.array_equal(au, bu)
     eng.close(); packed.close()
+
+
+def concat_pair_batches(a, b):
+    """two batches of independent test cases (synth.gen_pairhmm_pairs) as one"""
+    d = {k: np.concatenate([a[k], b[k]]) for k in ("bases", "qual", "ins", "dele", "gcp", "hap_bases")}
+    d["read_off"] = np.concatenate([a["read_off"], b["read_off"][1:] + a["read_off"][-1]])
+    d["hap_off"] = np.concatenate([a["hap_off"], b["hap_off"][1:] + a["hap_off"][-1]])
+    n = a["n_pairs"] + b["n_pairs"]
+    d["pair_read"] = d["pair_hap"] = np.arange(n, dtype=np.uint32)
+    d["cells"], d["alg_bytes"] = a["cells"] + b["cells"], a["alg_bytes"] + b["alg_bytes"]
+    return d
+
+
+@pytest.mark.parametrize("n_small,launches", [(4095, 1), (4096, 2)])
+def test_small_class_merge_threshold(pkg, oracle, synth, n_small, launches):
+    """A class of fewer than 4096 test cases is folded into the next class of its lane width, one of 4096 keeps its launch: reads of
+    9-12 bases (4 lanes x 3 rows) next to 5000 test cases of 13-16 bases (4 lanes x 4 rows)."""
+    d = concat_pair_batches(synth.gen_pairhmm_pairs(n_small, 0x5EED0410, r_range=(9, 12), h_range=(20, 40)),
+                            synth.gen_pairhmm_pairs(5000, 0x5EED0411, r_range=(13, 16), h_range=(20, 40)))
+    eng = pkg.PairHMMEngine(0, flags=pkg.pairhmm.TIMING)
+    out, used, st = run(eng, d)
+    eng.close()
+    want, wused = oracle.batch(d)
+    assert_log10_close(out, want)
+    assert (used != wused).sum() <= max(2, len(out) // 2000)
+    assert st["cells"] == d["cells"] and st["alg_bytes"] == d["alg_bytes"] and st["n_rerun_f64"] == int(used.sum())
+    assert st["n_launches_f32"] == launches
+
+
+@pytest.mark.parametrize("chunk", [50, 1])
+def test_compute_regions_chunk_seams(engine, synth, monkeypatch, chunk):
+    """mgx_pairhmm_compute_regions cut into chunks of 50 test cases and of one: twelve regions of at most 8 reads x 5 haplotypes, one of
+    them empty, and a thirteenth of 12 x 5 that alone exceeds the chunk of 50.  Every region's block is, bit for bit, what a compute of
+    its explicit pair list returns."""
+    shapes = [(8, 5), (3, 2), (1, 1), (8, 4), (5, 5), (2, 3), (12, 5), (7, 5), (1, 5), (8, 1), (4, 4), (6, 2)]
+    regs = [synth.gen_pairhmm_region(nr, nh, 700 + k, r_range=(10, 140), h_range=(30, 200)) for k, (nr, nh) in enumerate(shapes)]
+    empty = dict(regs[0]); empty["read_off"] = np.zeros(1, dtype=np.uint64)
+    regs.insert(4, empty)
+    monkeypatch.setenv("MGX_PAIRHMM_REGION_CHUNK", str(chunk))
+    got = engine.compute_regions(regs)
+    monkeypatch.delenv("MGX_PAIRHMM_REGION_CHUNK")
+    assert got[4].shape == (0, 5)
+    for k, (d, o) in enumerate(zip(regs, got)):
+        if k != 4:
+            assert np.array_equal(o, engine.compute(d).reshape(o.shape)), k
