@@ -55,8 +55,12 @@ struct SwDeviceSource {
     int (*gather)(void* user, hipStream_t s, uint64_t lo, uint64_t hi, uint8_t* d_ref, uint8_t* d_alt);
     void* user;
 };
+// The aligner's CIGAR of every pair in binary beside its text: pair p's elements, BAM-encoded (length << 4 | M I D S = 0 1 2 4) and
+// in text order, are el[off[p] .. off[p] + n[p]); exactly the elements the text holds (one the text has no room for is absent here
+// too; without a text buffer the capacity is the reference's 2 * max(lengths)).  nullptr: the aligner behaves as without it.
+struct SwElementSink { std::vector<uint64_t> off; std::vector<uint32_t> n, el; };
 int sw_align_from_device(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const SwDeviceSource& src,
-                         int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score);
+                         int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score, SwElementSink* sink = nullptr);
 struct SwView { int device; int max_ref, max_alt; };
 SwView sw_view(mgx_sw_t* c);
 

@@ -618,13 +618,17 @@ constexpr int kCompactElems = 16;             // merged CIGAR elements copied ba
 int itoa_len(int v) { const int neg = v < 0; if (neg) v = -v; int d = 0; while (v > 0) { v /= 10; ++d; } return d + neg; }
 
 // PairWiseSW.h:410-444: last element first; an element whose text does not fit is skipped
-int render(const int16_t* el, int n_elems, char* out, int cap) {
+// bam != nullptr: the elements that went into the text also as length << 4 | BAM operator (9 where the text says R), *n_bam of them;
+// out == nullptr: no text, the elements alone
+int render(const int16_t* el, int n_elems, char* out, int cap, u32* bam = nullptr, u32* n_bam = nullptr) {
     int cur = 0;
     for (int k = n_elems - 1; k >= 0; --k) {
         const int op = el[2 * k], len = el[2 * k + 1];
         const char c = op == kOpMatch ? 'M' : op == kOpInsert ? 'I' : op == kOpDelete ? 'D' : op == MGX_SW_SOFTCLIP ? 'S' : 'R';
         const int need = itoa_len(len) + 1;
         if (need > 1 && cur + need <= cap) {
+            if (bam && len > 0) bam[(*n_bam)++] = (u32)len << 4 | (c == 'M' ? 0u : c == 'I' ? 1u : c == 'D' ? 2u : c == 'S' ? 4u : 9u);
+            if (!out) { cur += need; continue; }
             int v = len;
             if (v < 0) { out[cur++] = '-'; v = -v; }
             const int d = itoa_len(v);
@@ -695,7 +699,7 @@ struct Chunk {
     Chunk(const mgx_sw_input_t* in, u64 lo_, u64 hi_) : lo(lo_), hi(hi_), n((u32)(hi_ - lo_)), base1(in->ref_off[lo_]), base2(in->alt_off[lo_]),
         n1(in->ref_off[hi_] - base1), n2(in->alt_off[hi_] - base2), a1((n1 + 255) & ~(size_t)255), a2((n2 + 255) & ~(size_t)255) {}
 };
-struct Outputs { int32_t* offset; char* cigar; u32 stride; int32_t* score; int cap_override; };      // the caller's, indexed by input pair
+struct Outputs { int32_t* offset; char* cigar; u32 stride; int32_t* score; int cap_override; mgx_internal::SwElementSink* sink; };      // the caller's, indexed by input pair
 Lens pair_lens(const mgx_sw_input_t* in, u64 p) { return mgx_sw_layout::pair_lens(in->ref_off, in->alt_off, p); }
 using mgx_internal::SwDeviceSource;
 struct Stager {                   // the helper threads of stage_sequences: upload_jobs joins them, and so does every way out before it
@@ -846,6 +850,10 @@ int fetch_results(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, u64 bt_by
 }
 // results and CIGAR text, a few threads when the batch is large (rendering long element lists is the library's biggest host cost)
 void emit_text(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, const Fetched& f, const Outputs& out) {
+    if (out.sink) {             // room for every element of the chunk; chunks come in pair order
+        for (u32 q = 0; q < k.n; ++q) out.sink->off[k.lo + q + 1] = out.sink->off[k.lo + q] + (u64)std::max(f.res[q].n_elems, 0);
+        out.sink->el.resize(out.sink->off[k.lo + k.n]);
+    }
     auto emit = [&](u32 q0, u32 q1, u64* cells_out) {
         u64 cells = 0;
         for (u32 q = q0; q < q1; ++q) {
@@ -854,13 +862,13 @@ void emit_text(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, const Fetche
             const SwResult& r = f.res[q];
             out.offset[p] = r.offset;
             if (out.score) out.score[p] = r.score;
-            if (out.cigar) {
-                char* dst = out.cigar + (size_t)p * out.stride;
+            if (out.cigar || out.sink) {
+                char* dst = out.cigar ? out.cigar + (size_t)p * out.stride : nullptr;
                 const int cap = out.cap_override >= 0 ? out.cap_override
-                                                      : (int)std::min<u64>(2ull * std::max(l.l1, l.l2), (u64)out.stride - 1);   // IntelSmithWaterman.cpp:8
+                                                      : (int)std::min<u64>(2ull * std::max(l.l1, l.l2), out.cigar ? (u64)out.stride - 1 : ~0ull);   // IntelSmithWaterman.cpp:8
                 const int16_t* src = r.n_elems > kCompactElems ? f.big.get() + f.big_at[q] : f.cel + (size_t)q * 2 * kCompactElems;
-                const int len = render(src, r.n_elems, dst, cap);
-                dst[len] = 0;                             // cap <= stride - 1
+                const int len = render(src, r.n_elems, dst, cap, out.sink ? out.sink->el.data() + out.sink->off[p] : nullptr, out.sink ? &out.sink->n[p] : nullptr);
+                if (dst) dst[len] = 0;                    // cap <= stride - 1
             }
             cells += l.l1 * l.l2;
         }
@@ -938,11 +946,12 @@ void mgx_sw_destroy(mgx_sw_t* c) {
 
 static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in,
                       int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score, int cap_override,
-                      const SwDeviceSource* src = nullptr) {
+                      const SwDeviceSource* src = nullptr, mgx_internal::SwElementSink* sink = nullptr) {
     if (!c || !params || !in || !out_offset) { set_error("NULL argument"); return -EINVAL; }
     if (out_cigar && cigar_stride < 2) { set_error("cigar_stride must be at least 2"); return -EINVAL; }
     c->stats = mgx_sw_stats_t{};
     c->stats.n_pairs = in->n_pairs;
+    if (sink) { sink->off.assign(in->n_pairs + 1, 0); sink->n.assign(in->n_pairs, 0); sink->el.clear(); }
     if (in->n_pairs == 0) return 0;
     if (!in->ref_off || !in->alt_off || (!src && (!in->ref || !in->alt)) || !in->strategy) { set_error("NULL array in input"); return -EINVAL; }
     if (in->n_pairs > 0x7FFFFFFFull) { set_error("more than 2^31-1 pairs in one batch"); return -E2BIG; }
@@ -959,7 +968,7 @@ static int align_impl(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_i
     HIP_TRY(hipSetDevice(c->device));
     const Knobs knobs;
     const u64 limit = knobs.arena ? knobs.arena : kArenaLimit;
-    const Outputs out{out_offset, out_cigar, cigar_stride, out_score, cap_override};
+    const Outputs out{out_offset, out_cigar, cigar_stride, out_score, cap_override, sink};
     for (u64 lo = 0, hi; lo < in->n_pairs; lo = hi) {
         hi = chunk_end(in->ref_off, in->alt_off, in->n_pairs, lo, limit);      // by chunk_bound per pair (sw_layout.h)
         const int rc = run_chunk(c, params, in, Chunk(in, lo, hi), knobs, out, src);
@@ -998,9 +1007,9 @@ int mgx_sw_stats(mgx_sw_t* c, mgx_sw_stats_t* out) {
 
 namespace mgx_internal {
 int sw_align_from_device(mgx_sw_t* c, const mgx_sw_params_t* params, const mgx_sw_input_t* in, const SwDeviceSource& src,
-                         int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score) {
+                         int32_t* out_offset, char* out_cigar, uint32_t cigar_stride, int32_t* out_score, SwElementSink* sink) {
     if (!src.gather) { set_error("NULL argument"); return -EINVAL; }
-    return align_impl(c, params, in, out_offset, out_cigar, cigar_stride, out_score, -1, &src);
+    return align_impl(c, params, in, out_offset, out_cigar, cigar_stride, out_score, -1, &src, sink);
 }
 SwView sw_view(mgx_sw_t* c) { return SwView{c->device, (c->flags & MGX_SW_LONG_REF) ? kMaxLen : kMaxRef, kMaxLen}; }
 }  // namespace mgx_internal

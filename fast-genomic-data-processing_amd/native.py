@@ -217,7 +217,32 @@ class RealignStats(C.Structure):
                 ("ms_best", C.c_float), ("ms_verbatim", C.c_float), ("ms_gather", C.c_float)]
 
 
+TO_REF_OK, TO_REF_DROPPED, TO_REF_UNCHANGED, TO_REF_THROWS, TO_REF_UNDEFINED, TO_REF_NO_ROOM = range(6)
+
+
+class ToRefInput(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("read_off", C.c_void_p), ("read_bases", C.c_void_p), ("sw_offset", C.c_void_p),
+                ("sw_cigar_off", C.c_void_p), ("sw_cigar", C.c_void_p), ("read_hap", C.c_void_p), ("n_haps", C.c_uint64),
+                ("hap_cigar_off", C.c_void_p), ("hap_cigar", C.c_void_p), ("hap_start", C.c_void_p), ("read_ref", C.c_void_p),
+                ("n_refs", C.c_uint64), ("ref_off", C.c_void_p), ("ref_bases", C.c_void_p), ("reference_start", C.c_void_p),
+                ("hard_clips", C.c_void_p)]
+
+
+class ToRefRegion(C.Structure):
+    _fields_ = [("hap_cigar_off", C.c_void_p), ("hap_cigar", C.c_void_p), ("hap_start", C.c_void_p), ("ref_hap", C.c_uint32),
+                ("reference_start", C.c_int32), ("hard_clips", C.c_void_p)]
+
+
+class RealignToRefStats(C.Structure):
+    _fields_ = [("n_status", C.c_uint64 * 6), ("ms_to_ref", C.c_float)]
+
+
 REALIGN_SYMBOLS = {
+    "mgx_read_to_ref": (C.c_int, [C.c_void_p, C.POINTER(ToRefInput), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mgx_realign_regions_to_ref": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwParams),
+                                             C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mgx_realign_to_ref_stats": (C.c_int, [C.c_void_p, C.POINTER(RealignToRefStats)]),
     "mgx_pairhmm_best_alleles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_realign_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwParams),
                                       C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -3,7 +3,12 @@ lastIndexOf, host assembly, mgx_sw_align_batch): builds tools/realign_ab.cpp aga
 regions of 40 x 25) and a large-region leg (200 regions of 300 x 100, reads 100-151 against haplotypes 250-400), each with about 90 %
 and about 0 % of the reads verbatim, and writes what the program printed.  Needs an MI355X.
 
-    python tools/dev_realign.py [--out profiles/realign_ab.txt] [--rounds 6] [--build-only]
+With --to-ref the same four workloads, their haplotypes carrying CIGARs with zero to two indels, measure mgx_realign_regions_to_ref
+against mgx_realign_regions followed by the rule's own serial host pass (csrc/read_to_ref_rule.h, single thread) over the kept reads.
+With --parent LIB (a library of the parent commit, tools/build_ab_lib.sh HEAD parent) the existing calls of the two libraries, loaded
+side by side, take turns on the region leg and on 20 000 Smith-Waterman pairs; their outputs are compared byte for byte.
+
+    python tools/dev_realign.py [--out profiles/realign_ab.txt] [--rounds 6] [--build-only] [--to-ref] [--parent tools/ab/libmgx_parent.so]
 """
 import argparse
 import os
@@ -23,29 +28,91 @@ def build():
     src = os.path.join(ROOT, "tools", "realign_ab.cpp")
     if os.path.exists(EXE) and os.path.getmtime(EXE) >= max(os.path.getmtime(src), os.path.getmtime(os.path.join(PKGDIR, "libmgx.so"))):
         return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-L", PKGDIR, "-lmgx",
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKGDIR, "csrc"), src, "-L", PKGDIR, "-lmgx",
                            "-Wl,-rpath," + PKGDIR, "-o", EXE])
+
+
+def existing_calls(parent, rounds):
+    """mgx_realign_regions on the region leg and mgx_sw_align_batch on 20 000 pairs: the parent's library and this tree's, side by
+    side in one process, taking turns; medians and max - min of the rounds, outputs compared byte for byte"""
+    import ctypes as C
+    import importlib
+    import time
+
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    pkg = importlib.import_module("fast-genomic-data-processing_amd")
+    native, synth = pkg.native, pkg.synth
+
+    def engines(path):
+        if path is None:
+            lib = native.load()
+        else:
+            lib = C.CDLL(path)
+            for name, (res, args) in native.SYMBOLS.items():
+                if hasattr(lib, name):                    # the parent lacks what this tree adds
+                    fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
+        mine = native.load()
+        native._LIB = lib                                 # the engines fetch their library through native.load()
+        try:
+            hmm, sw = pkg.PairHMMEngine(0), pkg.SmithWatermanEngine(0)
+            return hmm, sw, pkg.RealignEngine(hmm, sw)
+        finally:
+            native._LIB = mine
+    sides = {"parent": engines(parent), "new": engines(None)}
+    regions = [synth.gen_pairhmm_region(40, 25, 0x5EED0100 + g, r_range=(20, 128), h_range=(64, 256)) for g in range(1000)]
+    mapqs = [np.full(40, 60, dtype=np.uint8)] * 1000
+    w = synth.gen_sw_pairs(20000, 9, ref_range=(30, 300), alt_range=(10, 150))
+    jobs = {"realign_regions 1000 x 40 x 25": lambda e: e[2].regions(regions, mapqs),
+            "sw_align_batch 20 000 pairs": lambda e: e[1].align_batch(w["ref_off"], w["ref"], w["alt_off"], w["alt"], w["strategy"], want_score=True)}
+
+    def flat(o):
+        if isinstance(o, dict):
+            return [(k, flat(v)) for k, v in sorted(o.items())]
+        if isinstance(o, (list, tuple)):
+            return [flat(x) for x in o]
+        return np.asarray(o).tobytes() if isinstance(o, np.ndarray) else o
+    lines = []
+    for name, job in jobs.items():
+        outs = {k: flat(job(e)) for k, e in sides.items()}          # the warm-up, and the outputs
+        times = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, e in sides.items():
+                t0 = time.perf_counter(); job(e); times[k].append((time.perf_counter() - t0) * 1e3)
+        lines.append(f"{name:32s} identical: {outs['parent'] == outs['new']}; " + "; ".join(
+            f"{k} {np.median(t):.3f} ms (spread {max(t) - min(t):.3f})" for k, t in times.items()))
+        print(lines[-1], flush=True)
+    return lines
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "realign_ab.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--build-only", action="store_true")
+    ap.add_argument("--to-ref", action="store_true")
+    ap.add_argument("--parent", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "realign_to_ref_ab.txt" if a.to_ref else "realign_ab.txt")
     build()
     if a.build_only:
         return 0
-    text = ["mgx_realign_regions (fused) against the composition of mgx_pairhmm_regions, host searchBestAllele + lastIndexOf, host assembly and",
+    text = ["mgx_realign_regions_to_ref (fused) against mgx_realign_regions followed by the serial host pass of csrc/read_to_ref_rule.h over the",
+            f"kept reads (composed): one process per workload, the two take turns, one warm-up each, {a.rounds} rounds; wall time per call.", ""] if a.to_ref else ["mgx_realign_regions (fused) against the composition of mgx_pairhmm_regions, host searchBestAllele + lastIndexOf, host assembly and",
             f"mgx_sw_align_batch (composed): one process per workload, the two take turns, one warm-up each, {a.rounds} rounds; wall time per call.", ""]
+    mode = ["to_ref"] if a.to_ref else []
     for name, shape in LEGS:
         for share in SHARES:
-            res = subprocess.run([EXE] + [str(x) for x in shape] + [str(share), str(a.rounds)], capture_output=True, text=True, timeout=900)
+            res = subprocess.run([EXE] + [str(x) for x in shape] + [str(share), str(a.rounds)] + mode, capture_output=True, text=True, timeout=900)
             if res.returncode != 0:
                 sys.stderr.write(res.stdout + res.stderr)
                 return res.returncode
             text += [f"== {name}, {share} % verbatim asked", res.stdout.rstrip(), ""]
             print(text[-3] + "\n" + text[-2], flush=True)
+    if a.parent:
+        text += ["== the existing calls, the parent commit's libmgx.so (tools/build_ab_lib.sh HEAD parent) against this tree's, loaded side by side in one",
+                 f"== process and taking turns, one warm-up each, {a.rounds} rounds, medians and max - min; outputs compared byte for byte"]
+        text += existing_calls(a.parent, a.rounds) + [""]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(text))

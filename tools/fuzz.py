@@ -1,5 +1,5 @@
 """Randomised soak: loops over seeded random inputs for the paths and compares the device with the oracles
-(bit-exact for sort/dedup and Smith-Waterman, 1e-5 for PairHMM, zlib's inflate for the BGZF blocks).  usage: fuzz.py [seconds] [seed0] [kind 0..6: that path only; 3 = Smith-Waterman, one batch in four on a MGX_SW_LONG_REF context with references of up to 6 000 bases]"""
+(bit-exact for sort/dedup and Smith-Waterman, 1e-5 for PairHMM, zlib's inflate for the BGZF blocks).  usage: fuzz.py [seconds] [seed0] [kind 0..7: that path only; 7 = read -> reference against the sequential restatement of tests/read_to_ref_cases.py; 3 = Smith-Waterman, one batch in four on a MGX_SW_LONG_REF context with references of up to 6 000 bases]"""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,21 +8,23 @@ pkg = importlib.import_module("fast-genomic-data-processing_amd")
 synth = pkg.synth
 from conftest import PairHMMOracle, SortDedupOracle, SmithWatermanOracle, _ensure_oracle
 from test_pairhmm_gpu import flush_regime_pairs
+import read_to_ref_cases as RTR
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1
 ph, sd, sw = pkg.PairHMMEngine(0), pkg.SortDedupEngine(0), pkg.SmithWatermanEngine(0)
 sw_long = pkg.SmithWatermanEngine(0, pkg.smithwaterman.LONG_REF)
+realign = pkg.RealignEngine(ph, sw)
 oph, osd, osw = PairHMMOracle(_ensure_oracle()), SortDedupOracle(), SmithWatermanOracle()
 rng = np.random.default_rng(seed0)
-t0 = time.time(); it = 0; fails = 0; counts = {"sort": 0, "pairhmm": 0, "regions": 0, "sw": 0, "shards": 0, "queue": 0, "bgzf": 0}
+t0 = time.time(); it = 0; fails = 0; counts = {"sort": 0, "pairhmm": 0, "regions": 0, "sw": 0, "shards": 0, "queue": 0, "bgzf": 0, "to_ref": 0}
 import zlib
 bz = pkg.BgzfCompressor(0)
 bam_bytes = synth.gen_bam_record_bytes(6_000_000, 99, qual_bins=(2, 11, 25, 37))
 queue = pkg.PairHMMQueue(devices=(0, 0), lanes_per_device=2, depth=2, batch_pairs=700)
 while time.time() - t0 < budget:
     seed = int(rng.integers(1, 2**31 - 1)); it += 1
-    kind = only if only >= 0 else it % 7
+    kind = only if only >= 0 else it % 8
     try:
         if kind == 0:
             kw = dict(n_contigs=int(rng.integers(1, 6)), contig_len=int(rng.choice([5000, 60000, 400000, 3000000])),
@@ -103,6 +105,19 @@ while time.time() - t0 < budget:
                 ok &= dz.decompress(blk[18:-8]) + dz.flush() == want and dz.eof
                 ok &= int.from_bytes(blk[-8:-4], "little") == zlib.crc32(want) and int.from_bytes(blk[-4:], "little") == len(want)
             counts["bgzf"] += 1
+        elif kind == 7:
+            # read -> reference: the CPU test's generators on a fresh seed, every row capacity from 1 to ample, against the restatement
+            cl = RTR.cases(seed, int(rng.integers(13, 600)))
+            stride = int(rng.choice([1, 2, 3, 5, 24]))
+            n = len(cl)
+            st, start, cig, ncig = realign.to_ref([c["read"] for c in cl], [c["offset"] for c in cl], [RTR.encode(c["sw"]) for c in cl], np.arange(n),
+                                                  [RTR.encode(c["hap"]) for c in cl], [c["hap_start"] for c in cl], np.arange(n), [c["ref"] for c in cl],
+                                                  [c["reference_start"] for c in cl], hard_clips=[c["hard"] for c in cl], stride=stride)
+            ok = True
+            for r, c in enumerate(cl):
+                ws, wstart, wel = RTR.to_ref(dict(c, stride=stride))
+                ok &= bool(st[r] == ws and (ws != RTR.OK or (start[r] == wstart and list(cig[r]) == list(wel))) and (ws != RTR.NO_ROOM or ncig[r] == len(wel)))
+            counts["to_ref"] += 1
         elif kind == 5:
             # the host work queue: a stream cut into small batches over two lanes x two "devices" equals one call
             if it % 12 == 5:
