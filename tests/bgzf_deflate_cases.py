@@ -8,7 +8,8 @@ import zlib
 import numpy as np
 
 MAX_IN = 0xff00
-# the kernel's geometry (mgx_bgzf.hip): 64-position chunks, match windows of kWin positions, groups of kGrp windows
+# the kernel's geometry (mgx_bgzf.hip): 64-position chunks, match windows of kWin = 896 positions (14 wavefronts), groups of kGrp = 4
+# windows = 3584 positions = 56 chunks (kGrpPos, kGrpChunks); the longest match and the farthest distance are deflate_rules.h's
 K_CHUNK, K_WIN, K_GRP_POS, K_MAX_MATCH, K_MAX_DIST = 64, 896, 4 * 896, 258, 32768
 # the knob values under which the cost rule drops every match of at most 16 bytes (its literal price is at most
 # 255 * len <= 4080 = 16 * 255), so that data without a repeated 17-byte substring comes out as literals only
