@@ -4,6 +4,8 @@
 // bgzf_flush2, hts_close2, merge_index, hts_idx_finish3 -- functions that exist nowhere in the
 // reference tree): per-thread compression of contiguous slices of the sorted records into
 // independent BGZF blocks, concatenation, and a BAI index built from the records' virtual offsets.
+// write_bam is in bam_writer.cpp (host only; with zlib it needs no libmgx.so), write_bam_store and the device's part in
+// write_bam(device >= 0) in bam_writer_device.cpp; bam_writer_parts.h is what the two share.
 #pragma once
 
 #include <atomic>

@@ -217,3 +217,23 @@ def test_corrupt_block_size_deep_in_a_multi_batch_input_exits(tmp_path, syntheti
             res = run(["-b", "-I", inp, "-O", str(tmp_path / "x.bam"), "-t", str(threads), "-s", "20000"], env=dict(env, MGX_CLI_INFLATE_BATCH=str(256 << 10)), timeout=120)
             assert res.returncode == 1, (bs, res.returncode, res.stderr[-2000:])
             assert f"offset {o} " in res.stderr and "corrupt" in res.stderr, (bs, res.stderr[-2000:])
+
+
+def test_records_longer_than_a_block_through_every_output_mode(tmp_path):
+    """Records just over one BGZF block, of about two and of more than two (a Z tag of 65 300, 131 000 and 140 000 bytes) among
+    short ones: each output mode cuts them across blocks in its own way (SAMv1 4.1), holds the same stream and indexes it."""
+    recs = [bm.rec(f"q{i:02d}", tid=i % 2, pos=500 + 37 * i, cigar=bm.C("30M")) for i in range(60)]
+    for k, n in ((7, 65300), (30, 131000), (52, 140000)):
+        recs[k]["aux"] = [["XL", "Z", "L" * n]]
+    data, first, _ = bm.encode_bam("@HD\tVN:1.6\n", bm.EDGE_REFS, recs)
+    inp = write(tmp_path / "long.bam", bc.bgzf(data, size=65280, level=1))
+    want = sorted(bm.encode_record(r) for r in recs)             # (no flag has 0x400, and no record here is another's duplicate)
+    assert sum(len(x) > 0xff00 for x in want) == 3 and sum(len(x) > 2 * 0xff00 for x in want) == 2
+    streams = {}
+    for mode in ("device", "pinned", "zlib"):
+        bam, bai, _ = outputs(tmp_path, inp, mode, ["-b"], tag=mode)
+        streams[mode] = gzip.decompress(bam)
+        assert records_without_dup(streams[mode]) == want, mode
+        assert all(isize <= 0xff00 for _, _, isize in sam_spec.bgzf_blocks(bam)), mode
+        assert sam_spec.check_index(bam, bai) == len(recs), mode
+    assert streams["device"] == streams["pinned"] == streams["zlib"] and streams["zlib"][:first] == data[:first]

@@ -14,7 +14,7 @@ from conftest import ROOT
 PKGDIR = os.path.join(ROOT, "fast-genomic-data-processing_amd")
 EXE = os.path.join(PKGDIR, "bin", "sortmardup")
 CLI_SRC = [os.path.join(PKGDIR, "csrc", "cli", f) for f in ("sortmardup_main.cpp", "ingest.cpp", "slice_cut.cpp", "gz_source.cpp", "sam_text.cpp",
-                                                            "bam_writer.cpp")]
+                                                            "bam_writer.cpp", "bam_writer_device.cpp", "bai_index.cpp")]
 
 
 def build_cli():
