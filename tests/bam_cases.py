@@ -1,6 +1,7 @@
 """Test data for BAM input (tests/test_bam_host.py, test_bam_gpu.py, test_cli_bam_gpu.py): a spec-based BAM encoder over the
 record dicts of sam_spec.parse_sam_line (SAMv1 4.2), the synthetic record set the compressed-SAM tests use, an edge list
-for the key rules, seam and decoy inputs for the device index, and mutations for the sanitizer run.  Test infrastructure
+for the key rules, seam and decoy inputs for the device index (dependent_decoys: misses that need several repair rounds,
+with the index's guess rule restated to assert the layout), and mutations for the sanitizer run.  Test infrastructure
 only."""
 import struct
 
@@ -183,6 +184,126 @@ def decoy_bam(pad, in_b_tag=False):
             r["aux"] = [["XD", "Z", payload]]
         recs.append(r)
     return refs, recs
+
+
+MAX_RECORD = 1 << 28                                             # MGX_BAM_MAX_RECORD
+
+
+def _fixed_ok(data, c, n_ref):
+    """check_fixed and, with n_ref given, plausible (bam_record_core.h) of the 36 bytes at c -> (block_size, l_read_name) or None"""
+    bs, tid, pos = struct.unpack_from("<iii", data, c)
+    l_name = data[c + 12]
+    n_cigar = struct.unpack_from("<H", data, c + 16)[0]
+    l_seq, ntid, npos = struct.unpack_from("<iii", data, c + 20)
+    if not 32 <= bs <= MAX_RECORD or l_name < 1 or l_seq < 0 or 32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq > bs:
+        return None
+    if n_ref is not None and not (-1 <= tid < n_ref and -1 <= ntid < n_ref and pos >= -1 and npos >= -1):
+        return None
+    return bs, l_name
+
+
+def guess_hit(data, n, c, n_ref):
+    """The index kernel's guess rule for a record start at c, restated: check_fixed, plausible, the record inside the
+    data, the name's NUL, and follower_ok of what comes behind it."""
+    if c + 36 > n:
+        return False
+    f = _fixed_ok(data, c, n_ref)
+    if f is None or f[0] > n - c - 4 or data[c + 36 + f[1] - 1] != 0:
+        return False
+    at = c + 4 + f[0]
+    if n - at < 4:
+        return True
+    if not 32 <= struct.unpack_from("<i", data, at)[0] <= MAX_RECORD:
+        return False
+    return n - at < 36 or _fixed_ok(data, at, n_ref) is not None
+
+
+def first_hits(data, first, n_ref, tile, n_tiles):
+    """What each of the first n_tiles tiles is walked from: None before `first`, `first` in its own tile, else the lowest
+    offset of the tile that passes the guess rule (None: no guess)."""
+    n, out = len(data), []
+    for t in range(n_tiles):
+        base = t * tile
+        if base + tile <= first:
+            out.append(None)
+        elif first >= base:
+            out.append(first)
+        else:
+            out.append(next((c for c in range(base, base + tile) if guess_hit(data, n, c, n_ref)), None))
+    return out
+
+
+def chain_exit(data, entry, end):
+    """The chain walked from `entry` to `end` as the tile walk does it -> (exit, records, stopped by the data)"""
+    n, o, cnt = len(data), entry, 0
+    while o < end:
+        if n - o < 4:
+            return o, cnt, True
+        bs = struct.unpack_from("<i", data, o)[0]
+        f = _fixed_ok(data, o, None) if 32 <= bs <= n - o - 4 else None
+        if f is None or data[o + 36 + f[1] - 1] != 0:
+            return o, cnt, True
+        o += 4 + bs; cnt += 1
+    return o, cnt, False
+
+
+def dependent_decoys(tile, k, lead=3, tail=3, every=1, leak=False, pad=7, extra=()):
+    """Misses of the index's guess that depend on each other -> (refs, data, first, record offsets, decoy tiles).
+
+    One record of exactly `tile` bytes starts in every tile, 56 bytes before its end, so each tile's true entry is the exit
+    of the tile before it and no tile holds a second start.  A record's Z payload lies wholly in the next tile, in front
+    of that tile's record; in the k tiles lead, lead + every, ... it holds two consecutive well-formed fake records (as
+    decoy_bam), so the lowest offset of the tile that passes the guess rule is the first fake.  What follows the second
+    fake is filler: the walk from the guess stops there, short of the tile's true start, and nothing it leaves says where
+    the next tile is entered.  With every == 1 the run can therefore be repaired only one tile per stitch pass; with
+    every == 2 a tile that guesses right follows each miss and the misses are independent.
+    leak: the second fake's block_size carries the wrong chain to a filler offset in the next tile instead, so that the
+    stitch hands a WRONG entry to the tile after the next.
+    The regular part ends with a 38-byte record inside the last tile (a last tile without a record start would itself be
+    a miss and cost a round); `extra` record dicts follow it and are not part of the asserted layout.
+    Asserted here, on the CPU, by the restated guess rule: in each decoy tile the first hit is the fake and the walk from
+    it does not reach the true chain; in every other tile the first hit is the true start."""
+    assert tile >= 256 and lead >= 1 and every >= 1
+    refs = EDGE_REFS
+    s = tile - 56
+    head = encode_header("", refs)
+    fakes = [bytearray(encode_record(rec(f"fake{i}", cigar=C("8M"), tid=i))) for i in range(2)]
+    if leak:
+        fakes[1][:4] = struct.pack("<i", tile + len(fakes[1]) + 12)
+    fake = bytes(fakes[0] + fakes[1])
+    decoys = [lead + every * i for i in range(k)]
+    n_regular = (decoys[-1] if decoys else lead) + 1 + tail       # tiles with a full-size record
+    recs, fake_at = [], {}
+    r = rec("pad", cigar=C("10M"), aux=[("XP", "Z", b"")])
+    r["aux"][0][2] = b"p" * (s - len(head) - len(encode_record(r)))
+    recs.append(r)
+    for j in range(n_regular):
+        r = rec(f"r{j:05d}", cigar=C("10M"), pos=1000 + j, aux=[("XD", "Z", b"")])
+        body = bytearray(b"p" * (tile - len(encode_record(r))))
+        payload_at = j * tile + s + len(encode_record(r)) - 1
+        assert payload_at > (j + 1) * tile and len(body) > pad + len(fake) + 40
+        if j + 1 in decoys:                                      # this record's payload is the front of tile j + 1
+            body[pad:pad + len(fake)] = fake
+            fake_at[j + 1] = payload_at + pad
+        r["aux"][0][2] = bytes(body)
+        recs.append(r)
+    recs.append(dict(qname="s", flag=0, tid=0, pos=7, mapq=0, cigar=[], mtid=-1, mpos=-1, tlen=0, seq="", qual=[], aux=[]))
+    recs += list(extra)
+    data, first, at = encode_bam("", refs, recs)
+    assert first == len(head) and [int(a) % tile for a in at[1:n_regular + 2]] == [s] * (n_regular + 1)
+    starts = {int(a) // tile: int(a) for a in at[1:n_regular + 2]}
+    hits = first_hits(data, first, len(refs), tile, n_regular + 1)
+    for t in range(1, n_regular + 1):
+        if t in decoys:
+            assert hits[t] == fake_at[t] < starts[t] and data[fake_at[t]:fake_at[t] + len(fake)] == fake, (t, hits[t], fake_at[t])
+            ex, cnt, stopped = chain_exit(data, hits[t], (t + 1) * tile)
+            assert cnt == 2 and ex != starts[t + 1] and stopped != leak, (t, ex, cnt, stopped)
+            if leak:
+                assert (t + 1) * tile < ex < starts[t + 1] and not guess_hit(data, len(data), ex, len(refs))
+        else:
+            assert hits[t] == starts[t], (t, hits[t], starts[t])
+    assert hits[0] == first
+    return refs, data, first, at, decoys
 
 
 def mutate(rng, data, first):

@@ -1,5 +1,6 @@
 """BGZF blocks for the inflate tests, made with Python's zlib: every level / window / memLevel / strategy zlib offers, over
-data of many kinds, plus corrupt and hand-crafted hostile blocks."""
+data of many kinds, plus corrupt and hand-crafted hostile blocks, and members written token by token (fixed_block,
+stored_block) that sit on the seams of the device inflater's window."""
 import struct
 import zlib
 
@@ -176,6 +177,226 @@ def crafted_bad_blocks():
         payload = b.bytes() if isinstance(b, Bits) else b
         res.append((name, member(payload, 0, 4)))
     return res
+
+
+# ---- hand-made streams for the seams of the device inflater's window (WaveSink of mgx_bgzf_inflate.hip) -------------------
+_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEN_EXTRA = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
+_DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
+              12289, 16385, 24577]
+_DIST_EXTRA = [0, 0, 0, 0] + [e for e in range(1, 14) for _ in (0, 1)]
+TOK, WIN = 512, 4096                                          # kTok, kWin of the kernel: a window is expanded at 512 tokens or 4096 bytes
+
+
+def _fixed_sym(b, s):
+    if s < 144:
+        b.put_rev(0x30 + s, 8)
+    elif s < 256:
+        b.put_rev(0x190 + s - 144, 9)
+    elif s < 280:
+        b.put_rev(s - 256, 7)
+    else:
+        b.put_rev(0xc0 + s - 280, 8)
+
+
+def fixed_block(tokens, last, b=None):
+    """A fixed-Huffman block (RFC 1951 3.2.6) of tokens ("L", byte) and ("M", len, dist), appended to the bit stream b.
+    Nothing is checked but the ranges a code exists for: a distance may reach back past the output."""
+    b = Bits() if b is None else b
+    b.put(1 if last else 0, 1).put(1, 2)
+    for t in tokens:
+        if t[0] == "L":
+            _fixed_sym(b, t[1])
+            continue
+        _, ln, dist = t
+        assert 3 <= ln <= 258 and 1 <= dist <= 32768
+        i = 28 if ln == 258 else max(k for k in range(28) if _LEN_BASE[k] <= ln)
+        _fixed_sym(b, 257 + i)
+        b.put(ln - _LEN_BASE[i], _LEN_EXTRA[i])
+        j = max(k for k in range(30) if _DIST_BASE[k] <= dist)
+        b.put_rev(j, 5)
+        b.put(dist - _DIST_BASE[j], _DIST_EXTRA[j])
+    _fixed_sym(b, 256)
+    return b
+
+
+def stored_block(data, last, b=None):
+    b = Bits() if b is None else b
+    b.put(1 if last else 0, 1).put(0, 2)
+    b.put(0, -b.n % 8)
+    b.put(len(data), 16).put(len(data) ^ 0xffff, 16)
+    return b.put(int.from_bytes(data, "little"), 8 * len(data))
+
+
+def lits(n, salt=0):
+    return [("L", (i * 37 + i // 256 * 11 + salt) & 0xff) for i in range(n)]
+
+
+def produced(tokens):
+    return sum(1 if t[0] == "L" else t[1] for t in tokens)
+
+
+def fill(n, salt=0, period=29):
+    """tokens for n bytes: a short literal prefix, 258-byte matches over it, the rest"""
+    out = lits(min(n, period), salt)
+    left = n - len(out)
+    while left >= 258 + 3 or left == 258:
+        out.append(("M", 258, period)); left -= 258
+    if left > 258:                                               # 259 or 260: leave a match of 3 or 4
+        out.append(("M", 256, period)); left -= 256
+    if left >= 3:
+        out.append(("M", left, period)); left = 0
+    return out + lits(left, salt + 1)
+
+
+def windows(blocks):
+    """The windows the kernel's sink expands for blocks ("F", tokens) / ("S", bytes): [(start in the output, tokens, bytes)]"""
+    out, w0, nt, wb = [], 0, 0, 0
+    for kind, x in blocks:
+        if kind == "S":
+            if nt:
+                out.append((w0, nt, wb))
+            w0, nt, wb = w0 + wb + len(x), 0, 0
+            continue
+        assert kind == "F"
+        for t in x:
+            nt += 1; wb += 1 if t[0] == "L" else t[1]
+            if nt == TOK or wb >= WIN:
+                out.append((w0, nt, wb)); w0, nt, wb = w0 + wb, 0, 0
+    return out + ([(w0, nt, wb)] if nt else [])
+
+
+def to_window_start(tokens):
+    """tokens + literals up to the next point at which the sink's window is empty"""
+    tokens = list(tokens)
+    while True:
+        w = windows([("F", tokens)])
+        if sum(x[2] for x in w) == produced(tokens) and (not w or w[-1][1] == TOK or w[-1][2] >= WIN):
+            return tokens
+        tokens.append(("L", (len(tokens) * 5 + 1) & 0xff))
+
+
+def assemble(blocks):
+    """-> the raw DEFLATE payload of blocks ("F", tokens) / ("S", bytes) / ("Z", a Bits holding one non-final block)"""
+    b = Bits()
+    for i, (kind, x) in enumerate(blocks):
+        last = i == len(blocks) - 1
+        if kind == "F":
+            fixed_block(x, last, b)
+        elif kind == "S":
+            stored_block(x, last, b)
+        else:
+            assert not last
+            b.put(x.v, x.n)
+    return b.bytes()
+
+
+def dynamic_block_bits(data, before, after):
+    """zlib's level-9 dynamic block for `data` as bits, not final, cut to its exact length.  zlib pads its last byte with
+    up to 7 zero bits; the length is the one at which the block, set between two fixed blocks, decodes to the whole."""
+    raw = deflate_raw(data, 9)
+    assert raw[0] & 7 == 5                                       # BFINAL, BTYPE 10: one dynamic block
+    want = bytes(t[1] for t in before) + data + bytes(t[1] for t in after)
+    for cut in range(8):
+        z = Bits()
+        z.v, z.n = int.from_bytes(raw, "little") & ~1, 8 * len(raw) - cut
+        z.v &= (1 << z.n) - 1
+        try:
+            d = zlib.decompressobj(-15)
+            if d.decompress(assemble([("F", before), ("Z", z), ("F", after)])) == want and d.eof:
+                return z
+        except zlib.error:
+            pass
+    raise AssertionError("no cut of zlib's block decodes")
+
+
+def _member_of(blocks, isize=None, flip_last=False):
+    payload = assemble(blocks)
+    d = zlib.decompressobj(-15)
+    want = d.decompress(payload)                                 # the reference: zlib's own inflate of the payload
+    assert d.eof and not d.unused_data
+    crc = zlib.crc32(want[:-1] + bytes([want[-1] ^ 1])) if flip_last else zlib.crc32(want)
+    return member(payload, crc, len(want) if isize is None else isize), want
+
+
+def window_seam_cases():
+    """(name, member, want): single members whose tokens are placed on the seams of the device sink -- the token and byte
+    limits of a window, sources across a window's start, link chains, block kinds in one member, output lengths around the
+    64-way CRC split.  want is zlib's inflate of the payload; the windows a case is meant to produce are asserted here."""
+    cases = []
+
+    def add(name, blocks, expect=None):
+        if expect is not None:
+            assert expect(windows(blocks)), (name, windows(blocks)[:6])
+        m, want = _member_of(blocks)
+        cases.append((name, m, want))
+
+    # token count: a window of exactly 512 literals, one less, one more, and the same at the second window
+    for n in (511, 512, 513, 1023, 1024, 1025):
+        add(f"lit{n}", [("F", lits(n, n))], lambda w, n=n: [x[1] for x in w] == [TOK] * (n // TOK) + [n % TOK] * (n % TOK > 0))
+    # window bytes: the fullest window (4095 + 258 cells), exactly 4096, 4096 reached by a 3-byte match
+    pre = lits(37) + [("M", 258, 37)] * 15
+    assert produced(pre) == 3907
+    add("win4353", [("F", pre + [("M", 188, 37), ("M", 258, 100)] + lits(5, 3))], lambda w: w[0] == (0, 54, WIN + 257) and w[1][0] == WIN + 257)
+    add("win4096", [("F", pre + [("M", 189, 37)] + lits(5, 3) + [("M", 30, 4000)])], lambda w: w[0] == (0, 53, WIN) and w[1][0] == WIN)
+    add("win4093+3", [("F", pre + [("M", 186, 37), ("M", 3, 1)] + lits(5, 3) + [("M", 30, 4099)])], lambda w: w[0] == (0, 54, WIN))
+    # the source of a match across the window's start: the first window is 512 literals
+    first = lits(TOK, 9)
+    at_start = lambda w: w[0] == (0, TOK, TOK) and w[1][0] == TOK                # noqa: E731
+    add("src_before_periodic", [("F", first + [("M", 100, 5)] + lits(3))], at_start)                 # dist < len, every byte read back
+    add("src_mixed_periodic", [("F", first + lits(2, 1) + [("M", 50, 7)] + lits(3))], at_start)        # dist < len, tstart < dist
+    add("src_dist_eq_len", [("F", first + [("M", 20, 20)] + lits(2, 1) + [("M", 9, 9)])], at_start)
+    add("src_1_before", [("F", first + lits(4, 1) + [("M", 3, 5), ("M", 200, 300)])], at_start)        # dist > len: 1 byte before the window
+    add("src_2_before", [("F", first + lits(4, 1) + [("M", 4, 6), ("M", 258, 259)])], at_start)
+    far = to_window_start(lits(40, 2) + [("M", 258, 40)] * 128)
+    assert produced(far) >= 32768
+    add("src_32768_before", [("F", far + lits(1, 5) + [("M", 10, 32768), ("M", 258, 32768)])],
+        lambda w: any(x[0] == produced(far) for x in w))
+    # link chains
+    add("chain_dist1", [("F", lits(1, 65) + [("M", 258, 1)] * 16)], lambda w: w == [(0, 17, 1 + 16 * 258)])
+    for d in (2, 3, 7):
+        add(f"chain_dist{d}", [("F", lits(d, d) + [("M", max(d, 3), d)] * 500 + lits(2))], lambda w, d=d: w == [(0, 502 + d, d + 500 * max(d, 3) + 2)])
+    add("chain_three_windows", [("F", lits(1, 66) + [("M", 258, 1)] * 50 + lits(1) + [("M", 258, 2)] * 3)], lambda w: len(w) >= 4)
+    # block kinds in one member
+    some = lits(100, 4) + [("M", 40, 60)]
+    sbytes = bytes((i * 89 + 7) & 0xff for i in range(200))
+    add("fixed_stored_fixed", [("F", some), ("S", sbytes), ("F", [("M", 250, 260), ("L", 1), ("M", 30, 450)])],
+        lambda w: w == [(0, 101, 140), (340, 3, 281)])
+    add("stored_with_tokens_pending", [("F", lits(10, 8)), ("S", sbytes[:50]), ("F", [("M", 58, 58)])], lambda w: w[0] == (0, 10, 10))
+    add("stored_empty_not_last", [("F", some), ("S", b""), ("F", [("M", 100, 140)] + lits(3))], lambda w: w[1][0] == 140)
+    add("stored_empty_last", [("F", some), ("S", b"")])
+    add("stored_empty_first", [("S", b""), ("F", some)])
+    add("stored_only_empty", [("S", b"")])
+    for n in (1, 63, 64, 65):
+        add(f"stored{n}_then_match", [("F", lits(20, n)), ("S", sbytes[:n]), ("F", [("M", 30, n + 10), ("M", 258, n + 40)])])
+    add("final_empty_fixed", [("F", some), ("F", [])])
+    text = b"".join(b"line %d of the dynamic block, with some text to code\n" % (i * i) for i in range(60))
+    before, after = lits(300, 6), lits(5, 7)
+    z = dynamic_block_bits(text, before, after)
+    add("fixed_dynamic_fixed", [("F", before), ("Z", z), ("F", after + [("M", 258, len(text) + 100), ("M", 100, 4)])])
+    # output length: the CRC's 64 lanes and the x^(8n) shift
+    for n in (0, 1, 63, 64, 65, 127, 4095, 4096, 4097, 65535, 65536):
+        add(f"isize{n}", [("F", fill(n, n))])
+        assert len(cases[-1][2]) == n and len(cases[-1][1]) < 4000
+    assert len({c[0] for c in cases}) == len(cases)
+    return cases
+
+
+def window_seam_hostile():
+    """(name, member, status): members the inflater must refuse with this status (bgzf_inflate_core.h: 11 distance too far
+    back, 12 output longer than ISIZE, 14 CRC mismatch), each at a seam of the window."""
+    out = []
+    payload = fixed_block(lits(TOK, 9) + lits(2, 1) + [("M", 10, TOK + 3)] + lits(4), True).bytes()      # one byte before the output
+    out.append(("dist_too_far_across_window", member(payload, 0, TOK + 16), 11))
+    toks = lits(37) + [("M", 258, 37)] * 15 + [("M", 188, 37)]
+    assert produced(toks) == WIN - 1 and windows([("F", toks)]) == [(0, 53, WIN - 1)]
+    good, want = _member_of([("F", toks + [("M", 257, 100)])])
+    payload = fixed_block(toks + [("M", 258, 100)], True).bytes()                                  # ISIZE + 1 bytes, over the window's end
+    out.append(("overflow_across_window", member(payload, zlib.crc32(want), len(want)), 12))
+    m, want = _member_of([("F", fill(4094, 3) + lits(3, 8))], flip_last=True)                     # lane 63 covers bytes 4095 and 4096
+    assert len(want) == 4097
+    out.append(("crc_last_lane", m, 14))
+    return out
 
 
 def mutate(rng, blk):

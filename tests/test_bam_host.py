@@ -197,3 +197,21 @@ def test_pack_keys_on_several_threads(pkg, synth, tmp_path, monkeypatch):
         rep[k] = np.concatenate([o[:-1] + np.uint64(i) * o[-1] for i in range(17)] + [np.array([17 * int(o[-1])], dtype=np.uint64)])
     want = pkg.sortdedup.pack(rep)
     assert got[0].tobytes() == want[0].tobytes() and np.array_equal(got[1], want[1]) and got[2] == want[2]
+
+
+@pytest.mark.parametrize("kw", [dict(tile=256, k=0), dict(tile=256, k=1), dict(tile=256, k=12), dict(tile=256, k=12, every=2),
+                                dict(tile=256, k=3, leak=True), dict(tile=256, k=3, lead=255), dict(tile=256, k=12, lead=251, leak=True),
+                                dict(tile=16384, k=5), dict(tile=16384, k=3, leak=True)], ids=lambda kw: "-".join(f"{k}{v}" for k, v in kw.items()))
+def test_dependent_decoy_layout(pkg, kw):
+    """The inputs of the device index's repair-round tests (test_bam_gpu.py): the builder asserts, by the guess rule
+    restated in Python, that exactly the decoy tiles guess a fake and that the walk from it misses the true chain; here the
+    host walk finds the records the builder laid down, so the bytes are a valid chain and the fakes are not on it."""
+    refs, data, first, at, decoys = bm.dependent_decoys(**kw)
+    assert len(decoys) == kw["k"] and decoys == sorted(set(decoys))
+    off, nxt = pkg.bam.walk_host(data, first)
+    assert np.array_equal(off, at) and nxt == len(data)
+    assert pkg.bam.parse_header(data)[2] == first
+    # the guess rule's restatement against the host's own validity: every true start passes it, no filler byte does
+    for o in at[1:-1]:
+        assert bm.guess_hit(data, len(data), int(o), len(refs))
+    assert not bm.guess_hit(data, len(data), int(at[1]) + 1, len(refs))

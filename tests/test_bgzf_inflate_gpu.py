@@ -1,7 +1,8 @@
 """The device BGZF inflater (mgx_bgzf_inflate_*, mgx_bgzf_decompress): blocks made by zlib with every level, window,
 memLevel and strategy over many kinds of data, blocks from the device compressor, htslib's own BAM files, a stream of
-ragged blocks over several batches in flight, and corrupt blocks inside good batches -- the error names the block, the
-other blocks are intact, the context stays usable."""
+ragged blocks over several batches in flight, hand-made members on the seams of the window expansion (token and byte
+limits, sources across a window's start, link chains, stored blocks between Huffman blocks, ISIZE up to 65 536), and
+corrupt blocks inside good batches -- the error names the block, the other blocks are intact, the context stays usable."""
 import gzip
 import os
 
@@ -134,3 +135,69 @@ def test_corrupt_blocks_name_the_block_and_leave_the_context_usable(pkg, inf):
     # and the one-shot path names the bad block of the whole stream
     with pytest.raises(pkg.MgxError, match="block 9 "):
         inf.decompress(b"".join(good[:9] + [bytes(bad_crc)] + good[10:]))
+
+
+# ---- the seams of the window expansion (bgzf_cases.window_seam_cases: hand-made members, zlib's inflate as the reference) ----
+@pytest.fixture(scope="module")
+def seams():
+    return bc.window_seam_cases()
+
+
+def check_batch(inf, cases):
+    """one batch of (name, member, want): every status 0, every block's bytes equal to want"""
+    data, status, err = run_batch(inf, [m for _, m, _ in cases])
+    offs = np.cumsum([0] + [len(w) for _, _, w in cases])
+    bad = [name for i, (name, _, w) in enumerate(cases) if status[i] != 0 or data[offs[i]:offs[i + 1]] != w]
+    assert not bad and err is None and len(data) == offs[-1], (bad, err)
+
+
+def test_window_seams_in_one_batch(inf, seams):
+    check_batch(inf, seams)
+    for case in seams:                                            # and each alone: a wavefront that has served no other block
+        if case[0] in ("isize0", "isize65536", "win4353", "chain_dist1", "stored_only_empty"):
+            check_batch(inf, [case])
+
+
+def test_window_seams_between_ordinary_blocks_and_reversed(inf, seams):
+    """One wavefront serves several blocks in turn (more blocks than the grid has wavefronts): the window, the token list
+    and the tables in LDS must not leak from one block into the next, whatever the order."""
+    rng = np.random.RandomState(14)
+    text = bc.sam_like(rng, 60_000)
+    plain = [("zlib%d" % i, bc.block(text[i * 3000:(i + 1) * 3000 + 17 * i], level=i % 10), text[i * 3000:(i + 1) * 3000 + 17 * i]) for i in range(len(seams))]
+    mixed = [c for pair in zip(seams, plain) for c in pair]
+    check_batch(inf, mixed)
+    check_batch(inf, mixed[::-1])
+    many = (mixed + mixed[::-1]) * 30                              # more blocks than 8 wavefronts on each of 256 CUs
+    assert len(many) > 2 * 2048
+    check_batch(inf, many)
+
+
+def test_hostile_window_seams_inside_good_batches(pkg, inf, seams):
+    hostile = bc.window_seam_hostile()
+    assert sorted(s for _, _, s in hostile) == [11, 12, 14]
+    good = [c for c in seams if c[0] in ("win4353", "src_mixed_periodic", "chain_dist1", "fixed_stored_fixed", "isize4097", "isize65536", "lit512")]
+    assert len(good) == 7
+    for name, bad, want_status in hostile:
+        pos = 3
+        blocks = [m for _, m, _ in good]
+        blocks[pos] = bad
+        data, status, err = run_batch(inf, blocks)
+        assert err is not None and f"block {pos} " in err, (name, err)
+        assert list(np.nonzero(status)[0]) == [pos] and status[pos] == want_status, (name, status)
+        offs = np.cumsum([0] + [int.from_bytes(b[-4:], "little") for b in blocks])
+        for i, (gname, _, w) in enumerate(good):
+            if i != pos:
+                assert data[offs[i]:offs[i + 1]] == w, (name, gname)
+        check_batch(inf, good)                                     # the context is usable afterwards
+    # every wavefront serves good and hostile blocks in turn: what a refused block leaves in LDS does not reach the next
+    unit = [good[0], good[1], hostile[0], good[2], hostile[1], good[4], hostile[2]]
+    blocks = [c[1] for c in unit] * 350
+    assert len(blocks) > 2048
+    data, status, err = run_batch(inf, blocks)
+    assert list(status) == [0, 0, 11, 0, 12, 0, 14] * 350, err
+    offs = np.cumsum([0] + [int.from_bytes(b[-4:], "little") for b in blocks])
+    for i in range(len(blocks)):
+        if status[i] == 0:
+            assert data[offs[i]:offs[i + 1]] == unit[i % 7][2], (i, unit[i % 7][0])
+    with pytest.raises(pkg.MgxError, match="block 2 "):
+        inf.decompress(good[0][1] + good[1][1] + hostile[0][1] + good[2][1])

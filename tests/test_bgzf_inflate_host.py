@@ -4,6 +4,7 @@ bytes, corrupt and hostile blocks decode correctly or fail (never a sanitizer re
 Python's walk over split and concatenated streams."""
 import gzip
 import os
+import struct
 import subprocess
 import zlib
 
@@ -104,6 +105,42 @@ def test_one_length_one_distance_code_is_accepted(driver, tmp_path):
     bc.case_file(p, [(blk, want)])
     c, st = counts(run(driver, "inflate", p))
     assert c["ok"] == 1 and c["wrong"] == 0, (c, st)
+
+
+def test_window_seam_cases_are_valid_streams():
+    """The hand-made members of bgzf_cases.window_seam_cases: zlib accepts every payload, whole, and yields `want`; the
+    trailer carries want's CRC and length.  (No device, no driver: this proves the inputs of the device tests.)"""
+    cases = bc.window_seam_cases()
+    assert len(cases) >= 40
+    for name, m, want in cases:
+        d = zlib.decompressobj(-15)
+        assert d.decompress(m[18:-8]) == want and d.eof and d.unused_data == b"", name
+        assert m[-8:] == struct.pack("<II", zlib.crc32(want), len(want)), name
+        assert gzip.decompress(m) == want, name
+    assert max(len(w) for _, _, w in cases) == 65536 > bc.MAX_IN
+    for name, m, status in bc.window_seam_hostile():
+        if status == 11:
+            with pytest.raises(zlib.error):                          # zlib refuses the distance too
+                zlib.decompressobj(-15).decompress(m[18:-8])
+        else:                                                        # a valid stream: one byte more than ISIZE, or another CRC
+            got = zlib.decompressobj(-15).decompress(m[18:-8])
+            isize = int.from_bytes(m[-4:], "little")
+            assert (len(got) == isize + 1) if status == 12 else (len(got) == isize and zlib.crc32(got) != int.from_bytes(m[-8:-4], "little")), name
+
+
+def test_window_seam_cases_on_the_shared_core(driver, tmp_path):
+    """The same members through bgzf_inflate_core.h with the host sink, under the sanitizers: every good case decodes to
+    `want`, every hostile one fails with the status it was made for."""
+    cases = bc.window_seam_cases()
+    path = str(tmp_path / "seams.bin")
+    bc.case_file(path, [(m, want) for _, m, want in cases])
+    c, st = counts(run(driver, "inflate", path))
+    assert c["cases"] == len(cases) and c["ok"] == len(cases) and c["wrong"] == 0, (c, st)
+    for name, m, status in bc.window_seam_hostile():
+        p = str(tmp_path / (name + ".bin"))
+        bc.case_file(p, [(m, None)])
+        _, s1 = counts(run(driver, "inflate", p))
+        assert s1 == {status: 1}, (name, s1)
 
 
 def test_scanner_agrees_with_python(driver, tmp_path):
