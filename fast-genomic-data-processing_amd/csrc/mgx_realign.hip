@@ -28,6 +28,7 @@
 #include "mgx_realign_internal.h"
 #include "pairhmm_pack.h"
 #include "read_to_ref_rule.h"
+#include "sw_trace_rule.h"
 
 using mgx::set_error;
 using namespace mgx_internal;
@@ -417,12 +418,10 @@ int gather_chunk(void* user, hipStream_t s, u64 lo, u64 hi, u8* d_ref, u8* d_alt
     return 0;
 }
 
-// "<len>M" under the aligner's capacity rule (PairWiseSW.h:410-444: an element whose text does not fit is skipped)
+// "<len>M" as the aligner writes a one-element list (sw_trace_rule.h: an element whose text does not fit is skipped; a read is at most max_alt bases)
 void verbatim_text(u32 len, u64 hap_len, char* dst, u32 stride) {
-    char tmp[16];
-    const int need = snprintf(tmp, sizeof tmp, "%uM", len);
-    const u64 cap = std::min<u64>(2ull * std::max<u64>(hap_len, len), (u64)stride - 1);
-    if ((u64)need <= cap) memcpy(dst, tmp, (size_t)need + 1); else dst[0] = 0;
+    const int16_t el[2] = {(int16_t)mgx_sw_trace::kOpMatch, (int16_t)len};
+    dst[mgx_sw_trace::render(el, 1, dst, mgx_sw_trace::text_cap(hap_len, len, stride))] = 0;
 }
 
 // ---- the per-read results into the caller's arrays of every region: dropped, verbatim, aligned

@@ -11,9 +11,11 @@
 //   * best end cell among equal scores, replayed in anti-diagonal order: PairWiseSW.h:256-285
 //   * back-trace state machine, leading / trailing overhang, merge: PairWiseSW.h:299-408
 //   * CIGAR text and its capacity rule (host, next to the caller's buffer): PairWiseSW.h:410-444
+// The cell, the end-cell ties, the walk and the text are stated once, in sw_trace_rule.h, which also runs on the CPU
+// (tests/cpp/sw_trace_driver.cpp); this file keeps the sweeps, the launches and the host stages.
 //
 // Back-trace bytes are laid out by (step, lane, row-in-lane) so that one step of a wavefront stores
-// 64 * RPL consecutive bytes; the trace kernel converts (i, j) back to that index (BtView).
+// 64 * RPL consecutive bytes (bt_slot_at); the trace converts (i, j) back to that index (BtView, sw_trace_rule.h).
 //
 // Three fill kernels:
 //   k_sw_fill16   packed 16-bit scores, two pairs per lane group, the four decisions of a cell taken from the sign bits of four
@@ -22,7 +24,8 @@
 //   k_sw_fill     32-bit scores, one pair per lane group, compare + select per decision, back-trace bytes, one launch per row class
 //                 -- everything else (long references with long alternates, large scoring parameters)
 //   k_sw_fill_strip  the 32-bit cell with a strip loop around the sweep, for references of 2049 .. 32 767 bases (MGX_SW_LONG_REF)
-// All write what the trace kernel reads through BtView / LastRow / LastCol; a batch may mix them pair by pair.
+// All write what the trace kernel reads through BtView / LastRow / LastCol (sw_trace_rule.h: the addresses they store through and the
+// views that invert them); a batch may mix them pair by pair.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,46 +46,24 @@
 #include "mgx_hip_util.h"      // HIP_TRY
 #include "mgx_realign_internal.h"
 #include "sw_layout.h"
+#include "sw_trace_rule.h"
 
 using mgx::set_error;
 
 namespace {
 
 using namespace mgx_sw_layout;     // SwJob, shapes, region sizes, chunks, build_jobs, next_launch: sw_layout.h (CPU-tested)
-
-constexpr int kOpMatch = 0, kOpInsert = 1, kOpDelete = 2, kInsertExt = 4, kDeleteExt = 8;
-constexpr int kMinCutoff = -100000000;           // MATRIX_MIN_CUTOFF, smithwaterman_common.h:73
-constexpr int kLowInit = INT32_MIN / 2;          // LOW_INIT_VALUE, smithwaterman_common.h:74
+using namespace mgx_sw_trace;      // alphabet, addresses, views, sw_edge / sw_cell, end cell, walk, text: sw_trace_rule.h (CPU-tested)
 
 struct SwResult { int32_t score, max_i, max_j, offset, n_elems; };
-struct SwParams { int match, mismatch, open, extend; };
 
-// ---- what the fill kernels share.  H(x, 0) = H(0, x), x >= 1: the matrix boundary per overhang strategy (PairWiseSW.h:243-253)
-__device__ __forceinline__ int sw_edge(bool indel, const SwParams& P, int x) { return indel ? P.open + (x - 1) * P.extend : 0; }
-// One 32-bit cell (PairWiseSW.h:31-66), row k of a lane: hl / gs are the row's H and its gap state along the sweep, diag / up_h / up_g
-// come from the row above and leave as this row's for the row below; the back-trace byte goes into the lane's packed word.
-__device__ __forceinline__ void sw_cell(const SwParams& P, int sa, int c2, int k, int& hl, int& gs, int& diag, int& up_h, int& up_g, u32& packed) {
-    const int open_s = hl + P.open, ext_s = gs + P.extend;               // along the sweep
-    const int ee = max(open_s, ext_s);
-    const int open_c = up_h + P.open, ext_c = up_g + P.extend;           // along the lanes' own positions
-    const int ff = max(ext_c, open_c);
-    // E is the horizontal gap (INSERT), F the vertical one (DELETE); ties prefer the extension
-    int ext = 0;
-    if (!(open_s > ext_s)) ext |= kInsertExt;
-    if (!(open_c > ext_c)) ext |= kDeleteExt;
-    int h = max(diag + (sa == c2 ? P.match : P.mismatch), kMinCutoff);   // H prefers the diagonal, then E, then F
-    int op = kOpMatch;
-    if (ee > h) { op = kOpInsert; h = ee; }
-    if (ff > h) { op = kOpDelete; h = ff; }
-    diag = hl; hl = h; gs = ee; up_h = h; up_g = ff;
-    packed |= (u32)(op | ext) << ((k & 3) * 8);
-}
+// ---- what the fill kernels share beside sw_edge and sw_cell (sw_trace_rule.h).
 // Two pieces that take a lane's register arrays are macros over the kernel's RPL: a function is optimised on its own before it is inlined,
 // with the array as a pointer, and the pick became ONE indexed load, which moved hl to scratch memory (the store merely came out otherwise).
 // H of the pair's last row, which is row k_last of the lane that owns it: a select per row, the registers are not indexable
 #define MGX_SW_LAST_ROW_H(dst, hl, k_last) \
     do { int v_ = hl[0]; _Pragma("unroll") for (int k_ = 1; k_ < RPL; ++k_) if (k_ == k_last) v_ = hl[k_]; dst = v_; } while (0)
-// the back-trace bytes of one lane and step into their slot (bt_slot)
+// the back-trace bytes of one lane and step into their slot (bt_slot_at): row k is byte k
 #define MGX_SW_STORE_BT(dst_, packed) do { u8* dst = (dst_); \
     if constexpr (RPL == 1) dst[0] = (u8)packed[0]; \
     else if constexpr (RPL == 2) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)packed[0]; \
@@ -152,7 +133,7 @@ __global__ __launch_bounds__(64) void k_sw_fill(const SwJob* __restrict__ jobs, 
             for (int k = 0; k < RPL; ++k) sw_cell(P, sa[k], c2, k, hl[k], gs[k], diag, up_h, up_g, packed[k >> 2]);
             send_h = up_h; send_g = up_g;
             if (lane == lane_last) MGX_SW_LAST_ROW_H(edge_own[j], hl, k_last);
-            MGX_SW_STORE_BT(btp + ((size_t)t * G + lane) * bt_slot(RPL), packed);
+            MGX_SW_STORE_BT(btp + bt_slot_at(t, lane, G, bt_slot(RPL)), packed);
         }
     }
     // a lane's last active step is the last sweep position: its registers now hold H there (kept out of the loop --
@@ -246,7 +227,7 @@ __global__ __launch_bounds__(64) void k_sw_fill_strip(const SwJob* __restrict__ 
                         if (!last) bnd[j] = make_int2(up_h, up_g);        // lane 63, row base + kStripRows
                         else MGX_SW_LAST_ROW_H(last_row[j], hl, k_last);
                     }
-                    MGX_SW_STORE_BT(btp + ((size_t)t * 64 + lane) * SLOT, packed);
+                    MGX_SW_STORE_BT(btp + bt_slot_at(t, lane, 64, SLOT), packed);
                 }
             }
         }
@@ -364,15 +345,15 @@ __device__ __forceinline__ void sw_fill16_body(const SwJob& JA, const SwJob& JB,
             }
             if constexpr (RPL % 4 != 0) word[W - 1] >>= 4 * (4 - RPL % 4);
             send_h = up_h; send_g = up_g;
-            u32* dst = reinterpret_cast<u32*>(btp + ((size_t)t * G + lane) * (4 * W));
+            u32* dst = reinterpret_cast<u32*>(btp + bt_slot_at(t, lane, G, bt_slot16(RPL)));
 #pragma unroll
             for (int q = 0; q < W; ++q) dst[q] = word[q];
             // the lane's RPL packed H values (both halves) where LastRow / LastCol read them; a macro for the reason MGX_SW_LAST_ROW_H is one
 #define MGX_SW16_STORE_ROWS(dst) do { u32* d_ = (dst); _Pragma("unroll") for (int k = 0; k < RPL; ++k) d_[k] = bits(hl[k]); } while (0)
-            if (lane == lane_lastA) MGX_SW16_STORE_ROWS(lrA + (size_t)j * RPL);
-            if (lr_apart && lane == lane_lastB) MGX_SW16_STORE_ROWS(lrB + (size_t)j * RPL);
-            if (j == ncolA) MGX_SW16_STORE_ROWS(lcA + r0);
-            if (lc_apart && j == ncolB) MGX_SW16_STORE_ROWS(lcB + r0);
+            if (lane == lane_lastA) MGX_SW16_STORE_ROWS(lrA + lr16_at(j, RPL, 0));
+            if (lr_apart && lane == lane_lastB) MGX_SW16_STORE_ROWS(lrB + lr16_at(j, RPL, 0));
+            if (j == ncolA) MGX_SW16_STORE_ROWS(lcA + lc16_at(r0 + 1));
+            if (lc_apart && j == ncolB) MGX_SW16_STORE_ROWS(lcB + lc16_at(r0 + 1));
 #undef MGX_SW16_STORE_ROWS
         }
     }
@@ -407,53 +388,31 @@ __global__ __launch_bounds__(64) void k_sw_fill16(const SwJob* __restrict__ jobs
 #undef MGX_SW16_CASE
 }
 
-// what the trace kernel reads of a pair's back-trace, whichever kernel filled it: the byte of the 32-bit form (op | INSERT_EXT | DELETE_EXT)
-struct BtView {
-    const u8* p; int rpl, g, slot; bool i16; int half;
-    u64 strip_stride;          // bytes from one strip to the next; 0: the pair is one strip (every class but k_sw_fill_strip's)
-    __device__ BtView(const SwJob& J, const u8* bt) : p(bt + J.bt_off), rpl((int)J.rpl), g((int)(J.g & 0xFFu)),
-                                                     i16((J.g & kJobI16) != 0), half((J.g & kJobHalf) ? 1 : 0),
-                                                     strip_stride((J.g & kJobStrip) ? strip_bt_stride(J.len2) : 0) {
-        slot = i16 ? bt_slot16(rpl) : bt_slot(rpl);
+// The walk's diagonal provider on the device (sw_trace_rule.h: walk, LanesDiag is its CPU twin): the 64 lanes fetch the next 64 cells of the
+// current DIAGONAL in one gather (lane t: cell (c_i - t, c_j - t)) and the walk consumes them from registers.  A run of diagonal matches
+// is consumed in ONE step (round 3): the walk is wave-uniform -- one cell per iteration keeps 63 lanes idle for ~275 iterations per pair,
+// and that issue time, not the memory, was most of the trace kernel.
+struct WaveDiag {
+    const BtView& view; const int lane;
+    int cached = 0, c_i = 0, c_j = 0, tt = 0;
+    bool valid = false;
+    __device__ __forceinline__ int run(int i, int j) {
+        if (!diag_cached(valid, c_i, c_j, i, j)) {
+            c_i = i; c_j = j; valid = true;
+            const int ii = i - lane, jj = j - lane;
+            cached = (ii >= 1 && jj >= 1) ? view.cell(ii, jj) : 0;
+        }
+        tt = __builtin_amdgcn_readfirstlane(c_i - i);
+        return diag_run(__ballot((cached & 3) == kOpMatch), tt, i, j);
     }
-    __device__ int cell(int i, int j) const {
-        int r = i - 1;
-        size_t at = 0;
-        if (strip_stride) { const int s = r / kStripRows; r -= s * kStripRows; at = (size_t)s * strip_stride; }
-        const int l = r / rpl, k = r - l * rpl;                      // the lane that owns row i and its row in the lane
-        const size_t base = at + ((size_t)(j + l) * g + l) * slot;
-        if (!i16) return p[base + k];
-        const int by = p[base + (k >> 2) * 4 + half * 2 + ((k & 3) >> 1)];
-        const int nib = (k & 1) ? by >> 4 : by & 15;
-        return ((nib & 1) ? kOpDelete : (nib & 2) ? kOpInsert : kOpMatch) | ((nib & 8) ? 0 : kInsertExt) | ((nib & 4) ? 0 : kDeleteExt);
-    }
-};
-// H(nrow, j), j = 1 .. ncol
-struct LastRow {
-    const int32_t* p32; const u32* p16; int rpl, k_last, half;
-    __device__ LastRow(const SwJob& J, const u8* bt, const int32_t* sc) : p32(sc + J.sc_off), p16(reinterpret_cast<const u32*>(bt + J.lr_off)),
-                                                                            rpl((int)J.rpl), k_last(((int)J.len1 - 1) % (int)J.rpl), half((J.g & kJobHalf) ? 16 : 0) {
-        if (!(J.g & kJobI16)) p16 = nullptr;
-    }
-    __device__ int operator[](int j) const { return p16 ? (int)(int16_t)(p16[(size_t)j * rpl + k_last] >> half) : p32[j]; }
-};
-// H(i, ncol), i = 1 .. nrow
-struct LastCol {
-    const int32_t* p32; const u32* p16; int half;
-    __device__ LastCol(const SwJob& J, const u8* bt, const int32_t* sc) : p32(sc + J.sc_off + J.len2 + 1), p16(reinterpret_cast<const u32*>(bt + J.lc_off)),
-                                                                            half((J.g & kJobHalf) ? 16 : 0) {
-        if (!(J.g & kJobI16)) p16 = nullptr;
-    }
-    __device__ int operator[](int i) const { return p16 ? (int)(int16_t)(p16[i - 1] >> half) : p32[i]; }
+    __device__ __forceinline__ int byte(int, int) const { return __builtin_amdgcn_readlane(cached, tt); }
 };
 
 // One WAVEFRONT per pair: best end cell, back-trace, merged element list (in the order getCIGAR holds it).  A lane per
 // pair walks ~275 dependent byte loads of ~2 us each with a third of a wavefront per SIMD to hide them
-// behind; here the 64 lanes fetch the next 64 cells of the current DIAGONAL in one
-// gather (lane t: cell (i - t, j - t)) and the walk consumes them from registers, so an alignment of a few hundred
-// matches with a handful of gaps costs a handful of memory round trips.  Inside a gap (extension states) cells are
-// loaded one at a time as before.  The walk itself is wave-uniform; elements are merged on the fly (run-length form,
-// which is what the reference's final merge pass produces, PairWiseSW.h:390-408) and written by lane 0.
+// behind; here an alignment of a few hundred matches with a handful of gaps costs a handful of memory round trips (WaveDiag).
+// Inside a gap (extension states) cells are loaded one at a time as before.  The rules are sw_trace_rule.h's; the kernel keeps
+// how the edges are loaded, the maximum, the provider and lane 0's element store, and the compact copy.
 __global__ __launch_bounds__(64) void k_sw_trace_wave(const SwJob* __restrict__ jobs, u32 n, const u8* __restrict__ bt,
                                                       const int32_t* __restrict__ sc, int16_t* __restrict__ elems_all, SwResult* __restrict__ res,
                                                       int16_t* __restrict__ compact, int n_compact) {
@@ -468,27 +427,9 @@ __global__ __launch_bounds__(64) void k_sw_trace_wave(const SwJob* __restrict__ 
     const BtView view(J, bt);
     int16_t* el = elems_all + J.el_off;
     const bool use_row = strategy == MGX_SW_SOFTCLIP || strategy == MGX_SW_IGNORE;
-    // ---- best end cell (PairWiseSW.h:256-285).  The maximum first, in parallel; then the cells that reach it are
-    //      replayed in anti-diagonal order (row candidate before column candidate), which is all the tie rules see.
+    // ---- best end cell.  The maximum first, in parallel; then the cells that reach it go through EndCell::replay, 64 anti-diagonals a ballot
     int best = INT32_MIN;
-    int mi = 0, mj = 0;
-    bool have = false;
-    auto replay = [&](int d0, u64 ma, u64 mb) {           // the candidates of anti-diagonals d0 .. d0 + 63, in order
-        u64 any = ma | mb;
-        while (any) {
-            const int t = __ffsll((long long)any) - 1;
-            any &= any - 1;
-            const int dd = d0 + t;
-            if ((ma >> t) & 1) {
-                const int j = dd - nrow;
-                if (!have || abs(nrow - j) < abs(mi - mj)) { mi = nrow; mj = j; have = true; }
-            }
-            if ((mb >> t) & 1) {
-                const int i = dd - ncol;
-                if (!have || mj == ncol || abs(i - ncol) <= abs(mi - mj)) { mi = i; mj = ncol; have = true; }
-            }
-        }
-    };
+    EndCell end(nrow, ncol);
     constexpr int kEdgeRegs = 8;
     if (nrow + ncol <= 64 * kEdgeRegs) {
         // the usual case (a read against its haplotype window): both edges fit the wavefront's registers -- all loads issued at
@@ -507,7 +448,7 @@ __global__ __launch_bounds__(64) void k_sw_trace_wave(const SwJob* __restrict__ 
 #pragma unroll
         for (int q = 0; q < kEdgeRegs; ++q) {
             if (1 + 64 * q > nrow + ncol) break;
-            replay(1 + 64 * q, __ballot(va[q] == best), __ballot(vb[q] == best));
+            end.replay(1 + 64 * q, __ballot(va[q] == best), __ballot(vb[q] == best));
         }
     } else {
         if (use_row) for (int j = 1 + lane; j <= ncol; j += 64) best = max(best, last_row[j]);
@@ -519,77 +460,20 @@ __global__ __launch_bounds__(64) void k_sw_trace_wave(const SwJob* __restrict__ 
             const int ja = d - nrow, ib = d - ncol;
             const bool eq_a = use_row && d <= nrow + ncol && ja >= 1 && last_row[ja] == best;
             const bool eq_b = d <= nrow + ncol && ib >= 1 && last_col[ib] == best;
-            replay(d0, __ballot(eq_a), __ballot(eq_b));
+            end.replay(d0, __ballot(eq_a), __ballot(eq_b));
         }
     }
-    // ---- back-trace (PairWiseSW.h:299-408), elements in run-length form
-    int i, j;
-    if (strategy == MGX_SW_INDEL) { i = nrow; j = ncol; }
-    else if (strategy == MGX_SW_LEADING_INDEL) { i = mi; j = ncol; }
-    else { i = mi; j = mj; }
-    int m = 0;                    // elements written so far
-    int cur_op = -1, cur_len = 0; // the open element
-    auto flush = [&]() {
-        if (cur_op >= 0) { if (lane == 0) { el[2 * m] = (int16_t)cur_op; el[2 * m + 1] = (int16_t)cur_len; } ++m; }
-    };
-    auto push = [&](int op, int len) {          // append, merging with the open element
-        if (op == cur_op) cur_len += len;
-        else { flush(); cur_op = op; cur_len = len; }
-    };
-    if (j < ncol) push(MGX_SW_SOFTCLIP, ncol - j);
-    int state = 0;
-    int c_i = 0, c_j = 0;         // the cached diagonal starts at (c_i, c_j): lane t holds cell (c_i - t, c_j - t)
-    int cached = 0;
-    bool valid = false;
-    while (i > 0 && j > 0) {
-        int btr;
-        if (state == 0) {
-            int t = c_i - i;
-            if (!valid || t < 0 || t >= 64 || c_j - j != t) {
-                c_i = i; c_j = j; valid = true; t = 0;
-                const int ii = i - lane, jj = j - lane;
-                cached = (ii >= 1 && jj >= 1) ? view.cell(ii, jj) : 0;
-            }
-            const int tt = __builtin_amdgcn_readfirstlane(t);
-            // A run of diagonal matches is consumed in ONE step (round 3): the walk is wave-uniform -- one cell per iteration keeps
-            // 63 lanes idle for ~275 iterations per pair, and that issue time, not the memory, was most of the trace kernel.  Lanes
-            // beyond the matrix hold 0 = a match: the run is bounded by i and j.
-            const u64 rest = ~(__ballot((cached & 3) == kOpMatch) >> tt);
-            const int run = min(rest ? (int)__builtin_ctzll(rest) : 64, min(i, j));
-            if (run > 0) { i -= run; j -= run; push(kOpMatch, run); continue; }
-            btr = __builtin_amdgcn_readlane(cached, tt);
-        } else {
-            btr = view.cell(i, j);
-        }
-        if (state == kInsertExt) { --j; cur_len++; state = btr & kInsertExt; }
-        else if (state == kDeleteExt) { --i; cur_len++; state = btr & kDeleteExt; }
-        else {
-            const int op = btr & 3;
-            if (op == kOpMatch) { --i; --j; push(kOpMatch, 1); state = 0; }
-            else if (op == kOpInsert) { --j; push(kOpInsert, 1); state = btr & kInsertExt; }
-            else { --i; push(kOpDelete, 1); state = btr & kDeleteExt; }
-        }
-    }
-    int offset;
-    if (strategy == MGX_SW_SOFTCLIP) {
-        if (j > 0) push(MGX_SW_SOFTCLIP, j);
-        offset = i;
-    } else if (strategy == MGX_SW_IGNORE) {
-        if (j > 0) push(cur_op, j);             // "the last element once more, j long"
-        offset = (int16_t)(i - j);
-    } else {
-        if (i > 0) push(kOpDelete, i);
-        else if (j > 0) push(kOpInsert, j);
-        offset = 0;
-    }
-    flush();
+    // ---- back-trace: the walk is wave-uniform, lane 0 writes the elements
+    WaveDiag diag{view, lane};
+    const Walked w = walk(nrow, ncol, strategy, end.mi, end.mj, [&](int i, int j) { return view.cell(i, j); }, diag,
+                          [&](int k, int op, int len) { if (lane == 0) { el[2 * k] = (int16_t)op; el[2 * k + 1] = (int16_t)len; } });
     if (lane == 0) {
-        SwResult r; r.score = best; r.max_i = mi; r.max_j = mj; r.offset = offset; r.n_elems = m;
+        SwResult r; r.score = best; r.max_i = end.mi; r.max_j = end.mj; r.offset = w.offset; r.n_elems = w.n_elems;
         res[J.out_index] = r;
     }
     __syncthreads();                             // lane 0's element stores before the block's lanes copy them
     int16_t* ce = compact + (size_t)J.out_index * 2 * n_compact;
-    for (int q = lane; q < 2 * min(m, n_compact); q += 64) ce[q] = el[q];
+    for (int q = lane; q < 2 * min(w.n_elems, n_compact); q += 64) ce[q] = el[q];
 }
 
 // alignments with more than kCompactElems elements: their element lists are packed densely for one download
@@ -614,31 +498,6 @@ struct Knobs {
     }
 };
 constexpr int kCompactElems = 16;             // merged CIGAR elements copied back per pair without a second look
-
-int itoa_len(int v) { const int neg = v < 0; if (neg) v = -v; int d = 0; while (v > 0) { v /= 10; ++d; } return d + neg; }
-
-// PairWiseSW.h:410-444: last element first; an element whose text does not fit is skipped
-// bam != nullptr: the elements that went into the text also as length << 4 | BAM operator (9 where the text says R), *n_bam of them;
-// out == nullptr: no text, the elements alone
-int render(const int16_t* el, int n_elems, char* out, int cap, u32* bam = nullptr, u32* n_bam = nullptr) {
-    int cur = 0;
-    for (int k = n_elems - 1; k >= 0; --k) {
-        const int op = el[2 * k], len = el[2 * k + 1];
-        const char c = op == kOpMatch ? 'M' : op == kOpInsert ? 'I' : op == kOpDelete ? 'D' : op == MGX_SW_SOFTCLIP ? 'S' : 'R';
-        const int need = itoa_len(len) + 1;
-        if (need > 1 && cur + need <= cap) {
-            if (bam && len > 0) bam[(*n_bam)++] = (u32)len << 4 | (c == 'M' ? 0u : c == 'I' ? 1u : c == 'D' ? 2u : c == 'S' ? 4u : 9u);
-            if (!out) { cur += need; continue; }
-            int v = len;
-            if (v < 0) { out[cur++] = '-'; v = -v; }
-            const int d = itoa_len(v);
-            for (int q = d - 1; q >= 0; --q) { out[cur + q] = (char)('0' + v % 10); v /= 10; }
-            cur += d;
-            out[cur++] = c;
-        }
-    }
-    return cur;
-}
 
 template <typename T>
 struct DevBuf {
@@ -864,8 +723,7 @@ void emit_text(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, const Fetche
             if (out.score) out.score[p] = r.score;
             if (out.cigar || out.sink) {
                 char* dst = out.cigar ? out.cigar + (size_t)p * out.stride : nullptr;
-                const int cap = out.cap_override >= 0 ? out.cap_override
-                                                      : (int)std::min<u64>(2ull * std::max(l.l1, l.l2), out.cigar ? (u64)out.stride - 1 : ~0ull);   // IntelSmithWaterman.cpp:8
+                const int cap = out.cap_override >= 0 ? out.cap_override : text_cap(l.l1, l.l2, out.cigar ? (u64)out.stride : kNoStride);
                 const int16_t* src = r.n_elems > kCompactElems ? f.big.get() + f.big_at[q] : f.cel + (size_t)q * 2 * kCompactElems;
                 const int len = render(src, r.n_elems, dst, cap, out.sink ? out.sink->el.data() + out.sink->off[p] : nullptr, out.sink ? &out.sink->n[p] : nullptr);
                 if (dst) dst[len] = 0;                    // cap <= stride - 1
