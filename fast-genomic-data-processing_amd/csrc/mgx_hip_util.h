@@ -52,6 +52,23 @@ struct Owner {
     ~Owner() { release(); }
 };
 
+// a device buffer with a pinned mirror, grown on demand
+struct Mirror {
+    uint8_t* dev = nullptr; uint8_t* pin = nullptr; size_t cap = 0;
+    int reserve(size_t n) {
+        if (n <= cap) return 0;
+        release();
+        const size_t want = n + n / 4 + 256;
+        if (hipMalloc((void**)&dev, want) != hipSuccess || hipHostMalloc((void**)&pin, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); release(); mgx::set_error("allocation of %zu bytes failed", want); return -ENOMEM;
+        }
+        cap = want;
+        return 0;
+    }
+    void release() { if (dev) (void)hipFree(dev); if (pin) (void)hipHostFree(pin); dev = pin = nullptr; cap = 0; }
+    ~Mirror() { release(); }
+};
+
 // rc, with the message that came with it kept across a destroy (which may set another)
 template <typename Destroy> int keep_error(int rc, Destroy destroy) {
     const std::string msg = rc ? mgx_last_error() : "";

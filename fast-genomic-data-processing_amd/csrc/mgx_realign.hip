@@ -31,6 +31,7 @@
 #include "sw_trace_rule.h"
 
 using mgx::set_error;
+using mgx_hip::Mirror;
 using namespace mgx_internal;
 
 namespace {
@@ -144,23 +145,6 @@ __global__ __launch_bounds__(256) void k_read_to_ref(const ToRefJob* __restrict_
         out_status[r] = res.status;
     }
 }
-
-// a device buffer with a pinned mirror, grown on demand
-struct Mirror {
-    u8* dev = nullptr; u8* pin = nullptr; size_t cap = 0;
-    int reserve(size_t n) {
-        if (n <= cap) return 0;
-        release();
-        const size_t want = n + n / 4 + 256;
-        if (hipMalloc((void**)&dev, want) != hipSuccess || hipHostMalloc((void**)&pin, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); release(); set_error("allocation of %zu bytes failed", want); return -ENOMEM;
-        }
-        cap = want;
-        return 0;
-    }
-    void release() { if (dev) (void)hipFree(dev); if (pin) (void)hipHostFree(pin); dev = pin = nullptr; cap = 0; }
-    ~Mirror() { release(); }
-};
 
 // what a PairHMM context keeps for this call (mgx_internal::PairhmmExt)
 struct Realign {

@@ -99,4 +99,33 @@ const Tables<double>& tables<double>() {
     return t;
 }
 
+// digamma at the integers as the reference's cache evaluates it: from 49 on the asymptotic series ln x - 1/(2x) - 1/(12 x^2) -/+ ..., and
+// psi(n) = psi(n + 1) - 1/n below it.  The series' next term is +1/(120 x^4); the reference subtracts it (sic, as Apache Commons Math's
+// Gamma.digamma does), which puts every value 2/(120 x^4) <= 2.9e-9 below the function.  Under a common offset the difference
+// digamma(nRef + 1) - digamma(nAlt + 1) of the rule keeps it only where one count is below 49 and the other is not, but there it moves the
+// log-odds by more than the 1e-9 they are held to, so the sign is the reference's.  log10(n!) = lgamma(n + 1) log10(e).
+void build_activity_tables(unsigned n_counts, ActivityTables* out) {
+    constexpr unsigned kSeriesFrom = 49;
+    auto series = [](double x) {
+        const double inv = 1.0 / (x * x);
+        return std::log(x) - 0.5 / x - inv * (1.0 / 12 + inv * (1.0 / 120 - inv / 252));
+    };
+    const unsigned n_dig = std::max(n_counts, kSeriesFrom + 1);
+    std::vector<double> dig(n_dig);
+    for (unsigned n = kSeriesFrom; n < n_dig; ++n) dig[n] = series(double(n));
+    for (unsigned n = kSeriesFrom; n-- > 0;) dig[n] = dig[n + 1] - 1.0 / double(n);          // n = 0: -inf
+    out->digamma.assign(dig.begin(), dig.begin() + n_counts);
+    out->log10_factorial.resize(n_counts);
+    for (unsigned n = 0; n < n_counts; ++n) out->log10_factorial[n] = std::lgamma(double(n) + 1.0) * 0.4342944819032518;
+    constexpr double kPhredToLogErrorProb = -0.23025850929940458;      // -ln(10) / 10
+    constexpr double kLogHalf = -0.6931471805599453;
+    for (int q = 0; q < 128; ++q) {
+        out->eps[q] = std::pow(10.0, double(q) / -10.0);
+        const double a = double(q) * kPhredToLogErrorProb;
+        out->log_eps[q] = a;
+        // log(1 - exp(a)) for a <= 0, the branch by which side of log(1/2) a lies
+        out->log_one_minus_eps[q] = a == 0 ? -HUGE_VAL : a < kLogHalf ? std::log1p(-std::exp(a)) : std::log(-std::expm1(a));
+    }
+}
+
 }  // namespace mgx

@@ -24,4 +24,13 @@ const Tables<float>& tables<float>();
 template <>
 const Tables<double>& tables<double>();
 
+// ---- active-site detection (activity_rule.h): the tables behind MathUtils::digamma / log10Factorial (M2/MathUtils.cpp:12-22) and the
+// per-quality caches of QualityUtils::qualToErrorProb (M2/QualityUtils.cpp:31-45) and NaturalLogUtils (M2/NaturalLogUtils.cpp:13-32)
+struct ActivityTables {
+    std::vector<double> digamma;          // [n_counts] digamma(n); digamma(0) = -inf
+    std::vector<double> log10_factorial;  // [n_counts] log10(n!)
+    double eps[128], log_eps[128], log_one_minus_eps[128];
+};
+void build_activity_tables(unsigned n_counts, ActivityTables* out);
+
 }  // namespace mgx

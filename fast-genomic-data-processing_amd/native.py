@@ -360,3 +360,32 @@ SAM_SYMBOLS = {
     "mgx_bgzf_store_put_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _U64P]),
 }
 SYMBOLS.update(SAM_SYMBOLS)
+
+
+# ---- include/mgx_activity.h -----------------------------------------------------------------------
+class ActivityInput(C.Structure):
+    _fields_ = [("interval_start", C.c_int32), ("n_loci", C.c_uint32), ("ref_bases", C.c_void_p), ("n_reads", C.c_uint64),
+                ("read_start", C.c_void_p), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p), ("base_off", C.c_void_p),
+                ("bases", C.c_void_p), ("quals", C.c_void_p), ("flags", C.c_void_p), ("mate_start", C.c_void_p), ("sample", C.c_void_p),
+                ("act_start", C.c_void_p), ("act_stop", C.c_void_p)]
+
+
+class ActivityParams(C.Structure):
+    _fields_ = [("has_normal", C.c_int32), ("genotype_germline_sites", C.c_int32), ("min_callable_depth", C.c_int32),
+                ("pcr_error_qual", C.c_int32), ("min_base_quality", C.c_int32), ("flags", C.c_uint32), ("initial_log_odds", C.c_double)]
+
+
+class ActivityStats(C.Structure):
+    _fields_ = [("n_loci", C.c_uint64), ("n_elements", C.c_uint64), ("n_active", C.c_uint64), ("n_callable", C.c_uint64),
+                ("n_launches", C.c_uint32), ("ms_elements", C.c_float), ("ms_locus", C.c_float)]
+
+
+ACTIVITY_SYMBOLS = {
+    "mgx_activity_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mgx_activity_destroy": (None, [C.c_void_p]),
+    "mgx_activity_params_defaults": (None, [C.POINTER(ActivityParams)]),
+    "mgx_activity_interval": (C.c_int, [C.c_void_p, C.POINTER(ActivityInput), C.POINTER(ActivityParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_activity_stats": (C.c_int, [C.c_void_p, C.POINTER(ActivityStats)]),
+    "mgx_activity_last_elements": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+}
+SYMBOLS.update(ACTIVITY_SYMBOLS)

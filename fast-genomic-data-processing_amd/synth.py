@@ -566,3 +566,99 @@ def gen_bam_record_bytes(n_bytes, seed, read_len=150, qual_bins=None):
     c += read_len
     a[:, c:c + len(aux)] = np.frombuffer(aux, dtype=np.uint8)
     return a.reshape(-1)[:n_bytes].copy()
+
+
+# ---- active-site detection (include/mgx_activity.h) -------------------------------------------------------------------------------
+def cigar_spans(elements):
+    """(reference span, read length) of BAM-encoded elements"""
+    ref = sum(int(e) >> 4 for e in elements if (int(e) & 15) in (0, 2, 3, 7, 8))
+    read = sum(int(e) >> 4 for e in elements if (int(e) & 15) in (0, 1, 4, 7, 8))
+    return ref, read
+
+
+def pack_activity_reads(interval_start, ref_bases, reads):
+    """The structure-of-arrays input of ActivityEngine.interval.  ``reads``: dicts with start, cigar (text or BAM-encoded elements),
+    bases, quals and optionally flags (0), mate_start (-1), sample (0), act = (start, stop) (default: the read's whole reference
+    span).  The reads are put in the order of act_start, stable, which is the order the reference's read cache holds them in."""
+    rows = []
+    for r in reads:
+        el = cigar_encode(r["cigar"]) if isinstance(r["cigar"], str) else [int(e) for e in r["cigar"]]
+        span, _ = cigar_spans(el)
+        act = r.get("act") or (r["start"], r["start"] + span - 1)
+        b = np.frombuffer(bytes(r["bases"]), dtype=np.uint8) if isinstance(r["bases"], (bytes, bytearray)) else np.asarray(r["bases"], dtype=np.uint8)
+        rows.append((int(act[0]), int(act[1]), int(r["start"]), el, b, np.asarray(r["quals"], dtype=np.uint8), int(r.get("flags", 0)),
+                     int(r.get("mate_start", -1)), int(r.get("sample", 0))))
+    rows.sort(key=lambda t: t[0])
+    off = lambda lens: np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)  # noqa: E731
+    cat = lambda xs, dt: np.concatenate([np.asarray(x, dtype=dt) for x in xs] + [np.zeros(0, dt)])  # noqa: E731
+    return dict(interval_start=int(interval_start), ref_bases=np.frombuffer(bytes(ref_bases), dtype=np.uint8).copy(),
+                act_start=np.array([t[0] for t in rows], np.int32), act_stop=np.array([t[1] for t in rows], np.int32),
+                read_start=np.array([t[2] for t in rows], np.int32), cigar_off=off([len(t[3]) for t in rows]),
+                cigar=cat([t[3] for t in rows], np.uint32), base_off=off([len(t[4]) for t in rows]), bases=cat([t[4] for t in rows], np.uint8),
+                quals=cat([t[5] for t in rows], np.uint8), flags=np.array([t[6] for t in rows], np.uint16),
+                mate_start=np.array([t[7] for t in rows], np.int32), sample=np.array([t[8] for t in rows], np.uint8))
+
+
+def gen_activity_interval(n_reads, n_loci, seed, interval_start=5000, len_range=(30, 151), normal_rate=0.3, n_variants=None):
+    """Reads with insertions, deletions, soft clips and mates over a random reference: ``n_reads`` reads of len_range bases that
+    touch [interval_start, interval_start + n_loci), some starting before it and some ending after it.  ``n_variants`` sites
+    (default n_loci // 150) carry an alternative base in a third of the tumour reads; elsewhere bases differ at a rate of 1/200."""
+    rng = np.random.default_rng(seed)
+    pad = len_range[1] + 40
+    lo = interval_start - pad
+    contig = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=n_loci + 2 * pad)
+    n_variants = n_loci // 150 if n_variants is None else n_variants
+    variant_at = rng.choice(n_loci, size=min(n_variants, n_loci), replace=False) + pad if n_loci else np.zeros(0, np.int64)
+    variant_base = {int(p): int(b) for p, b in zip(variant_at, rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=len(variant_at)))}
+    starts = np.sort(rng.integers(interval_start - len_range[1] // 2, interval_start + max(n_loci, 1), size=n_reads))
+    reads = []
+    for s in starts:
+        s = int(max(s, lo + 5))
+        n = int(rng.integers(len_range[0], len_range[1] + 1))
+        shape = rng.random()
+        el = []
+        lead = int(rng.integers(1, 8)) if shape < 0.08 else 0
+        trail = int(rng.integers(1, 8)) if 0.06 < shape < 0.14 else 0
+        body = n - lead - trail
+        if lead:
+            el.append((lead, "S"))
+        if 0.14 < shape < 0.24 and body > 12:
+            a, k = int(rng.integers(4, body - 6)), int(rng.integers(1, 4))
+            el += [(a, "M"), (k, "I"), (body - a - k, "M")]
+        elif 0.24 < shape < 0.34 and body > 12:
+            a, k = int(rng.integers(4, body - 6)), int(rng.integers(1, 15))
+            el += [(a, "M"), (k, "D"), (body - a, "M")]
+        else:
+            el.append((body, "M"))
+        if trail:
+            el.append((trail, "S"))
+        sample = int(rng.random() < normal_rate)
+        carries = rng.random() < 1 / 3 and sample == 0
+        bases, at = [], s - lo
+        for k, op in el:
+            if op == "M":
+                piece = contig[at:at + k].copy()
+                piece = np.where(rng.random(k) < 1 / 200, rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=k), piece)
+                if carries:
+                    for p in range(at, at + k):
+                        if p in variant_base:
+                            piece[p - at] = variant_base[p]
+                bases.append(piece); at += k
+            elif op == "D":
+                at += k
+            else:
+                bases.append(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=k))
+        span = at - (s - lo)
+        u = rng.random()
+        act = None
+        if u < 0.02:
+            act = (s + 3, s + 2)                                    # an empty window
+        elif u < 0.12 and span > 10:
+            a, b = sorted(int(x) for x in rng.integers(0, span, size=2))
+            act = (s + a, s + b)
+        paired = rng.random() < 0.9
+        flags = (0x1 | (0x2 if rng.random() < 0.85 else 0) | (0x8 if rng.random() < 0.05 else 0)) if paired else 0
+        reads.append(dict(start=s, cigar=cigar_encode("".join("%d%s" % e for e in el)), bases=np.concatenate(bases),
+                          quals=rng.integers(2, 42, size=n), flags=flags, mate_start=s + int(rng.integers(-250, 250)) if paired else -1,
+                          sample=sample, act=act))
+    return pack_activity_reads(interval_start, contig[pad:pad + n_loci].tobytes(), reads)
