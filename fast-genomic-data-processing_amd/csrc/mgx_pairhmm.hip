@@ -571,6 +571,7 @@ int begin_run(Run& r) {
     base.gcp = b->dev(b->lay.seq[kSeqGcp]); base.hap_bases = b->dev(b->lay.seq[kSeqHap]);
     base.out_log10 = b->dev<double>(b->lay.o_out); base.used_f64 = b->dev(b->lay.o_used);
     base.nhap_list = b->dev<uint32_t>(b->lay.nlist); base.nhap_count = b->counters() + kNhapCount;
+    base.form_count = b->counters() + kFormDeferCount;
     base.log10_initial_f = c->log10_initial_f;
     base.log10_initial_d = c->log10_initial_d;
     return 0;
@@ -794,10 +795,13 @@ int mgx_pairhmm_batch_stats(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, mgx_pairhm
     st.n_launches_f64 = (uint32_t)b->bins.size();
     st.n_rerun_f64 = 0;
     st.n_nhap_f32 = 0;
+    st.n_form_deferred_f32 = 0;
     if (b->ran && b->n_pairs) {
         std::vector<uint32_t> cnt(kCounters);
         HIP_TRY(hipMemcpy(cnt.data(), b->counters(), kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < b->bins.size(); ++k) st.n_nhap_f32 += cnt[kNhapCount + k];
+        st.n_form_deferred_f32 = cnt[kFormDeferCount];      // on the same lists, without an N
+        st.n_nhap_f32 -= st.n_form_deferred_f32;
         for (size_t k = 0; k < b->bins.size(); ++k) st.n_rerun_f64 += force_f64 ? b->bins[k].job_count : cnt[k];
         if (!force_f64) st.n_rerun_f64 += cnt[kSharedCount];          // the narrow classes' shared list
         st.n_exact = cnt[kExactCount];

@@ -33,7 +33,8 @@
 //     double processes that list (IntelPairHmm.cc:338-350).
 //   * The cell is not computed in the reference's 8-operation order but in an algebraically equal
 //     one: 6 operations in fp32 (X scaled by pGAPM of the row below, Y carried divided by its own
-//     row's pMY), 7 in fp64; see the comment above `use_plain`.
+//     row's pMY), 7 in fp64, and 5 in the first fp32 launch of the classes of up to 16 lanes (every row rescaled once more;
+//     what that form cannot take goes to the N-haplotype list below); see the comment above `use_plain`.
 
 #include <type_traits>
 
@@ -66,6 +67,7 @@ struct KernelArgs {
     uint32_t* rerun_count;      // fp64: jobs whose result is in reach of the flush-to-zero threshold -> exact re-run
     uint32_t* nhap_list;        // fp32 with the four-code table: jobs whose haplotype holds an N -> the five-code fp32
     uint32_t* nhap_count;       // launch of the same class (no result is written for them here)
+    uint32_t* form_count;       // fp32 with the five-operation cell: how many jobs of those lists hold no N but were deferred for the cell form
     uint32_t lds_stride;        // bytes of LDS per group (>= max H of the bin + 2)
     void* strip_scratch;        // strip-mined class only: [workgroups][2][3][strip_stride] boundary rows (M, X, Y per column)
     uint32_t strip_stride;
@@ -149,7 +151,8 @@ template <> struct Prec<double> {
 
 // LDS emission table (fp32 kernels): etab[(s/2)][code][lane][s&1] holds e(row s of that lane,
 // haplotype code), so the per-cell compare+select becomes one conflict-free ds_read_b64 per
-// two rows (bank = lane) whose address is "code*512 + lane*8" plus an immediate offset.
+// two rows (bank = lane) whose address is "code*512 + lane*8" plus an immediate offset.  (With the five-operation cell the
+// entries are E = e * pMM of the row below, rounded once here; same layout, same size.)
 // CODES (a template parameter of the body) is the number of code columns.  5: A C T G N  (PAD reads as N: harmless).
 // 4: no column for N -- 8 KB instead of 10 KB per wavefront of eight rows per lane, so that the register budget and not
 // LDS decides how many wavefronts a CU holds (16 instead of 14).  The first fp32 launch of every class but the
@@ -169,13 +172,16 @@ template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return ((RPL
 // on its own.  Flush-to-zero is on in the reference (IntelPairHmm.cc:230) and here, and a result within a few
 // hundred orders of magnitude of 2^-1022 depends on WHICH intermediate products were flushed: the fused
 // multiply-adds and the scaled form of the fast tiers flush at other points than the reference does.
-template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false, int CODES = kMaxCodes>
+// FIVE (fp32, four-code table, groups of up to 16 lanes -- reads of at most 192 bases): the five-operation cell is the
+// only form of the sweep (see the comment above `use_plain`); a test case it cannot take joins the N-haplotype list.
+template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false, int CODES = kMaxCodes, bool FIVE = false>
 __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem, const uint32_t block, const uint32_t n_blocks) {
     constexpr int GPW = 64 / G;                   // groups per wavefront
     constexpr bool kETab = (sizeof(T) == 4);      // fp32: emission table in LDS; fp64: compare+select
     constexpr int kNumCodes = CODES;
     static_assert(CODES == 4 || CODES == kMaxCodes, "four or five code columns");
     static_assert(kETab || CODES == kMaxCodes, "fp64 has no table: the N code is compared");
+    static_assert(!FIVE || (kETab && CODES == 4 && G <= 16 && !STRIP && !EXACT), "the five-operation cell: first fp32 launch of the classes of up to 16 lanes");
     constexpr bool kSix = (sizeof(T) == 4) && !EXACT;   // fp32: the 6-operation cell; fp64: the scaled 7-operation cell (see sweep)
     constexpr int RP2 = (RPL + 1) / 2;
     constexpr int S = lane_stride<G>();           // lane stride of a group inside its DPP row
@@ -246,16 +252,16 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
             }
         }
         bool group_hap_n = false;
-        if constexpr (kETab && kNumCodes == 4) {
-            uint64_t gmask;                                        // the lanes of this lane's group
-            if constexpr (G == 64) gmask = ~0ull;
-            else if constexpr (G == 16) gmask = 0xFFFFull << (lane & 48);
-            else gmask = (uint64_t)((G == 8 ? 0x5555u : 0x1111u) << ((lane & 15) % S)) << (lane & 48);
-            group_hap_n = (__ballot((int)hap_n) & gmask) != 0;
-        }
+        uint64_t gmask = ~0ull;                                    // the lanes of this lane's group
+        if constexpr (G == 16) gmask = 0xFFFFull << (lane & 48);
+        else if constexpr (G < 16) gmask = (uint64_t)((G == 8 ? 0x5555u : 0x1111u) << ((lane & 15) % S)) << (lane & 48);
+        if constexpr (kETab && kNumCodes == 4) group_hap_n = (__ballot((int)hap_n) & gmask) != 0;
 
         T sumM = 0, sumX = 0;
         bool zero_gap = false;                            // some row has pGAPM == 0 (gcp byte 0)
+        bool zero_mm = false;                             // (FIVE) some row has pMM == 0
+        bool defer = group_hap_n;                         // the test case is left to the class's second launch
+        T res_scale = 1;                                  // (FIVE) A' of this lane's bottom row: the last lane's turns sum x into sum X
         if constexpr (STRIP) {                            // every strip of a pair must take the same algebraic form
             for (int rr = lane; rr < R; rr += 64) zero_gap |= (a.gcp[job.read_off + (uint64_t)rr] & 127) == 0;
         }
@@ -301,6 +307,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     k2[s] = ph2pr[qi];
                     k4[s] = ph2pr[qd];
                     zero_gap |= (qc == 0);
+                    if constexpr (FIVE) zero_mm |= (k0[s] == (T)0);
                     const T distm = ph2pr[qq];
                     eM[s] = (T)1.0 - distm;
                     const int code = base_code(a.bases[o]);
@@ -309,6 +316,46 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     rb[s] = code;
                 }
             }
+        }
+        // FIVE, the static rule: the cell divides by every row's pMM and pGAPM, so a test case with a zero among them is left
+        // to the second launch -- per test case, like a haplotype with an N
+        if constexpr (FIVE) {
+            defer |= (__ballot((int)(zero_gap | zero_mm)) & gmask) != 0;
+            // The coefficients of the five-operation cell (see the comment above `use_plain`), per row:
+            //   k1 = a = A' of the row above, k2 = B', k3 = q', k4 = pYY, and the emissions times s = pMM of the row below.
+            // Rows below / above the lane's own come from the neighbour lanes; read row R has g' = s = 1, and above read
+            // row 0 lie A' = 0 and pMY = 1.  Every product and quotient is rounded on its own, in this order, which
+            // tools/cell_emulator.cpp (form 4) repeats.
+            const bool last_lane = j == nl - 1;
+            const T g_next_lane = shr1_down<G>(k1[0]), mm_next_lane = shr1_down<G>(k0[0]);
+            T rcp[RPL], Ap[RPL], gr[RPL];
+#pragma unroll
+            for (int s = 0; s < RPL; ++s) {
+                const T gb = (s + 1 < RPL) ? k1[s + 1] : (last_lane ? (T)1.0 : g_next_lane);
+                const T sb = (s + 1 < RPL) ? k0[s + 1] : (last_lane ? (T)1.0 : mm_next_lane);
+                rcp[s] = (T)1.0 / k0[s];
+                Ap[s] = clone[s] ? (T)0 : (gb * k2[s]) * rcp[s];           // A' = g' pMX / pMM
+                gr[s] = gb * ratio[s];                                    // g' pXX / g
+                eM[s] *= sb; eX[s] *= sb;                                 // E = e s
+            }
+            const T my_up = shr1<G>((T)1.0, clone[RPL - 1] ? (T)1.0 : k4[RPL - 1]);
+            const T a_up = shr1<G>((T)0, Ap[RPL - 1]);
+            T qv[RPL], av[RPL], bv[RPL];
+#pragma unroll
+            for (int s = 0; s < RPL; ++s) {
+                const int rho = j * RPL + s - top_clones;
+                const T my_above = s ? (clone[s - 1] ? (T)1.0 : k4[s - 1]) : my_up;
+                av[s] = s ? Ap[s - 1] : a_up;
+                qv[s] = rho == 0 ? k1[s] : (k1[s] * my_above) * rcp[s];    // q' = g pMY' / pMM; read row 0: g (y of the boundary row is unscaled)
+                bv[s] = (gr[s] * av[s]) / Ap[s];                          // B' = g' (pXX / g) A'' / A'  (A'': of the row above)
+            }
+#pragma unroll
+            for (int s = 0; s < RPL; ++s) {
+                k4[s] = k3[s];                                            // pYY
+                k1[s] = av[s]; k2[s] = bv[s]; k3[s] = qv[s];
+                if (clone[s]) { k1[s] = 0; k2[s] = 0; k3[s] = 0; k4[s] = 1; }
+            }
+            res_scale = Ap[RPL - 1];
         }
         if constexpr (kETab) {
             float* et = reinterpret_cast<float*>(etab) + lane * 2;
@@ -324,7 +371,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         // ---- anti-diagonal sweep
         // (a group that leaves its test case to the five-code launch takes no steps of its own: like a group without a job
         // it follows its neighbours, and a wavefront made of such groups only skips the sweep)
-        const bool swept = live && !group_hap_n;
+        const bool swept = live && !defer;
         const int nsteps_g = swept ? (H + nl - 1) : 0;
         int nmax = nsteps_g, nmin = swept ? nsteps_g : 0x7fffffff;
         if constexpr (GPW > 1) {
@@ -382,13 +429,29 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         //  above lives (this lane, the lane above, the previous strip).
         //  B divides by g, so a wavefront that sees a row with pGAPM == 0 (gap-continuation byte 0)
         //  takes the plain form.
+        //  five (fp32, FIVE), 5 ops per cell: each row rescaled once more, m = s*M, x = X^ / A', yb = s*y with s = pMM of
+        //  the row below (1 for read row R) and A' = g'*pMX / pMM of the row itself:
+        //      m  = fma(q', yb2, fma(a, x2, m2)) * E     q' = g * pMY' / pMM,  a = A' of the row above,  E = e * s
+        //      x  = fma(x1, B', m1)                      B' = g' * (pXX / g) * a / A'
+        //      yb = fma(ybl, pYY, ml)
+        //  Above read row 0: a = B' = 0 and q' = g (the boundary row keeps y = INITIAL/H unscaled).  Read row R has
+        //  s = g' = 1, so sum M is sum m and sum X is A' * sum x: one multiply per test case.  E is rounded once, when the
+        //  table is built: the match-to-match path now carries one rounded product per row, which is why the form stops
+        //  at the 192 rows of the 16-lane classes (with two such products, form 2 of the emulator, 1000-row reads reach
+        //  1.5e-5; with one, reads of up to 192 rows stay at the 6-operation cell's 3.8e-6 / 7.6e-6:
+        //  profiles/pairhmm_fiveop_emulation.txt).  The form divides by pMM and, through A', by g': a test case with a
+        //  zero among them is deferred before the sweep (`defer`), and x is as large as M, not as X, so rows whose
+        //  insertion qualities differ by tens of dB can overflow fp32: every term is non-negative, an overflow reaches
+        //  the last row's sums as inf or NaN, and such a result is deferred after the sweep.  Both per test case, to the
+        //  class's N-haplotype list, which the second launch computes in the forms above.
         const bool use_plain = EXACT || __any((int)zero_gap) != 0;
-        constexpr int kPlain = 0, kScaled = 1, kSixOp = 2;
+        constexpr int kPlain = 0, kScaled = 1, kSixOp = 2, kFiveOp = 3;
 
         auto sweep = [&](auto form_tag) {
             constexpr int FORM = decltype(form_tag)::value;
             constexpr bool SC = FORM == kScaled;
             constexpr bool SIX = FORM == kSixOp;
+            constexpr bool FIV = FORM == kFiveOp;
             T y_above = init_y;                     // what the group's lane 0 sees above its top row
             if constexpr (SC || SIX) {
                 // g of the row below each row: next row in this lane, or the next lane's top row
@@ -470,6 +533,20 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     for (int s = 1; s < RPL; ++s) px[s] = fma_(px[s - 1], k2[s], pm[s - 1] * k1[s]);
 #pragma unroll
                     for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
+                } else if constexpr (FIV) {
+                    // in place like the 6-operation cell: m and yb bottom row first, then x top down from the new m
+#pragma unroll
+                    for (int s = RPL - 1; s >= 0; --s) {
+                        const T t = s ? fma_(k3[s], py[s - 1], fma_(k1[s], px[s - 1], pm[s - 1]))
+                                      : fma_(k3[0], o2Y, fma_(k1[0], o2X, o2M));
+                        py[s] = fma_(py[s], k4[s], pm[s]);
+                        pm[s] = t * ec[s];
+                    }
+                    px[0] = fma_(o1X, k2[0], o1M);
+#pragma unroll
+                    for (int s = 1; s < RPL; ++s) px[s] = fma_(px[s - 1], k2[s], pm[s - 1]);
+#pragma unroll
+                    for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
                 } else if constexpr (SC) {
                     Mn[0] = (fma_(o2M, k0[0], o2X) + o2Y) * ec[0];
                     Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
@@ -549,7 +626,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 load_e(hn, e);
             }
         };
-        if constexpr (EXACT) sweep(std::integral_constant<int, kPlain>{});
+        if constexpr (FIVE) sweep(std::integral_constant<int, kFiveOp>{});
+        else if constexpr (EXACT) sweep(std::integral_constant<int, kPlain>{});
         else if (use_plain) sweep(std::integral_constant<int, kPlain>{});
         else if constexpr (kSix) sweep(std::integral_constant<int, kSixOp>{});
         else sweep(std::integral_constant<int, kScaled>{});
@@ -557,11 +635,13 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 
         // ---- result (IntelPairHmm.cc:338-350)
         if (live && j == nl - 1) {
-            const T res = sumM + sumX;
+            const T res = FIVE ? sumM + res_scale * sumX : sumM + sumX;
             if constexpr (sizeof(T) == 4) {
-                if (group_hap_n) {
+                // (FIVE) the dynamic rule: a result that is not finite -- an overflow in any cell -- is left to the second launch
+                if (defer || (FIVE && !(res <= 3.402823466e+38f))) {
                     const uint32_t k = atomicAdd(a.nhap_count, 1u);
                     a.nhap_list[k] = job_idx;
+                    if constexpr (FIVE) { if (!group_hap_n) atomicAdd(a.form_count, 1u); }
                 } else if (res < 1e-28f) {
                     const uint32_t k = atomicAdd(a.rerun_count, 1u);
                     a.rerun_list[k] = job_idx;
@@ -590,13 +670,13 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 // changes the allocator's choices and parks 16-18 values (236 MB of scratch writes per 1 M test cases; same duration).
 // (Holding 11 rows per lane -- 171 registers -- to the 168 of 3 wavefronts spills 19: not done.)  10 rows per lane (the
 // 151-base reads) need 169 with the 6-operation cell: held to the 168 of 3 wavefronts.
-template <typename T, int G, int RPL, int CODES = kMaxCodes>
+template <typename T, int G, int RPL, int CODES = kMaxCodes, bool FIVE = false>
 #ifndef MGX_HMM_MINWAVES_8
 #define MGX_HMM_MINWAVES_8 4
 #endif
 __global__ __launch_bounds__(256, (sizeof(T) == 4 && RPL == 7) ? MGX_HMM_MINWAVES_8 : (sizeof(T) == 4 && RPL == 10) ? 3 : 1) void pairhmm_fwd(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    pairhmm_body<T, G, RPL, false, false, CODES>(a, smem, blockIdx.x, gridDim.x);
+    pairhmm_body<T, G, RPL, false, false, CODES, FIVE>(a, smem, blockIdx.x, gridDim.x);
 }
 
 // the strip-mined class: reads of more than 1024 bases, one test case per wavefront, 64 lanes x 16 rows per strip
@@ -636,7 +716,7 @@ __device__ __forceinline__ void pairhmm_multi_body(const MultiArgs& m, uint8_t* 
     a.nhap_list += m.job_first[k]; a.nhap_count += m.bin[k];          // every class keeps its own N-haplotype list
     const uint32_t blk = blockIdx.x - m.block_first[k], nblk = m.block_first[k + 1] - m.block_first[k];
     const int code = (int)m.G[k] * 16 + (int)m.RPL[k];
-#define MGX_MCASE(g, r) case (g) * 16 + (r): pairhmm_body<float, g, r, false, false, 4>(a, smem, blk, nblk); break;
+#define MGX_MCASE(g, r) case (g) * 16 + (r): pairhmm_body<float, g, r, false, false, 4, true>(a, smem, blk, nblk); break;
     if constexpr (GSET == 0) {
         switch (code) {
             MGX_MCASE(16, 1) MGX_MCASE(16, 2) MGX_MCASE(16, 3) MGX_MCASE(16, 4) MGX_MCASE(16, 5) MGX_MCASE(16, 6) MGX_MCASE(16, 7) MGX_MCASE(16, 8)
@@ -831,9 +911,10 @@ __global__ __launch_bounds__(256) void pairhmm_best_allele_rows(const double* __
 
 using KernelFn = void (*)(KernelArgs);
 
+// (four code columns: the first fp32 launch of a class -- with the five-operation cell in the classes of up to 16 lanes)
 template <typename T, int CODES = kMaxCodes>
 KernelFn pick_kernel(int G, int RPL) {
-#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r, CODES>;
+#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r, CODES, (CODES == 4 && g <= 16)>;
     MGX_CASE(4, 1) MGX_CASE(4, 2) MGX_CASE(4, 3) MGX_CASE(4, 4) MGX_CASE(4, 5) MGX_CASE(4, 6) MGX_CASE(4, 7) MGX_CASE(4, 8)
     MGX_CASE(8, 1) MGX_CASE(8, 2) MGX_CASE(8, 3) MGX_CASE(8, 4) MGX_CASE(8, 5) MGX_CASE(8, 6) MGX_CASE(8, 7) MGX_CASE(8, 8)
     MGX_CASE(16, 1) MGX_CASE(16, 2) MGX_CASE(16, 3) MGX_CASE(16, 4)

@@ -131,9 +131,10 @@ inline void bin_shape(int k, Bin* b) {
 }
 // device counters of a batch: [0, kBins) every class's own fp64 re-run list, kExactCount the exact tier's list (the
 // second half of the re-run list), kSharedCount the narrow classes' shared fp64 list, [kNhapCount, kNhapCount + kBins)
-// every class's N-haplotype list
-constexpr int kExactCount = 62, kSharedCount = 63, kNhapCount = 64, kCounters = 128;
-static_assert(kBins <= kExactCount && kNhapCount + kBins <= kCounters, "counter slots");
+// every class's N-haplotype list, kFormDeferCount how many entries of those lists (all classes) hold no N: test cases the
+// five-operation cell of the first launch deferred
+constexpr int kFormDeferCount = 61, kExactCount = 62, kSharedCount = 63, kNhapCount = 64, kCounters = 128;
+static_assert(kBins <= kFormDeferCount && kNhapCount + kBins <= kCounters, "counter slots");
 
 // launch geometry of a bin once job_count and max_h are known; `block` is 64, 128 or 256 threads (MGX_PAIRHMM_BLOCK)
 inline int finalize_bin(Bin& bin, int n_cu, uint32_t block) {

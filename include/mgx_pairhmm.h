@@ -111,6 +111,9 @@ typedef struct mgx_pairhmm_stats {
                                 * that were computed a third time in the reference's exact operation order (last run) */
     uint64_t n_nhap_f32;       /* test cases whose haplotype holds an N: computed by the five-code fp32 launch of their class
                                 * (last run; the strip-mined class has five codes throughout and is not counted) */
+    uint64_t n_form_deferred_f32; /* test cases without an N in the haplotype that the five-operation cell of the first fp32 launch
+                                * (reads of at most 192 bases) left to that second launch: a read row with matchToMatchProb 0 or a
+                                * gap-continuation byte 0, or a result that was not finite (last run) */
 } mgx_pairhmm_stats_t;
 
 const char* mgx_last_error(void);

@@ -1,7 +1,10 @@
 """CPU numerics check of the fp32 PairHMM cells (tools/cell_emulator.cpp) against the oracle, over the distributions the GPU
 tests use: max |log10 difference| of the scaled 7-operation cell (before), the 6-operation cell with E = e*pGAPM and
-p = pMM/pGAPM (A, not used) and the 6-operation cell of the kernels (B) over the test cases
+p = pMM/pGAPM (A, not used), the 6-operation cell of the kernels (B) and the 5-operation cell of the first launch of the
+classes of up to 16 lanes with its two deferral rules (5-op) over the test cases
 that both the emulation and the oracle keep in fp32, and how often the float-first decision (result < 1e-28f) differs.
+For the 5-operation cell also: how many test cases the static and the dynamic rule defer, how many keep the 6-operation
+cell because of an N in the haplotype or their length, and the largest |log10 difference| to the 6-operation cell.
 usage: python tools/dev_cell_emulate.py [--quick]"""
 import ctypes as C
 import importlib
@@ -28,7 +31,24 @@ def build():
                            "-I", CSRC, "-o", SO, os.path.join(ROOT, "tools", "cell_emulator.cpp"), os.path.join(CSRC, "mgx_tables.cpp")])
     lib = C.CDLL(SO)
     lib.cell_emulate_batch.restype = None
+    lib.cell_emulate_paths.restype = None
+    lib.cell_emulate_deferrals.restype = None
     return lib
+
+
+def paths(lib, n):
+    """Which way every test case of the last form-4 batch went (cell_emulator.cpp: 0 five-operation cell, 1 static deferral,
+    2 dynamic deferral, 3 haplotype with an N, 4 read too long)."""
+    out = np.empty(n, dtype=np.uint8)
+    lib.cell_emulate_paths(C.c_int(n), C.c_void_p(out.ctypes.data))
+    return out
+
+
+def deferrals(lib):
+    """(static, dynamic) deferral counts of the last form-4 batch."""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    lib.cell_emulate_deferrals(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
 
 
 def emulate(lib, form, d):
@@ -61,6 +81,8 @@ def cases(quick):
     for rr, hr, n in [((1, 128), (1, 256), 20000), ((100, 128), (200, 256), 8000), ((129, 512), (10, 600), 1500),
                       ((1, 16), (1, 40), 5000), ((129, 192), (100, 400), 6000), ((513, 1024), (300, 1200), 300)]:
         yield f"ragged sweep R{rr} H{hr}", synth.gen_pairhmm_pairs(n // k, 0x5EED0002 ^ n, r_range=rr, h_range=hr, hap_n_rate=0.01), None
+    # the ragged sweeps above hold an N in most haplotypes (1 % of the bases): those test cases keep the 6-operation cell
+    yield "N-free sweep R(1, 192) H(1, 300)", synth.gen_pairhmm_pairs(16000 // k, 0x5EED0005, r_range=(1, 192), h_range=(1, 300)), None
     for name in ("pairhmm_cfg1.npz", "pairhmm_edge.npz"):
         g = load_golden(name)
         yield f"golden {name}", g, g["expected"]
@@ -76,19 +98,25 @@ def main():
     quick = "--quick" in sys.argv
     lib = build()
     oracle = PairHMMOracle(_ensure_oracle())
-    print(f"{'data':36s} {'n':>6s} | {'7-op max|d|':>12s} {'flips':>5s} | {'6-op A max|d|':>12s} {'flips':>5s} | {'6-op B max|d|':>12s} {'flips':>5s}")
+    print(f"{'data':36s} {'n':>6s} | {'7-op max|d|':>12s} {'flips':>5s} | {'6-op A max|d|':>12s} {'flips':>5s} | {'6-op B max|d|':>12s} {'flips':>5s}"
+          f" | {'5-op max|d|':>12s} {'flips':>5s} {'static':>6s} {'dynam.':>6s} {'N/long':>6s} {'vs 6-op B':>10s}")
     for name, d, want in cases(quick):
         w, wused = oracle.batch(d)
         want = w if want is None else want
         row = [name[:36], len(want)]
         outs = {}
-        for form in (1, 2, 3):
+        for form in (1, 2, 3, 4):
             got, f64 = emulate(lib, form, d)
             keep = ~f64 & ~wused.astype(bool)
             err = float(np.abs(got[keep] - want[keep]).max()) if keep.any() else 0.0
             row += [err, int((f64 != wused.astype(bool)).sum())]
             outs[form] = (got, keep)
-        print(f"{row[0]:36s} {row[1]:6d} | {row[2]:12.3e} {row[3]:5d} | {row[4]:12.3e} {row[5]:5d} | {row[6]:12.3e} {row[7]:5d}", flush=True)
+        n_static, n_dynamic = deferrals(lib)
+        way = paths(lib, len(want))
+        both = outs[3][1] & outs[4][1]
+        vs6 = float(np.abs(outs[4][0][both] - outs[3][0][both]).max()) if both.any() else 0.0
+        print(f"{row[0]:36s} {row[1]:6d} | {row[2]:12.3e} {row[3]:5d} | {row[4]:12.3e} {row[5]:5d} | {row[6]:12.3e} {row[7]:5d}"
+              f" | {row[8]:12.3e} {row[9]:5d} {n_static:6d} {n_dynamic:6d} {int((way >= 3).sum()):6d} {vs6:10.3e}", flush=True)
 
 
 if __name__ == "__main__":
