@@ -39,11 +39,13 @@
 #include <type_traits>
 
 #include "best_allele_rule.h"
+#include "pairhmm_etab.h"      // the emission table's layout in LDS
 #include "pairhmm_plan.h"      // Job, SeqRef, RegionRef, kMaxCodes, kMultiBins: what the host writes and these kernels read
 
 namespace {
 
 using namespace mgx_hmm_plan;
+namespace etab = mgx_hmm_etab;
 
 struct KernelArgs {
     const Job* jobs;            // jobs of the batch
@@ -149,10 +151,14 @@ template <> struct Prec<double> {
     static __device__ __forceinline__ double initial() { return 0x1p1020; }  // Context.h:142
 };
 
-// LDS emission table (fp32 kernels): etab[(s/2)][code][lane][s&1] holds e(row s of that lane,
-// haplotype code), so the per-cell compare+select becomes one conflict-free ds_read_b64 per
-// two rows (bank = lane) whose address is "code*512 + lane*8" plus an immediate offset.  (With the five-operation cell the
-// entries are E = e * pMM of the row below, rounded once here; same layout, same size.)
+// LDS emission table (fp32 kernels): holds e(row s of a lane, haplotype code) for every row, code and lane, so the per-cell
+// compare+select becomes one conflict-free LDS read per four rows in the classes of 4, 8, 12 and 16 rows per lane
+// (ds_read_b128 from a quad table [code][lane][4 rows], address "code*1024 + lane*16" plus an immediate offset) and per
+// two rows in the others (ds_read_b64 from a pair table [code][lane][2 rows], "code*512 + lane*8").  pairhmm_etab.h is
+// the layout: which class has which tables, their offsets, and why 16 bytes at a time (two 8-byte reads a multiple of
+// 512 bytes apart become one ds_read2st64_b64, which takes the LDS pipe twice as long as a ds_read_b128).  Both layouts
+// take ceil(RPL / 2) * CODES * 512 bytes per wavefront, which is what the host books (pairhmm_plan.h, lds_bytes).  (With
+// the five-operation cell the entries are E = e * pMM of the row below, rounded once here; same layout, same size.)
 // CODES (a template parameter of the body) is the number of code columns.  5: A C T G N  (PAD reads as N: harmless).
 // 4: no column for N -- 8 KB instead of 10 KB per wavefront of eight rows per lane, so that the register budget and not
 // LDS decides how many wavefronts a CU holds (16 instead of 14).  The first fp32 launch of every class but the
@@ -160,7 +166,7 @@ template <> struct Prec<double> {
 // the class's N-haplotype list, which the five-column fp32 instantiation of the same class then works through (per
 // test case, never per wavefront: a value does not depend on the batch it is in, nor on which launch computed it --
 // both read the same table entries for A C T G).  fp64 has no table; its CODES stays 5.
-template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return ((RPL + 1) / 2) * CODES * 64 * 8; }
+template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return etab::bytes_per_wave(RPL, CODES); }
 
 // The recurrence for the jobs of ONE class (G, RPL); `block` / `n_blocks` are the workgroup's index and count among
 // the workgroups working on this class (the whole grid for a single-class launch).
@@ -183,7 +189,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
     static_assert(kETab || CODES == kMaxCodes, "fp64 has no table: the N code is compared");
     static_assert(!FIVE || (kETab && CODES == 4 && G <= 16 && !STRIP && !EXACT), "the five-operation cell: first fp32 launch of the classes of up to 16 lanes");
     constexpr bool kSix = (sizeof(T) == 4) && !EXACT;   // fp32: the 6-operation cell; fp64: the scaled 7-operation cell (see sweep)
-    constexpr int RP2 = (RPL + 1) / 2;
+    using ETab = etab::Layout<RPL, CODES, kETab && etab::quad_layout(G, RPL, CODES)>;
     constexpr int S = lane_stride<G>();           // lane stride of a group inside its DPP row
     const int gpb = (int)blockDim.x / G;          // groups per block
     const int tid = (int)threadIdx.x;
@@ -194,7 +200,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
     const int grp = wave * GPW + (G < 16 ? (lane >> 4) * S + (lane & 15) % S : lane / G);
     // LDS: [waves][etab] then [groups][hap codes]
     const int n_waves = (int)blockDim.x >> 6;
-    uint8_t* etab = smem + (kETab ? (size_t)wave * etab_bytes_per_wave<RPL, CODES>() : 0);
+    uint8_t* etab_base = smem + (kETab ? (size_t)wave * etab_bytes_per_wave<RPL, CODES>() : 0);
     uint8_t* hapbuf = smem + (kETab ? (size_t)n_waves * etab_bytes_per_wave<RPL, CODES>() : 0) +
                       (size_t)grp * a.lds_stride;
     const T* __restrict__ ph2pr = (const T*)a.ph2pr;
@@ -358,13 +364,23 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
             res_scale = Ap[RPL - 1];
         }
         if constexpr (kETab) {
-            float* et = reinterpret_cast<float*>(etab) + lane * 2;
+            // one store per read of the column loop (pairhmm_etab.h) and code
+            auto entry = [&](int s, int code) { return (code == rb[s] || code == kCodeN) ? eM[s] : eX[s]; };
 #pragma unroll
-            for (int s = 0; s < RPL; ++s)
+            for (int k = 0; k < ETab::kReads; ++k) {
+                const etab::Read rd = etab::read_of(RPL, CODES, ETab::kQuadLayout, k);
+                const int s = rd.row0;
 #pragma unroll
-                for (int code = 0; code < kNumCodes; ++code)
-                    et[((s >> 1) * kNumCodes + code) * 128 + (s & 1)] =
-                        (code == rb[s] || code == kCodeN) ? eM[s] : eX[s];
+                for (int code = 0; code < kNumCodes; ++code) {
+                    uint8_t* q = etab_base + rd.offset + lane * rd.bytes + code * rd.code_stride;
+                    if (rd.bytes == etab::kQuadBytes)
+                        *reinterpret_cast<float4*>(q) = make_float4(entry(s, code), entry(s + 1, code), entry(s + 2, code), entry(s + 3, code));
+                    else if (s + 1 < RPL)
+                        *reinterpret_cast<float2*>(q) = make_float2(entry(s, code), entry(s + 1, code));
+                    else
+                        *reinterpret_cast<float*>(q) = entry(s, code);      // the last, single row of an odd RPL
+                }
+            }
         }
         __syncthreads();                          // hapbuf / etab visible
 
@@ -390,16 +406,25 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         if (nmin > nmax) nmin = nmax;
 
         const uint8_t* hp_lane = hapbuf + (G - j);  // hp_lane[d] = code of this lane's column at step d
-        const uint8_t* et_lane = etab + lane * 8;
+        // this lane's entry of code 0 at offset 0 of a quad table and of a pair table
+        const uint8_t* et_quad = etab_base + lane * etab::kQuadBytes;
+        const uint8_t* et_pair = etab_base + lane * etab::kPairBytes;
 
         auto load_e = [&](int h, T (&dst)[RPL]) {
             if constexpr (kETab) {
-                const uint8_t* p = et_lane + (h << 9);
+                // the column's read list: one ds_read_b128 per quad table, one ds_read_b64 (b32: a single row) per pair table
 #pragma unroll
-                for (int s2 = 0; s2 < RP2; ++s2) {
-                    const float2 v = *reinterpret_cast<const float2*>(p + s2 * kNumCodes * 512);
-                    dst[2 * s2] = v.x;
-                    if (2 * s2 + 1 < RPL) dst[2 * s2 + 1] = v.y;
+                for (int k = 0; k < ETab::kReads; ++k) {
+                    const etab::Read rd = etab::read_of(RPL, CODES, ETab::kQuadLayout, k);
+                    const int s = rd.row0;
+                    if (rd.bytes == etab::kQuadBytes) {
+                        const float4 v = *reinterpret_cast<const float4*>(et_quad + h * rd.code_stride + rd.offset);
+                        dst[s] = v.x; dst[s + 1] = v.y; dst[s + 2] = v.z; dst[s + 3] = v.w;
+                    } else {
+                        const float2 v = *reinterpret_cast<const float2*>(et_pair + h * rd.code_stride + rd.offset);
+                        dst[s] = v.x;
+                        if (s + 1 < RPL) dst[s + 1] = v.y;
+                    }
                 }
             } else {
                 const bool hN = (h == kCodeN);
