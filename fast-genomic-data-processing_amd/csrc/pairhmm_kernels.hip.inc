@@ -34,11 +34,14 @@
 //   * The cell is not computed in the reference's 8-operation order but in an algebraically equal
 //     one: 6 operations in fp32 (X scaled by pGAPM of the row below, Y carried divided by its own
 //     row's pMY), 7 in fp64, and 5 in the first fp32 launch of the classes of up to 16 lanes (every row rescaled once more;
-//     what that form cannot take goes to the N-haplotype list below); see the comment above `use_plain`.
+//     what that form cannot take goes to the N-haplotype list below).  pairhmm_cell.h states every form, its per-row
+//     coefficients and the rules around them once, with the algebra; this file and the host emulation
+//     (tools/cell_emulator.cpp) both compute with its functions, so the two round alike.
 
 #include <type_traits>
 
 #include "best_allele_rule.h"
+#include "pairhmm_cell.h"      // the cell: model values, forms, coefficients, deferral rules, result and thresholds
 #include "pairhmm_etab.h"      // the emission table's layout in LDS
 #include "pairhmm_plan.h"      // Job, SeqRef, RegionRef, kMaxCodes, kMultiBins: what the host writes and these kernels read
 
@@ -46,6 +49,10 @@ namespace {
 
 using namespace mgx_hmm_plan;
 namespace etab = mgx_hmm_etab;
+namespace cell = mgx_hmm_cell;
+using cell::base_code;
+using cell::kCodeN;
+using Ar = cell::Bare;         // the arithmetic the cell functions take: the bare operations, flushed by the compile flags
 
 struct KernelArgs {
     const Job* jobs;            // jobs of the batch
@@ -77,19 +84,7 @@ struct KernelArgs {
     double log10_initial_d;
 };
 
-constexpr double kExactBelow = 1e-280;     // fp64 results below this go to the exact tier (2^-1022 ~ 2.2e-308)
-constexpr int kCodeN = 4;
 constexpr int kCodePad = 7;
-
-__device__ __forceinline__ int base_code(int b) {
-    // pairhmm_common.h:75-81 -- A=0 C=1 T=2 G=3 N=4, anything else 0
-    int c = 0;
-    c = (b == 'C') ? 1 : c;
-    c = (b == 'T') ? 2 : c;
-    c = (b == 'G') ? 3 : c;
-    c = (b == 'N') ? kCodeN : c;
-    return c;
-}
 
 // base_code() of four bytes at once.  (b >> 1) & 7 is distinct for A C T G N (0 1 2 3 7), so two
 // byte-permute lookups give the candidate code and the ASCII value it stands for; a byte that is not
@@ -140,17 +135,6 @@ __device__ __forceinline__ T shr1_down(T v) {
     return __shfl(v, src, 64);
 }
 
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-template <typename T> struct Prec;
-template <> struct Prec<float> {
-    static __device__ __forceinline__ float initial() { return 0x1p120f; }   // Context.h:183
-};
-template <> struct Prec<double> {
-    static __device__ __forceinline__ double initial() { return 0x1p1020; }  // Context.h:142
-};
-
 // LDS emission table (fp32 kernels): holds e(row s of a lane, haplotype code) for every row, code and lane, so the per-cell
 // compare+select becomes one conflict-free LDS read per four rows in the classes of 4, 8, 12 and 16 rows per lane
 // (ds_read_b128 from a quad table [code][lane][4 rows], address "code*1024 + lane*16" plus an immediate offset) and per
@@ -179,7 +163,7 @@ template <int RPL, int CODES> constexpr int etab_bytes_per_wave() { return etab:
 // hundred orders of magnitude of 2^-1022 depends on WHICH intermediate products were flushed: the fused
 // multiply-adds and the scaled form of the fast tiers flush at other points than the reference does.
 // FIVE (fp32, four-code table, groups of up to 16 lanes -- reads of at most 192 bases): the five-operation cell is the
-// only form of the sweep (see the comment above `use_plain`); a test case it cannot take joins the N-haplotype list.
+// only form of the sweep (pairhmm_cell.h); a test case it cannot take joins the N-haplotype list.
 template <typename T, int G, int RPL, bool STRIP = false, bool EXACT = false, int CODES = kMaxCodes, bool FIVE = false>
 __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem, const uint32_t block, const uint32_t n_blocks) {
     constexpr int GPW = 64 / G;                   // groups per wavefront
@@ -187,7 +171,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
     constexpr int kNumCodes = CODES;
     static_assert(CODES == 4 || CODES == kMaxCodes, "four or five code columns");
     static_assert(kETab || CODES == kMaxCodes, "fp64 has no table: the N code is compared");
-    static_assert(!FIVE || (kETab && CODES == 4 && G <= 16 && !STRIP && !EXACT), "the five-operation cell: first fp32 launch of the classes of up to 16 lanes");
+    static_assert(!FIVE || (kETab && CODES == 4 && G <= kFiveOpMaxG && !STRIP && !EXACT), "the five-operation cell: first fp32 launch of the classes of up to 16 lanes");
     constexpr bool kSix = (sizeof(T) == 4) && !EXACT;   // fp32: the 6-operation cell; fp64: the scaled 7-operation cell (see sweep)
     using ETab = etab::Layout<RPL, CODES, kETab && etab::quad_layout(G, RPL, CODES)>;
     constexpr int S = lane_stride<G>();           // lane stride of a group inside its DPP row
@@ -269,7 +253,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         bool defer = group_hap_n;                         // the test case is left to the class's second launch
         T res_scale = 1;                                  // (FIVE) A' of this lane's bottom row: the last lane's turns sum x into sum X
         if constexpr (STRIP) {                            // every strip of a pair must take the same algebraic form
-            for (int rr = lane; rr < R; rr += 64) zero_gap |= (a.gcp[job.read_off + (uint64_t)rr] & 127) == 0;
+            for (int rr = lane; rr < R; rr += 64) zero_gap |= cell::row_needs_plain(a.gcp[job.read_off + (uint64_t)rr] & 127);
         }
         int nl = 0;
         T* const bnd = STRIP ? reinterpret_cast<T*>(a.strip_scratch) + (size_t)block * 6u * a.strip_stride : nullptr;
@@ -291,7 +275,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         T pm[RPL], px[RPL], py[RPL];
         bool clone[RPL];
         T ratio[RPL];                                     // pXX / pGAPM per row (scaled form)
-        const T init_y = Prec<T>::initial() / (T)(H > 0 ? H : 1);
+        const T init_y = cell::initial_y<Ar, T>(H);
 #pragma unroll
         for (int s = 0; s < RPL; ++s) {
             const int rho = j * RPL + s - top_clones;     // 0-based read row, < 0: clone of row 0
@@ -304,21 +288,23 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     py[s] = init_y;
                 } else {
                     const uint64_t o = job.read_off + (uint64_t)(row_base + rho);
+                    // (the 7-bit masks, pMM's index and the mismatch emission are pairhmm_cell.h's q7, pMM_of and mismatch_of written
+                    // out: integer expressions moved into a function come back canonicalised otherwise, and with them the whole
+                    // register allocation -- DESIGN.md 3.2)
                     const int qi = a.ins[o] & 127, qd = a.del[o] & 127, qc = a.gcp[o] & 127;
                     const int qq = a.qual[o] & 127;
                     const int mn = qi <= qd ? qi : qd, mx = qi <= qd ? qd : qi;
                     k0[s] = mm[((mx * (mx + 1)) >> 1) + mn];
-                    k3[s] = ph2pr[qc];
-                    k1[s] = (T)1.0 - ph2pr[qc];
-                    k2[s] = ph2pr[qi];
-                    k4[s] = ph2pr[qd];
-                    zero_gap |= (qc == 0);
-                    if constexpr (FIVE) zero_mm |= (k0[s] == (T)0);
-                    const T distm = ph2pr[qq];
-                    eM[s] = (T)1.0 - distm;
+                    k3[s] = cell::pXX_of(ph2pr, qc);
+                    k1[s] = cell::pGAPM_of<Ar>(ph2pr, qc);
+                    k2[s] = cell::pMX_of(ph2pr, qi);
+                    k4[s] = cell::pMY_of(ph2pr, qd);
+                    zero_gap |= cell::row_needs_plain(qc);
+                    if constexpr (FIVE) zero_mm |= cell::row_has_zero_pMM(k0[s]);
+                    eM[s] = cell::match_of<Ar>(ph2pr, qq);
                     const int code = base_code(a.bases[o]);
                     eX[s] = (code == kCodeN) ? eM[s] : ph2pr_div3[qq];
-                    ratio[s] = gap_ratio[qc];
+                    ratio[s] = cell::ratio_of(gap_ratio, qc);
                     rb[s] = code;
                 }
             }
@@ -327,33 +313,31 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         // to the second launch -- per test case, like a haplotype with an N
         if constexpr (FIVE) {
             defer |= (__ballot((int)(zero_gap | zero_mm)) & gmask) != 0;
-            // The coefficients of the five-operation cell (see the comment above `use_plain`), per row:
-            //   k1 = a = A' of the row above, k2 = B', k3 = q', k4 = pYY, and the emissions times s = pMM of the row below.
-            // Rows below / above the lane's own come from the neighbour lanes; read row R has g' = s = 1, and above read
-            // row 0 lie A' = 0 and pMY = 1.  Every product and quotient is rounded on its own, in this order, which
-            // tools/cell_emulator.cpp (form 4) repeats.
+            // The coefficients of the five-operation cell, per row: k1 = a = A' of the row above, k2 = B', k3 = q', k4 = pYY, and
+            // the emissions times s = pMM of the row below.  Rows below / above the lane's own come from the neighbour lanes.
+            using Edge = cell::Edge<T>;
             const bool last_lane = j == nl - 1;
             const T g_next_lane = shr1_down<G>(k1[0]), mm_next_lane = shr1_down<G>(k0[0]);
             T rcp[RPL], Ap[RPL], gr[RPL];
 #pragma unroll
             for (int s = 0; s < RPL; ++s) {
-                const T gb = (s + 1 < RPL) ? k1[s + 1] : (last_lane ? (T)1.0 : g_next_lane);
-                const T sb = (s + 1 < RPL) ? k0[s + 1] : (last_lane ? (T)1.0 : mm_next_lane);
-                rcp[s] = (T)1.0 / k0[s];
-                Ap[s] = clone[s] ? (T)0 : (gb * k2[s]) * rcp[s];           // A' = g' pMX / pMM
-                gr[s] = gb * ratio[s];                                    // g' pXX / g
-                eM[s] *= sb; eX[s] *= sb;                                 // E = e s
+                const T gb = (s + 1 < RPL) ? k1[s + 1] : (last_lane ? Edge::g_below() : g_next_lane);
+                const T sb = (s + 1 < RPL) ? k0[s + 1] : (last_lane ? Edge::s_below() : mm_next_lane);
+                rcp[s] = cell::five_rcp<Ar>(k0[s]);
+                Ap[s] = clone[s] ? Edge::A_above() : cell::five_Ap<Ar>(gb, k2[s], rcp[s]);
+                gr[s] = cell::scaled_B<Ar>(gb, ratio[s]);
+                eM[s] = cell::five_E<Ar>(eM[s], sb); eX[s] = cell::five_E<Ar>(eX[s], sb);
             }
-            const T my_up = shr1<G>((T)1.0, clone[RPL - 1] ? (T)1.0 : k4[RPL - 1]);
-            const T a_up = shr1<G>((T)0, Ap[RPL - 1]);
+            const T my_up = shr1<G>(Edge::pMY_above(), clone[RPL - 1] ? Edge::pMY_above() : k4[RPL - 1]);
+            const T a_up = shr1<G>(Edge::A_above(), Ap[RPL - 1]);
             T qv[RPL], av[RPL], bv[RPL];
 #pragma unroll
             for (int s = 0; s < RPL; ++s) {
                 const int rho = j * RPL + s - top_clones;
-                const T my_above = s ? (clone[s - 1] ? (T)1.0 : k4[s - 1]) : my_up;
+                const T my_above = s ? (clone[s - 1] ? Edge::pMY_above() : k4[s - 1]) : my_up;
                 av[s] = s ? Ap[s - 1] : a_up;
-                qv[s] = rho == 0 ? k1[s] : (k1[s] * my_above) * rcp[s];    // q' = g pMY' / pMM; read row 0: g (y of the boundary row is unscaled)
-                bv[s] = (gr[s] * av[s]) / Ap[s];                          // B' = g' (pXX / g) A'' / A'  (A'': of the row above)
+                qv[s] = rho == 0 ? k1[s] : cell::five_q<Ar>(k1[s], my_above, rcp[s]);     // read row 0: g (y of the boundary row is unscaled)
+                bv[s] = cell::five_Bp<Ar>(gr[s], av[s], Ap[s]);
             }
 #pragma unroll
             for (int s = 0; s < RPL; ++s) {
@@ -433,42 +417,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
             }
         };
 
-        // The sweep in three algebraic forms (plain, or the precision's fast form; selected per wavefront):
-        //  plain  (the reference's operation order, avx-pairhmm-template.h:177-192), 8 ops per cell:
-        //      M = ((M2*pMM + X2*pGAPM) + Y2*pGAPM) * e ;  X = M1*pMX + X1*pXX ;  Y = Ml*pMY + Yl*pYY
-        //  scaled (fp64), 7 ops per cell: rows carry X^ = g'*X and Y^ = g'*Y, g' = pGAPM of the row BELOW
-        //  (the only consumer of X and Y across rows), so the consumer needs no multiply:
-        //      M  = (fma(pMM, M2, X^2) + Y^2) * e
-        //      X^ = A*M1 + B*X^1     A = g'*pMX,  B = g'*pXX/g   (g = this row's pGAPM)
-        //      Y^ = C*Ml + D*Y^l     C = g'*pMY,  D = pYY
-        //  Read row R has no row below: g' = 1 there, so its X^ is X and the final sums are unchanged.
-        //  six (fp32), 6 ops per cell: X^ as in the scaled form, Y carried as y = Y / pMY of its own row.  Y's
-        //  recurrence runs along the row, so that scale never changes along it and y needs no multiply:
-        //      M  = fma(q, y2, fma(pMM, M2, X^2)) * e     q = g * pMY' (pMY' = pMY of the row above, 1 for row 0)
-        //      X^ = A*M1 + B*X^1
-        //      y  = pYY*yl + Ml
-        //  The match-to-match path (pMM, e) carries table values only, as in the reference: a rounded per-row
-        //  product on it (e*g or pMM/g) adds a bias of up to an ulp per row, which over a 1000-row read
-        //  reaches 1.5e-5 in log10 (tools/dev_cell_emulate.py).  y <= max M / (1 - pYY) <= 4.9 max M for
-        //  gap-continuation bytes >= 1, and pMY' is a table value, so q has the same bits wherever the row
-        //  above lives (this lane, the lane above, the previous strip).
-        //  B divides by g, so a wavefront that sees a row with pGAPM == 0 (gap-continuation byte 0)
-        //  takes the plain form.
-        //  five (fp32, FIVE), 5 ops per cell: each row rescaled once more, m = s*M, x = X^ / A', yb = s*y with s = pMM of
-        //  the row below (1 for read row R) and A' = g'*pMX / pMM of the row itself:
-        //      m  = fma(q', yb2, fma(a, x2, m2)) * E     q' = g * pMY' / pMM,  a = A' of the row above,  E = e * s
-        //      x  = fma(x1, B', m1)                      B' = g' * (pXX / g) * a / A'
-        //      yb = fma(ybl, pYY, ml)
-        //  Above read row 0: a = B' = 0 and q' = g (the boundary row keeps y = INITIAL/H unscaled).  Read row R has
-        //  s = g' = 1, so sum M is sum m and sum X is A' * sum x: one multiply per test case.  E is rounded once, when the
-        //  table is built: the match-to-match path now carries one rounded product per row, which is why the form stops
-        //  at the 192 rows of the 16-lane classes (with two such products, form 2 of the emulator, 1000-row reads reach
-        //  1.5e-5; with one, reads of up to 192 rows stay at the 6-operation cell's 3.8e-6 / 7.6e-6:
-        //  profiles/pairhmm_fiveop_emulation.txt).  The form divides by pMM and, through A', by g': a test case with a
-        //  zero among them is deferred before the sweep (`defer`), and x is as large as M, not as X, so rows whose
-        //  insertion qualities differ by tens of dB can overflow fp32: every term is non-negative, an overflow reaches
-        //  the last row's sums as inf or NaN, and such a result is deferred after the sweep.  Both per test case, to the
-        //  class's N-haplotype list, which the second launch computes in the forms above.
+        // The sweep in one of the algebraic forms of pairhmm_cell.h (the algebra is in its header comment): plain, or the
+        // precision's fast form, selected per wavefront; with FIVE the five-operation cell.
         const bool use_plain = EXACT || __any((int)zero_gap) != 0;
         constexpr int kPlain = 0, kScaled = 1, kSixOp = 2, kFiveOp = 3;
 
@@ -487,8 +437,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 #pragma unroll
                 for (int s = 0; s < RPL; ++s) g_below[s] = (s + 1 < RPL) ? g_own[s + 1] : g_next_lane;
                 if (j == nl - 1) {                               // read row R: unscaled; a strip's last row: the next strip's first row
-                    g_below[RPL - 1] = (T)1.0;
-                    if constexpr (STRIP) { if (!last_strip) g_below[RPL - 1] = (T)1.0 - ph2pr[a.gcp[job.read_off + (uint64_t)(row_base + rows_here)] & 127]; }
+                    g_below[RPL - 1] = cell::Edge<T>::g_below();
+                    if constexpr (STRIP) { if (!last_strip) g_below[RPL - 1] = cell::pGAPM_of<Ar>(ph2pr, a.gcp[job.read_off + (uint64_t)(row_base + rows_here)] & 127); }
                 }
                 // six: pMY of the row above each row -- this lane's row s - 1, or lane j - 1's bottom row; above the group's
                 // lane 0 lies the boundary row (pMY_0 := 1, so y_0 = INITIAL/H) or the previous strip's last read row.
@@ -497,10 +447,10 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 if constexpr (SIX) {
                     T my_own[RPL];
 #pragma unroll
-                    for (int s = 0; s < RPL; ++s) my_own[s] = clone[s] ? (T)1.0 : k4[s];
-                    T my_top = (T)1.0;
+                    for (int s = 0; s < RPL; ++s) my_own[s] = clone[s] ? cell::Edge<T>::pMY_above() : k4[s];
+                    T my_top = cell::Edge<T>::pMY_above();
                     if constexpr (STRIP) {
-                        if (strip > 0) my_top = ph2pr[a.del[job.read_off + (uint64_t)(row_base - 1)] & 127];
+                        if (strip > 0) my_top = cell::pMY_of(ph2pr, a.del[job.read_off + (uint64_t)(row_base - 1)] & 127);
                     }
                     my_above[0] = shr1<G>(my_top, my_own[RPL - 1]);
 #pragma unroll
@@ -509,19 +459,19 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 #pragma unroll
                 for (int s = 0; s < RPL; ++s) {
                     if (clone[s]) {
-                        py[s] = SIX ? init_y : g_below[s] * init_y;   // Y^ / y of a row-0 clone, constant (D = 1)
+                        py[s] = SIX ? init_y : cell::scaled_Y0<Ar>(g_below[s], init_y);   // Y^ / y of a row-0 clone, constant (D = 1)
                     } else {
                         const T gb = g_below[s];
                         const T pMX = k2[s], pXX = k3[s], pMY = k4[s];
-                        k1[s] = gb * pMX;                        // A
-                        k2[s] = gb * ratio[s];                   // B = g' * (pXX / g), ratio from the table
-                        if constexpr (SIX) k3[s] = g_own[s] * my_above[s];   // q = g * pMY'
-                        else k3[s] = gb * pMY;                               // C
+                        k1[s] = cell::scaled_A<Ar>(gb, pMX);
+                        k2[s] = cell::scaled_B<Ar>(gb, ratio[s]);
+                        if constexpr (SIX) k3[s] = cell::six_q<Ar>(g_own[s], my_above[s]);
+                        else k3[s] = cell::scaled_C<Ar>(gb, pMY);
                         k4[s] = pXX;                             // D = pYY
                     }
                     if (clone[s]) { k1[s] = 0; k2[s] = 0; k3[s] = 0; k4[s] = 1; }
                 }
-                y_above = SIX ? init_y : g_own[0] * init_y;
+                y_above = SIX ? init_y : cell::scaled_Y0<Ar>(g_own[0], init_y);
             }
             const T old_y = (j == 0) ? y_above : (T)0;
             T uaM = 0, uaX = 0, uaY = old_y, ubM = 0, ubX = 0, ubY = old_y;   // two shifted-in sets
@@ -548,60 +498,60 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     // read them, so no value has to be moved out of the way; X follows top down from the new M
 #pragma unroll
                     for (int s = RPL - 1; s >= 0; --s) {
-                        const T t = s ? fma_(k3[s], py[s - 1], fma_(pm[s - 1], k0[s], px[s - 1]))
-                                      : fma_(k3[0], o2Y, fma_(o2M, k0[0], o2X));
-                        py[s] = fma_(py[s], k4[s], pm[s]);
-                        pm[s] = t * ec[s];
+                        const T t = s ? cell::six_M_paths<Ar>(pm[s - 1], px[s - 1], py[s - 1], k0[s], k3[s])
+                                      : cell::six_M_paths<Ar>(o2M, o2X, o2Y, k0[0], k3[0]);
+                        py[s] = cell::six_y<Ar>(pm[s], py[s], k4[s]);
+                        pm[s] = cell::emit<Ar>(t, ec[s]);
                     }
-                    px[0] = fma_(o1X, k2[0], o1M * k1[0]);
+                    px[0] = cell::scaled_X<Ar>(o1M, o1X, k1[0], k2[0]);
 #pragma unroll
-                    for (int s = 1; s < RPL; ++s) px[s] = fma_(px[s - 1], k2[s], pm[s - 1] * k1[s]);
+                    for (int s = 1; s < RPL; ++s) px[s] = cell::scaled_X<Ar>(pm[s - 1], px[s - 1], k1[s], k2[s]);
 #pragma unroll
                     for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
                 } else if constexpr (FIV) {
                     // in place like the 6-operation cell: m and yb bottom row first, then x top down from the new m
 #pragma unroll
                     for (int s = RPL - 1; s >= 0; --s) {
-                        const T t = s ? fma_(k3[s], py[s - 1], fma_(k1[s], px[s - 1], pm[s - 1]))
-                                      : fma_(k3[0], o2Y, fma_(k1[0], o2X, o2M));
-                        py[s] = fma_(py[s], k4[s], pm[s]);
-                        pm[s] = t * ec[s];
+                        const T t = s ? cell::five_m_paths<Ar>(pm[s - 1], px[s - 1], py[s - 1], k1[s], k3[s])
+                                      : cell::five_m_paths<Ar>(o2M, o2X, o2Y, k1[0], k3[0]);
+                        py[s] = cell::six_y<Ar>(pm[s], py[s], k4[s]);
+                        pm[s] = cell::emit<Ar>(t, ec[s]);
                     }
-                    px[0] = fma_(o1X, k2[0], o1M);
+                    px[0] = cell::five_x<Ar>(o1M, o1X, k2[0]);
 #pragma unroll
-                    for (int s = 1; s < RPL; ++s) px[s] = fma_(px[s - 1], k2[s], pm[s - 1]);
+                    for (int s = 1; s < RPL; ++s) px[s] = cell::five_x<Ar>(pm[s - 1], px[s - 1], k2[s]);
 #pragma unroll
                     for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
                 } else if constexpr (SC) {
-                    Mn[0] = (fma_(o2M, k0[0], o2X) + o2Y) * ec[0];
-                    Xn[0] = fma_(o1X, k2[0], o1M * k1[0]);
-                    Yn[0] = fma_(py[0], k4[0], pm[0] * k3[0]);
+                    Mn[0] = cell::scaled_M<Ar>(o2M, o2X, o2Y, k0[0], ec[0]);
+                    Xn[0] = cell::scaled_X<Ar>(o1M, o1X, k1[0], k2[0]);
+                    Yn[0] = cell::scaled_Y<Ar>(pm[0], py[0], k3[0], k4[0]);
 #pragma unroll
                     for (int s = 1; s < RPL; ++s) {
-                        Mn[s] = (fma_(pm[s - 1], k0[s], px[s - 1]) + py[s - 1]) * ec[s];
-                        Xn[s] = fma_(Xn[s - 1], k2[s], Mn[s - 1] * k1[s]);
-                        Yn[s] = fma_(py[s], k4[s], pm[s] * k3[s]);
+                        Mn[s] = cell::scaled_M<Ar>(pm[s - 1], px[s - 1], py[s - 1], k0[s], ec[s]);
+                        Xn[s] = cell::scaled_X<Ar>(Mn[s - 1], Xn[s - 1], k1[s], k2[s]);
+                        Yn[s] = cell::scaled_Y<Ar>(pm[s], py[s], k3[s], k4[s]);
                     }
                 } else if constexpr (EXACT) {
                     // avx-pairhmm-template.h:183-192, unfused (the file is built with -ffp-contract=off)
-                    Mn[0] = ((o2M * k0[0] + o2X * k1[0]) + o2Y * k1[0]) * ec[0];
-                    Xn[0] = o1M * k2[0] + o1X * k3[0];
-                    Yn[0] = pm[0] * k4[0] + py[0] * k3[0];
+                    Mn[0] = cell::exact_M<Ar>(o2M, o2X, o2Y, k0[0], k1[0], ec[0]);
+                    Xn[0] = cell::exact_X<Ar>(o1M, o1X, k2[0], k3[0]);
+                    Yn[0] = cell::exact_Y<Ar>(pm[0], py[0], k4[0], k3[0]);
 #pragma unroll
                     for (int s = 1; s < RPL; ++s) {
-                        Mn[s] = ((pm[s - 1] * k0[s] + px[s - 1] * k1[s]) + py[s - 1] * k1[s]) * ec[s];
-                        Xn[s] = Mn[s - 1] * k2[s] + Xn[s - 1] * k3[s];
-                        Yn[s] = pm[s] * k4[s] + py[s] * k3[s];
+                        Mn[s] = cell::exact_M<Ar>(pm[s - 1], px[s - 1], py[s - 1], k0[s], k1[s], ec[s]);
+                        Xn[s] = cell::exact_X<Ar>(Mn[s - 1], Xn[s - 1], k2[s], k3[s]);
+                        Yn[s] = cell::exact_Y<Ar>(pm[s], py[s], k4[s], k3[s]);
                     }
                 } else {
-                    Mn[0] = fma_(o2Y, k1[0], fma_(o2X, k1[0], o2M * k0[0])) * ec[0];
-                    Xn[0] = fma_(o1X, k3[0], o1M * k2[0]);
-                    Yn[0] = fma_(py[0], k3[0], pm[0] * k4[0]);
+                    Mn[0] = cell::plain_M<Ar>(o2M, o2X, o2Y, k0[0], k1[0], ec[0]);
+                    Xn[0] = cell::plain_X<Ar>(o1M, o1X, k2[0], k3[0]);
+                    Yn[0] = cell::plain_Y<Ar>(pm[0], py[0], k4[0], k3[0]);
 #pragma unroll
                     for (int s = 1; s < RPL; ++s) {
-                        Mn[s] = fma_(py[s - 1], k1[s], fma_(px[s - 1], k1[s], pm[s - 1] * k0[s])) * ec[s];
-                        Xn[s] = fma_(Xn[s - 1], k3[s], Mn[s - 1] * k2[s]);
-                        Yn[s] = fma_(py[s], k3[s], pm[s] * k4[s]);
+                        Mn[s] = cell::plain_M<Ar>(pm[s - 1], px[s - 1], py[s - 1], k0[s], k1[s], ec[s]);
+                        Xn[s] = cell::plain_X<Ar>(Mn[s - 1], Xn[s - 1], k2[s], k3[s]);
+                        Yn[s] = cell::plain_Y<Ar>(pm[s], py[s], k4[s], k3[s]);
                     }
                 }
 #pragma unroll
@@ -660,14 +610,14 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
 
         // ---- result (IntelPairHmm.cc:338-350)
         if (live && j == nl - 1) {
-            const T res = FIVE ? sumM + res_scale * sumX : sumM + sumX;
+            const T res = FIVE ? cell::five_result<Ar>(sumM, res_scale, sumX) : cell::result<Ar>(sumM, sumX);
             if constexpr (sizeof(T) == 4) {
                 // (FIVE) the dynamic rule: a result that is not finite -- an overflow in any cell -- is left to the second launch
-                if (defer || (FIVE && !(res <= 3.402823466e+38f))) {
+                if (defer || (FIVE && cell::five_overflowed(res))) {
                     const uint32_t k = atomicAdd(a.nhap_count, 1u);
                     a.nhap_list[k] = job_idx;
                     if constexpr (FIVE) { if (!group_hap_n) atomicAdd(a.form_count, 1u); }
-                } else if (res < 1e-28f) {
+                } else if (res < cell::kFloatFirstBelow) {
                     const uint32_t k = atomicAdd(a.rerun_count, 1u);
                     a.rerun_list[k] = job_idx;
                 } else {
@@ -677,7 +627,7 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 // below kExactBelow the flushed products may carry a visible share of the result (each flushed
                 // term is < 2^-1022 and the model passes on at most its own mass: with fewer than 1e21 operations
                 // per test case the share is < 1e-6 above the threshold); a zero counts as below
-                if (!EXACT && a.rerun_count && res < kExactBelow) {
+                if (!EXACT && a.rerun_count && res < cell::kExactBelow) {
                     const uint32_t k = atomicAdd(a.rerun_count, 1u);
                     a.rerun_list[k] = job_idx;
                 } else {
@@ -939,7 +889,7 @@ using KernelFn = void (*)(KernelArgs);
 // (four code columns: the first fp32 launch of a class -- with the five-operation cell in the classes of up to 16 lanes)
 template <typename T, int CODES = kMaxCodes>
 KernelFn pick_kernel(int G, int RPL) {
-#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r, CODES, (CODES == 4 && g <= 16)>;
+#define MGX_CASE(g, r) if (G == g && RPL == r) return pairhmm_fwd<T, g, r, CODES, (CODES == 4 && g <= kFiveOpMaxG)>;
     MGX_CASE(4, 1) MGX_CASE(4, 2) MGX_CASE(4, 3) MGX_CASE(4, 4) MGX_CASE(4, 5) MGX_CASE(4, 6) MGX_CASE(4, 7) MGX_CASE(4, 8)
     MGX_CASE(8, 1) MGX_CASE(8, 2) MGX_CASE(8, 3) MGX_CASE(8, 4) MGX_CASE(8, 5) MGX_CASE(8, 6) MGX_CASE(8, 7) MGX_CASE(8, 8)
     MGX_CASE(16, 1) MGX_CASE(16, 2) MGX_CASE(16, 3) MGX_CASE(16, 4)

@@ -66,6 +66,8 @@ constexpr int kNarrowMaxRPL = 8, kG8MaxRPL = 8, kG16MaxRPL = 12, kG64MinRPL = 4,
 constexpr int kMaxRowsG4 = 4 * kNarrowMaxRPL, kMaxRowsG8 = 8 * kG8MaxRPL;
 constexpr int kMaxRowsG16 = 16 * kG16MaxRPL;
 constexpr int kMaxRowsG64 = 64 * kG64MaxRPL;
+// the five-operation cell (pairhmm_cell.h) is the first fp32 launch of the classes of up to 16 lanes: reads of at most 192 bases
+constexpr int kFiveOpMaxG = 16, kFiveOpMaxRows = kMaxRowsG16;
 // Longer reads are strip-mined: 64 lanes x 16 rows per strip, the strips sweep the haplotype one after the other
 // (pairhmm_fwd_strip).  The limit below only keeps row indices and the boundary scratch in 32 bits.
 constexpr int kMaxRowsStrip = 1 << 20;

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from pairhmm_fiveop_cases import with_qualities
 from test_pairhmm_oracle import assert_log10_close
 
 pytestmark = pytest.mark.gpu
@@ -19,19 +20,6 @@ def run(engine, d):
     st = b.stats()
     b.close()
     return out, used, st
-
-
-def with_qualities(d, seed, qual=(0, 127), ins=(0, 127), dele=(0, 127), gcp=(1, 127), zero_ins_del_rate=0.05):
-    """d with every per-base quality drawn again, uniformly from the given ranges; a share of the bases gets
-    ins = del = 0, where matchToMatchProb is 0."""
-    rng = np.random.RandomState(seed)
-    nb = len(d["bases"])
-    draw = lambda r: rng.randint(r[0], r[1] + 1, nb).astype(np.uint8)  # noqa: E731
-    out = dict(d, qual=draw(qual), ins=draw(ins), dele=draw(dele), gcp=draw(gcp))
-    z = rng.rand(nb) < zero_ins_del_rate
-    out["ins"][z] = 0
-    out["dele"][z] = 0
-    return out
 
 
 def test_headline_shape_vs_oracle(engine, oracle, synth):

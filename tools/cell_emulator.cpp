@@ -1,170 +1,145 @@
-// cell_emulator.cpp -- host restatement of the fp32 PairHMM cells of pairhmm_body (csrc/pairhmm_kernels.hip.inc),
-// for numerics checks on a machine without a GPU (tools/dev_cell_emulate.py builds and drives it).
-//   form 1: the scaled 7-operation cell (X^ = g'X, Y^ = g'Y, g' = pGAPM of the row below) the fp32 kernels ran before
-//   form 2: a 6-operation cell with X as it is, y = Y / pMY of its own row, E = e*pGAPM, p = pMM/pGAPM (not used: the two
-//           rounded products on the match-to-match path of every row cost up to 1.5e-5 in log10 on reads of ~1000 bases)
-//   form 3: the 6-operation cell: X^ = g'X as in form 1, y = Y / pMY of its own row, q = pGAPM * pMY'
-//   form 4: the 5-operation cell of the first launch of the classes of up to 16 lanes (reads of at most 192 bases; longer
-//           reads stay with form 3): m = s*M, x = X^ / A', yb = s*y with s = pMM of the row below and A' = g'*pMX/pMM, the
-//           emission carried as E = e*s.  A test case it cannot take -- statically: a row with pMM == 0 or a
-//           gap-continuation byte of 0; dynamically: a result that is not finite -- is deferred to the second launch, as
-//           is one whose haplotype holds an N: those are computed in form 3 (form 0 with a gap-continuation byte of 0).
+// cell_emulator.cpp -- the fp32 PairHMM cells of pairhmm_body (csrc/pairhmm_kernels.hip.inc) on the host, for numerics checks on a
+// machine without a GPU (tests/pairhmm_fiveop_cases.py builds and drives it).  The forms, their per-row coefficients, the deferral
+// rules and the result are csrc/pairhmm_cell.h, the header the kernel computes with; here they run in a plain row-by-row sweep.
+//   form 0: the plain 8-operation cell; whatever form is asked for, a test case with a gap-continuation byte of 0 takes it
+//   form 1: the scaled 7-operation cell the fp32 kernels ran before
+//   form 2: a 6-operation cell with X as it is, y = Y / pMY of its own row, E = e*pGAPM, p = pMM/pGAPM.  No kernel runs it (the two
+//           rounded products on the match-to-match path of every row cost up to 1.5e-5 in log10 on reads of ~1000 bases), so its
+//           two coefficients are stated here and not in the header; its cells are the header's
+//   form 3: the 6-operation cell
+//   form 4: the first launch of the classes of up to 16 lanes: the 5-operation cell for reads of at most kFiveOpMaxRows bases.  A test
+//           case it defers (the static or the dynamic rule), one whose haplotype holds an N and a longer read are computed in form 3.
 //           cell_emulate_paths / cell_emulate_deferrals tell which way every test case of the last batch went.
-// A test case with a gap-continuation byte of 0 takes the plain 8-operation form (form 0), as its wavefront does.
-// Every multiply-add is an explicit fmaf, the file is built with -ffp-contract=off, and every rounded result is flushed to
-// zero when it is subnormal, as the device does (-fgpu-flush-denormals-to-zero).  The tables are the product's own
-// (csrc/mgx_tables.cpp).  A cell's value does not depend on the lane layout on the device, so a plain row-by-row sweep
-// gives the kernel's bits up to the final log10f.
+// The arithmetic handed to the header (Ftz) flushes every rounded result to zero when it is subnormal, as the device does
+// (-fgpu-flush-denormals-to-zero); the file is built with -ffp-contract=off.  The tables are the product's own (csrc/mgx_tables.cpp).
+// A cell's value does not depend on the lane layout on the device, so the sweep gives the kernel's bits up to the final log10f.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "mgx_tables.h"
+#include "pairhmm_cell.h"
+#include "pairhmm_plan.h"      // kFiveOpMaxRows
 
 namespace {
 
-inline float ftz(float v) { return std::fabs(v) < 0x1p-126f ? std::copysign(0.0f, v) : v; }
-inline float fma_(float a, float b, float c) { return ftz(std::fmaf(a, b, c)); }
-inline float mul(float a, float b) { return ftz(a * b); }
-inline float add(float a, float b) { return ftz(a + b); }
-inline float div(float a, float b) { return ftz(a / b); }
+namespace cell = mgx_hmm_cell;
+using Edge = cell::Edge<float>;
 
+struct Ftz {
+    static float ftz(float v) { return std::fabs(v) < 0x1p-126f ? std::copysign(0.0f, v) : v; }
+    static float fma(float a, float b, float c) { return ftz(std::fmaf(a, b, c)); }
+    static float mul(float a, float b) { return ftz(a * b); }
+    static float add(float a, float b) { return ftz(a + b); }
+    static float sub(float a, float b) { return ftz(a - b); }
+    static float div(float a, float b) { return ftz(a / b); }
+};
+
+enum Form { kPlain = 0, kScaled = 1, kSixA = 2, kSix = 3, kFirstLaunch = 4, kFive = 5 };
 // which way a test case went under form 4
 enum Path : uint8_t { kPathFive = 0, kPathStatic = 1, kPathDynamic = 2, kPathHapN = 3, kPathLong = 4 };
-constexpr int kFiveOpMaxRows = 192;
 std::vector<uint8_t> g_paths;      // of the last cell_emulate_batch call
 
-int code_of(uint8_t b) { return b == 'C' ? 1 : b == 'T' ? 2 : b == 'G' ? 3 : b == 'N' ? 4 : 0; }
+struct Rows {                      // a read's model values per row, and the haplotype's codes
+    std::vector<float> pMM, g, pMX, pXX, pMY, eM, eX, ratio;
+    std::vector<int> rc, hc;
+};
 
-// sum_c M[R][c] + sum_c X[R][c] of one test case, scaled by 2^120 (the kernel's `res`)
-float forward(int form, int R, const uint8_t* bases, const uint8_t* qual, const uint8_t* ins, const uint8_t* del,
-              const uint8_t* gcp, int H, const uint8_t* hap, uint8_t* path = nullptr) {
-    const auto& t = mgx::tables<float>();
-    const float init_y = 0x1p120f / (float)(H > 0 ? H : 1);
-    if (form == 4) {
-        // the kernel's order: a haplotype with an N goes to the list whatever the read holds, then the static rule
-        uint8_t way = kPathFive;
-        if (R > kFiveOpMaxRows) way = kPathLong;
-        if (way == kPathFive) for (int c = 0; c < H; ++c) if (hap[c] == 'N') way = kPathHapN;
-        if (way == kPathFive)
-            for (int i = 0; i < R; ++i) {
-                const int qi = ins[i] & 127, qd = del[i] & 127;
-                const int mn = qi <= qd ? qi : qd, mx = qi <= qd ? qd : qi;
-                if ((gcp[i] & 127) == 0 || t.mm[((mx * (mx + 1)) >> 1) + mn] == 0.0f) way = kPathStatic;
-            }
-        if (way == kPathFive) {
-            const float res = forward(5, R, bases, qual, ins, del, gcp, H, hap);
-            if (res <= 3.402823466e+38f) { if (path) *path = way; return res; }
-            way = kPathDynamic;
-        }
-        if (path) *path = way;
-        form = 3;
-    }
-    for (int i = 0; i < R; ++i) if ((gcp[i] & 127) == 0) form = 0;
-    std::vector<float> pMM(R), g(R), pMX(R), pXX(R), pMY(R), eM(R), eX(R), gratio(R), ginv(R);
-    std::vector<int> rc(R);
+// sum_c M[R][c] + sum_c X[R][c] in form F, scaled by 2^120 (the kernel's `res`)
+template <int F>
+float sweep(const Rows& r) {
+    const int R = (int)r.rc.size(), H = (int)r.hc.size();
+    const float init_y = cell::initial_y<Ftz, float>(H);
+    // rows above (index c = 0..H, column 0 is the DP's column 0); the boundary row: Y = INITIAL / H, Y^ in the scaled form
+    std::vector<float> Mu(H + 1, 0.0f), Xu(H + 1, 0.0f), Yu(H + 1, F == kScaled && R > 0 ? cell::scaled_Y0<Ftz>(r.g[0], init_y) : init_y);
+    std::vector<float> Mc(H + 1), Xc(H + 1), Yc(H + 1);
+    float Ap = Edge::A_above();                  // kFive: A' of the row above, in the end of read row R
     for (int i = 0; i < R; ++i) {
-        const int qi = ins[i] & 127, qd = del[i] & 127, qc = gcp[i] & 127, qq = qual[i] & 127;
-        const int mn = qi <= qd ? qi : qd, mx = qi <= qd ? qd : qi;
-        pMM[i] = t.mm[((mx * (mx + 1)) >> 1) + mn];
-        g[i] = 1.0f - t.ph2pr[qc];
-        pMX[i] = t.ph2pr[qi];
-        pXX[i] = t.ph2pr[qc];
-        pMY[i] = t.ph2pr[qd];
-        eM[i] = 1.0f - t.ph2pr[qq];
-        rc[i] = code_of(bases[i]);
-        eX[i] = rc[i] == 4 ? eM[i] : t.ph2pr_div3[qq];
-        gratio[i] = t.gap_ratio[qc];
-        ginv[i] = g[i] != 0.0f ? 1.0f / g[i] : 0.0f;
-    }
-    std::vector<int> hc(H);
-    for (int c = 0; c < H; ++c) hc[c] = code_of(hap[c]);
-    // rows above (index c = 0..H, column 0 is the DP's column 0)
-    std::vector<float> Mu(H + 1, 0.0f), Xu(H + 1, 0.0f), Yu(H + 1), Mc(H + 1), Xc(H + 1), Yc(H + 1);
-    float sumM = 0.0f, sumX = 0.0f;
-    // boundary row: Y = INITIAL / H (form 1: scaled by pGAPM of row 1; form 2: y_0 = Y_0 with pMY_0 := 1)
-    for (int c = 0; c <= H; ++c) Yu[c] = form == 1 ? (R > 0 ? mul(g[0], init_y) : init_y) : init_y;
-    if (form == 0) {
-        for (int i = 0; i < R; ++i) {
-            Mc[0] = 0.0f; Xc[0] = 0.0f; Yc[0] = 0.0f;
-            for (int c = 1; c <= H; ++c) {
-                const bool match = rc[i] == hc[c - 1] || rc[i] == 4 || hc[c - 1] == 4;
-                const float e = match ? eM[i] : eX[i];
-                Mc[c] = mul(fma_(Yu[c - 1], g[i], fma_(Xu[c - 1], g[i], mul(Mu[c - 1], pMM[i]))), e);
-                Xc[c] = fma_(Xu[c], pXX[i], mul(Mu[c], pMX[i]));
-                Yc[c] = fma_(Yc[c - 1], pXX[i], mul(Mc[c - 1], pMY[i]));
-            }
-            std::swap(Mu, Mc); std::swap(Xu, Xc); std::swap(Yu, Yc);
+        const bool last = i + 1 == R;
+        const float pMM = r.pMM[i], g = r.g[i], pMX = r.pMX[i], pXX = r.pXX[i], pMY = r.pMY[i];
+        const float gb = last ? Edge::g_below() : r.g[i + 1], s = last ? Edge::s_below() : r.pMM[i + 1];
+        const float my_above = i ? r.pMY[i - 1] : Edge::pMY_above();
+        float cA = 0, cB = 0, cC = 0, eM = r.eM[i], eX = r.eX[i];      // the form's coefficients, and its emissions
+        if constexpr (F == kScaled || F == kSix) {
+            cA = cell::scaled_A<Ftz>(gb, pMX);
+            cB = cell::scaled_B<Ftz>(gb, r.ratio[i]);
+            cC = F == kSix ? cell::six_q<Ftz>(g, my_above) : cell::scaled_C<Ftz>(gb, pMY);
+        } else if constexpr (F == kSixA) {
+            cA = Ftz::mul(pMM, g != 0.0f ? 1.0f / g : 0.0f);           // p
+            eM = Ftz::mul(eM, g); eX = Ftz::mul(eX, g);                // E
+        } else if constexpr (F == kFive) {
+            const float rcp = cell::five_rcp<Ftz>(pMM);
+            cA = Ap;                                                   // a
+            Ap = cell::five_Ap<Ftz>(gb, pMX, rcp);
+            cB = cell::five_Bp<Ftz>(cell::scaled_B<Ftz>(gb, r.ratio[i]), cA, Ap);
+            cC = i ? cell::five_q<Ftz>(g, my_above, rcp) : g;
+            eM = cell::five_E<Ftz>(eM, s); eX = cell::five_E<Ftz>(eX, s);
         }
-        for (int c = 1; c <= H; ++c) { sumM = add(sumM, Mu[c]); sumX = add(sumX, Xu[c]); }
-        return add(sumM, sumX);
-    }
-    if (form == 5) {
-        // the 5-operation sweep itself (form 4 without its deferral rules): Mu, Xu, Yu hold m, x, yb
-        float A_above = 0.0f, A_last = 0.0f;
-        for (int i = 0; i < R; ++i) {
-            Mc[0] = 0.0f; Xc[0] = 0.0f; Yc[0] = 0.0f;
-            const float gb = i + 1 < R ? g[i + 1] : 1.0f, s = i + 1 < R ? pMM[i + 1] : 1.0f;
-            const float rcp = div(1.0f, pMM[i]);
-            const float Ap = mul(mul(gb, pMX[i]), rcp);
-            const float q = i > 0 ? mul(mul(g[i], pMY[i - 1]), rcp) : g[0];
-            const float a = A_above;
-            const float Bp = div(mul(mul(gb, gratio[i]), A_above), Ap);
-            const float EM = mul(eM[i], s), EX = mul(eX[i], s);
-            for (int c = 1; c <= H; ++c) {
-                const bool match = rc[i] == hc[c - 1] || rc[i] == 4 || hc[c - 1] == 4;
-                const float E = match ? EM : EX;
-                Mc[c] = mul(fma_(q, Yu[c - 1], fma_(a, Xu[c - 1], Mu[c - 1])), E);
-                Xc[c] = fma_(Xu[c], Bp, Mu[c]);
-                Yc[c] = fma_(Yc[c - 1], pXX[i], Mc[c - 1]);
-            }
-            std::swap(Mu, Mc); std::swap(Xu, Xc); std::swap(Yu, Yc);
-            A_above = Ap; A_last = Ap;
-        }
-        if (R > 0)
-            for (int c = 1; c <= H; ++c) { sumM = add(sumM, Mu[c]); sumX = add(sumX, Xu[c]); }
-        return add(sumM, mul(A_last, sumX));
-    }
-    for (int i = 0; i < R; ++i) {
         Mc[0] = 0.0f; Xc[0] = 0.0f; Yc[0] = 0.0f;
-        if (form == 1) {
-            const float gb = i + 1 < R ? g[i + 1] : 1.0f;
-            const float A = mul(gb, pMX[i]), B = mul(gb, gratio[i]), C = mul(gb, pMY[i]), D = pXX[i];
-            for (int c = 1; c <= H; ++c) {
-                const bool match = rc[i] == hc[c - 1] || rc[i] == 4 || hc[c - 1] == 4;
-                const float e = match ? eM[i] : eX[i];
-                Mc[c] = mul(add(fma_(Mu[c - 1], pMM[i], Xu[c - 1]), Yu[c - 1]), e);
-                Xc[c] = fma_(Xu[c], B, mul(Mu[c], A));
-                Yc[c] = fma_(Yc[c - 1], D, mul(Mc[c - 1], C));
-            }
-        } else if (form == 3) {
-            const float gb = i + 1 < R ? g[i + 1] : 1.0f;
-            const float A = mul(gb, pMX[i]), B = mul(gb, gratio[i]), q = mul(g[i], i > 0 ? pMY[i - 1] : 1.0f);
-            for (int c = 1; c <= H; ++c) {
-                const bool match = rc[i] == hc[c - 1] || rc[i] == 4 || hc[c - 1] == 4;
-                const float e = match ? eM[i] : eX[i];
-                Mc[c] = mul(fma_(q, Yu[c - 1], fma_(Mu[c - 1], pMM[i], Xu[c - 1])), e);
-                Xc[c] = fma_(Xu[c], B, mul(Mu[c], A));
-                Yc[c] = fma_(Yc[c - 1], pXX[i], Mc[c - 1]);
-            }
-        } else {
-            const float p = mul(pMM[i], ginv[i]);
-            const float my_above = i > 0 ? pMY[i - 1] : 1.0f;
-            const float EM = mul(eM[i], g[i]), EX = mul(eX[i], g[i]);
-            for (int c = 1; c <= H; ++c) {
-                const bool match = rc[i] == hc[c - 1] || rc[i] == 4 || hc[c - 1] == 4;
-                const float E = match ? EM : EX;
-                Mc[c] = mul(fma_(my_above, Yu[c - 1], fma_(Mu[c - 1], p, Xu[c - 1])), E);
-                Xc[c] = fma_(Xu[c], pXX[i], mul(Mu[c], pMX[i]));
-                Yc[c] = fma_(Yc[c - 1], pXX[i], Mc[c - 1]);
+        for (int c = 1; c <= H; ++c) {
+            const float e = cell::is_match(r.rc[i], r.hc[c - 1]) ? eM : eX;
+            const float M2 = Mu[c - 1], X2 = Xu[c - 1], Y2 = Yu[c - 1], M1 = Mu[c], X1 = Xu[c], Ml = Mc[c - 1], Yl = Yc[c - 1];
+            if constexpr (F == kPlain) {
+                Mc[c] = cell::plain_M<Ftz>(M2, X2, Y2, pMM, g, e); Xc[c] = cell::plain_X<Ftz>(M1, X1, pMX, pXX); Yc[c] = cell::plain_Y<Ftz>(Ml, Yl, pMY, pXX);
+            } else if constexpr (F == kScaled) {
+                Mc[c] = cell::scaled_M<Ftz>(M2, X2, Y2, pMM, e); Xc[c] = cell::scaled_X<Ftz>(M1, X1, cA, cB); Yc[c] = cell::scaled_Y<Ftz>(Ml, Yl, cC, pXX);
+            } else if constexpr (F == kSix) {
+                Mc[c] = cell::emit<Ftz>(cell::six_M_paths<Ftz>(M2, X2, Y2, pMM, cC), e); Xc[c] = cell::scaled_X<Ftz>(M1, X1, cA, cB); Yc[c] = cell::six_y<Ftz>(Ml, Yl, pXX);
+            } else if constexpr (F == kSixA) {
+                Mc[c] = cell::emit<Ftz>(cell::six_M_paths<Ftz>(M2, X2, Y2, cA, my_above), e); Xc[c] = cell::plain_X<Ftz>(M1, X1, pMX, pXX); Yc[c] = cell::six_y<Ftz>(Ml, Yl, pXX);
+            } else {
+                Mc[c] = cell::emit<Ftz>(cell::five_m_paths<Ftz>(M2, X2, Y2, cA, cC), e); Xc[c] = cell::five_x<Ftz>(M1, X1, cB); Yc[c] = cell::six_y<Ftz>(Ml, Yl, pXX);
             }
         }
         std::swap(Mu, Mc); std::swap(Xu, Xc); std::swap(Yu, Yc);
     }
-    if (R > 0)
-        for (int c = 1; c <= H; ++c) { sumM = add(sumM, Mu[c]); sumX = add(sumX, Xu[c]); }
-    return add(sumM, sumX);
+    float sumM = 0.0f, sumX = 0.0f;
+    for (int c = 1; c <= H; ++c) { sumM = Ftz::add(sumM, Mu[c]); sumX = Ftz::add(sumX, Xu[c]); }
+    return F == kFive ? cell::five_result<Ftz>(sumM, Ap, sumX) : cell::result<Ftz>(sumM, sumX);
+}
+
+float forward(int form, int R, const uint8_t* bases, const uint8_t* qual, const uint8_t* ins, const uint8_t* del,
+              const uint8_t* gcp, int H, const uint8_t* hap, uint8_t* path) {
+    const auto& t = mgx::tables<float>();
+    Rows r;
+    for (auto* v : {&r.pMM, &r.g, &r.pMX, &r.pXX, &r.pMY, &r.eM, &r.eX, &r.ratio}) v->resize(R);
+    r.rc.resize(R); r.hc.resize(H);
+    bool plain = false, five_defers = false, hap_n = false;
+    for (int i = 0; i < R; ++i) {
+        const int qi = cell::q7(ins[i]), qd = cell::q7(del[i]), qc = cell::q7(gcp[i]), qq = cell::q7(qual[i]);
+        r.pMM[i] = cell::pMM_of(t.mm.data(), qi, qd);
+        r.g[i] = cell::pGAPM_of<Ftz>(t.ph2pr.data(), qc);
+        r.pMX[i] = cell::pMX_of(t.ph2pr.data(), qi);
+        r.pXX[i] = cell::pXX_of(t.ph2pr.data(), qc);
+        r.pMY[i] = cell::pMY_of(t.ph2pr.data(), qd);
+        r.eM[i] = cell::match_of<Ftz>(t.ph2pr.data(), qq);
+        r.rc[i] = cell::base_code(bases[i]);
+        r.eX[i] = cell::mismatch_of(t.ph2pr_div3.data(), qq, r.rc[i], r.eM[i]);
+        r.ratio[i] = cell::ratio_of(t.gap_ratio.data(), qc);
+        plain |= cell::row_needs_plain(qc);
+        five_defers |= cell::five_defers_row(r.pMM[i], qc);
+    }
+    for (int c = 0; c < H; ++c) { r.hc[c] = cell::base_code(hap[c]); hap_n |= r.hc[c] == cell::kCodeN; }
+    if (form == kFirstLaunch) {
+        // the kernel's order: a haplotype with an N goes to the list whatever the read holds, then the static rule
+        uint8_t way = R > mgx_hmm_plan::kFiveOpMaxRows ? kPathLong : hap_n ? kPathHapN : five_defers ? kPathStatic : kPathFive;
+        if (way == kPathFive) {
+            const float res = sweep<kFive>(r);
+            if (!cell::five_overflowed(res)) { *path = way; return res; }
+            way = kPathDynamic;
+        }
+        *path = way;
+        form = kSix;
+    }
+    if (plain) form = kPlain;
+    switch (form) {
+        case kPlain: return sweep<kPlain>(r);
+        case kScaled: return sweep<kScaled>(r);
+        case kSixA: return sweep<kSixA>(r);
+        case kFive: return sweep<kFive>(r);
+        default: return sweep<kSix>(r);
+    }
 }
 
 }  // namespace
@@ -192,5 +167,13 @@ void cell_emulate_paths(int n, uint8_t* out) {
 void cell_emulate_deferrals(uint64_t* n_static, uint64_t* n_dynamic) {
     *n_static = 0; *n_dynamic = 0;
     for (uint8_t w : g_paths) { *n_static += w == kPathStatic; *n_dynamic += w == kPathDynamic; }
+}
+// the four fp32 tables the cells read (128, 32640, 128 and 128 values), as this machine's libm built them
+void cell_emulate_tables(float* ph2pr, float* mm, float* ph2pr_div3, float* gap_ratio) {
+    const auto& t = mgx::tables<float>();
+    std::memcpy(ph2pr, t.ph2pr.data(), t.ph2pr.size() * sizeof(float));
+    std::memcpy(mm, t.mm.data(), t.mm.size() * sizeof(float));
+    std::memcpy(ph2pr_div3, t.ph2pr_div3.data(), t.ph2pr_div3.size() * sizeof(float));
+    std::memcpy(gap_ratio, t.gap_ratio.data(), t.gap_ratio.size() * sizeof(float));
 }
 }

@@ -6,10 +6,8 @@ that both the emulation and the oracle keep in fp32, and how often the float-fir
 For the 5-operation cell also: how many test cases the static and the dynamic rule defer, how many keep the 6-operation
 cell because of an N in the haplotype or their length, and the largest |log10 difference| to the 6-operation cell.
 usage: python tools/dev_cell_emulate.py [--quick]"""
-import ctypes as C
 import importlib
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,61 +17,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 synth = importlib.import_module("fast-genomic-data-processing_amd.synth")
 from conftest import PairHMMOracle, _ensure_oracle  # noqa: E402
+from pairhmm_fiveop_cases import DYNAMIC, HAP_N, STATIC, emulate, with_qualities  # noqa: E402
 from test_pairhmm_oracle import load_golden  # noqa: E402
-
-CSRC = os.path.join(ROOT, "fast-genomic-data-processing_amd", "csrc")
-SO = os.path.join(ROOT, "tools", "bin", "libcell_emulator.so")
-
-
-def build():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off",
-                           "-I", CSRC, "-o", SO, os.path.join(ROOT, "tools", "cell_emulator.cpp"), os.path.join(CSRC, "mgx_tables.cpp")])
-    lib = C.CDLL(SO)
-    lib.cell_emulate_batch.restype = None
-    lib.cell_emulate_paths.restype = None
-    lib.cell_emulate_deferrals.restype = None
-    return lib
-
-
-def paths(lib, n):
-    """Which way every test case of the last form-4 batch went (cell_emulator.cpp: 0 five-operation cell, 1 static deferral,
-    2 dynamic deferral, 3 haplotype with an N, 4 read too long)."""
-    out = np.empty(n, dtype=np.uint8)
-    lib.cell_emulate_paths(C.c_int(n), C.c_void_p(out.ctypes.data))
-    return out
-
-
-def deferrals(lib):
-    """(static, dynamic) deferral counts of the last form-4 batch."""
-    a, b = C.c_uint64(0), C.c_uint64(0)
-    lib.cell_emulate_deferrals(C.byref(a), C.byref(b))
-    return int(a.value), int(b.value)
-
-
-def emulate(lib, form, d):
-    n = len(d["pair_read"]) if d.get("pair_read") is not None else len(d["read_off"]) - 1
-    pr = np.ascontiguousarray(d["pair_read"] if d.get("pair_read") is not None else np.arange(n), dtype=np.uint32)
-    ph = np.ascontiguousarray(d["pair_hap"] if d.get("pair_hap") is not None else np.arange(n), dtype=np.uint32)
-    arrs = [np.ascontiguousarray(d[k]) for k in ("read_off", "hap_off", "bases", "qual", "ins", "dele", "gcp", "hap_bases")]
-    arrs[0] = arrs[0].astype(np.uint64); arrs[1] = arrs[1].astype(np.uint64)
-    res = np.empty(n, dtype=np.float32)
-    lib.cell_emulate_batch(C.c_int(form), C.c_int(n), C.c_void_p(pr.ctypes.data), C.c_void_p(ph.ctypes.data),
-                           *[C.c_void_p(a.ctypes.data) for a in arrs], C.c_void_p(res.ctypes.data))
-    with np.errstate(divide="ignore"):
-        log10 = (np.log10(res.astype(np.float32)) - np.float32(np.log10(np.float32(2.0 ** 120)))).astype(np.float64)
-    return log10, ~(res >= np.float32(1e-28))
-
-
-def with_qualities(d, seed, qual=(0, 127), ins=(0, 127), dele=(0, 127), gcp=(1, 127), zero_ins_del_rate=0.05):
-    rng = np.random.RandomState(seed)
-    nb = len(d["bases"])
-    draw = lambda r: rng.randint(r[0], r[1] + 1, nb).astype(np.uint8)  # noqa: E731
-    out = dict(d, qual=draw(qual), ins=draw(ins), dele=draw(dele), gcp=draw(gcp))
-    z = rng.rand(nb) < zero_ins_del_rate
-    out["ins"][z] = 0
-    out["dele"][z] = 0
-    return out
 
 
 def cases(quick):
@@ -96,7 +41,6 @@ def cases(quick):
 
 def main():
     quick = "--quick" in sys.argv
-    lib = build()
     oracle = PairHMMOracle(_ensure_oracle())
     print(f"{'data':36s} {'n':>6s} | {'7-op max|d|':>12s} {'flips':>5s} | {'6-op A max|d|':>12s} {'flips':>5s} | {'6-op B max|d|':>12s} {'flips':>5s}"
           f" | {'5-op max|d|':>12s} {'flips':>5s} {'static':>6s} {'dynam.':>6s} {'N/long':>6s} {'vs 6-op B':>10s}")
@@ -106,17 +50,17 @@ def main():
         row = [name[:36], len(want)]
         outs = {}
         for form in (1, 2, 3, 4):
-            got, f64 = emulate(lib, form, d)
+            got, f64, way = emulate(d, form)          # way: of the last form, 4
+            f64 = f64.astype(bool)
             keep = ~f64 & ~wused.astype(bool)
             err = float(np.abs(got[keep] - want[keep]).max()) if keep.any() else 0.0
             row += [err, int((f64 != wused.astype(bool)).sum())]
             outs[form] = (got, keep)
-        n_static, n_dynamic = deferrals(lib)
-        way = paths(lib, len(want))
+        n_static, n_dynamic = int((way == STATIC).sum()), int((way == DYNAMIC).sum())
         both = outs[3][1] & outs[4][1]
         vs6 = float(np.abs(outs[4][0][both] - outs[3][0][both]).max()) if both.any() else 0.0
         print(f"{row[0]:36s} {row[1]:6d} | {row[2]:12.3e} {row[3]:5d} | {row[4]:12.3e} {row[5]:5d} | {row[6]:12.3e} {row[7]:5d}"
-              f" | {row[8]:12.3e} {row[9]:5d} {n_static:6d} {n_dynamic:6d} {int((way >= 3).sum()):6d} {vs6:10.3e}", flush=True)
+              f" | {row[8]:12.3e} {row[9]:5d} {n_static:6d} {n_dynamic:6d} {int((way >= HAP_N).sum()):6d} {vs6:10.3e}", flush=True)
 
 
 if __name__ == "__main__":
