@@ -875,14 +875,15 @@ void scatter_region_results(const mgx_pairhmm_batch* b, const std::vector<uint64
     }
 }
 
-// every region of a whole-region call: valid, in the cross-product form, with an output if it holds test cases (total: of the call)
+// every region of a whole-region call: valid, in the cross-product form, with an output if it holds test cases (total: of the call;
+// out_log10 == nullptr: a call without outputs per test case)
 static int validate_regions(uint32_t n_regions, const mgx_pairhmm_input_t* regions, double* const* out_log10, uint64_t* total) {
     *total = 0;
     for (uint32_t g = 0; g < n_regions; ++g) {
         if (const int rc = validate(&regions[g])) return rc;
         if (regions[g].pair_read || regions[g].pair_hap) { set_error("region %u: regions are given in the cross-product form (pair arrays NULL)", g); return -EINVAL; }
         const uint64_t n = regions[g].n_reads * regions[g].n_haps;
-        if (n && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
+        if (n && out_log10 && !out_log10[g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
         *total += n;
     }
     return 0;
@@ -1082,6 +1083,34 @@ int mgx_pairhmm_regions(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_
     if (!rc) mgx_internal::regions_scatter(rb, regions, n_regions, out_log10, out_keep);
     mgx_internal::regions_end(c, &rb);
     return rc;
+}
+
+int mgx_pairhmm_regions_modified_inputs(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t* regions, const uint8_t* const* mapq,
+                                        const mgx_read_model_t* model, uint8_t* const* out_qual, uint8_t* const* out_ins, uint8_t* const* out_del,
+                                        uint8_t* const* out_gcp) {
+    if (!c || !model || (n_regions && (!regions || !mapq || !out_qual || !out_ins || !out_del || !out_gcp))) { set_error("NULL argument"); return -EINVAL; }
+    int rc;
+    uint64_t total;
+    if ((rc = validate_regions(n_regions, regions, nullptr, &total)) || total == 0) return rc;
+    uint8_t* const* const out[4] = {out_qual, out_ins, out_del, out_gcp};
+    const int seq[4] = {kSeqQual, kSeqIns, kSeqDel, kSeqGcp};
+    for (uint32_t g = 0; g < n_regions; ++g)      // every region with reads is staged and copied back, with or without haplotypes
+        for (int k = 0; k < 4 && regions[g].n_reads; ++k)
+            if (!out[k][g]) { set_error("region %u: output pointer is NULL", g); return -EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    BatchPtr b = new_batch();
+    if (!b) return -ENOMEM;
+    std::vector<uint64_t> base;
+    if ((rc = create_cross(c, n_regions, regions, b.get(), &base, mapq, model))) return rc;      // the upload and the read model, as regions_begin
+    HIP_TRY(hipEventSynchronize(b->uploaded));
+    uint64_t rb = 0;          // regions lie back to back in the batch's read arrays, each in the caller's read order (cross_stage)
+    for (uint32_t g = 0; g < n_regions; ++g) {
+        const uint64_t len = regions[g].n_reads ? regions[g].read_off[regions[g].n_reads] - regions[g].read_off[0] : 0;
+        for (int k = 0; k < 4 && len; ++k) HIP_TRY(hipMemcpy(out[k][g], b->dev(b->lay.seq[seq[k]]) + rb, len, hipMemcpyDeviceToHost));
+        rb += len;
+    }
+    mgx_pairhmm_batch_destroy(c, b.release());      // the slab goes back to the pool
+    return 0;
 }
 
 int mgx_pairhmm_best_alleles(mgx_pairhmm_t* c, uint64_t n_rows, const uint64_t* row_off, const uint32_t* row_nh, const double* values_log10,

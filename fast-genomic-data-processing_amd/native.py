@@ -90,6 +90,7 @@ PAIRHMM_SYMBOLS = {
                                               C.POINTER(PairHMMWire), C.POINTER(C.c_size_t)]),
     "mgx_pairhmm_wire_expand_host": (C.c_int, [C.POINTER(PairHMMWire)] + [C.c_void_p] * 6),
     "mgx_pairhmm_batch_read_inputs": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "mgx_pairhmm_regions_modified_inputs": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7),
     "mgx_pairhmm_table_f32": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "mgx_pairhmm_table_f64": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
 }

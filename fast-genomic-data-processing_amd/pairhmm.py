@@ -304,6 +304,34 @@ class PairHMMEngine:
                                                   C.cast(p_out, C.c_void_p), C.cast(p_keep, C.c_void_p)))
         return list(zip(outs, kept))
 
+    def regions_modified_inputs(self, regions, mapqs, **model_overrides):
+        """For tests: the read arrays as the device's read model left them, staged exactly as ``regions`` stages them (the
+        recurrence is not run).  Returns one dict of qual, ins, dele, gcp per region, each over that region's reads."""
+        n = len(regions)
+        arr = (native.PairHMMInput * n)()
+        keeps, outs, mqs = [], [], []
+        keys = ("qual", "ins", "dele", "gcp")
+        p_out = {k: (C.c_void_p * n)() for k in keys}
+        p_mq = (C.c_void_p * n)()
+        for g, d in enumerate(regions):
+            d = dict(d); d["pair_read"] = None; d["pair_hap"] = None
+            inp, keep = make_input(d)
+            arr[g] = inp; keeps.append(keep)
+            nb = int(keep["read_off"][-1] - keep["read_off"][0])
+            o = {k: np.zeros(nb, dtype=np.uint8) for k in keys}
+            mq = np.ascontiguousarray(mapqs[g], dtype=np.uint8)
+            outs.append(o); mqs.append(mq)
+            p_mq[g] = mq.ctypes.data
+            for k in keys:
+                p_out[k][g] = o[k].ctypes.data
+        m = native.ReadModel()
+        self.lib.mgx_read_model_defaults(C.byref(m))
+        for k2, v in model_overrides.items():
+            setattr(m, k2, v)
+        native.check(self.lib.mgx_pairhmm_regions_modified_inputs(self.ctx, n, C.cast(arr, C.c_void_p), C.cast(p_mq, C.c_void_p), C.byref(m),
+                                                                  *[C.cast(p_out[k], C.c_void_p) for k in keys]))
+        return outs
+
     def region(self, d, mapq, **model_overrides):
         """computeReadLikelihoods for one sample on the device: raw qualities in, normalised
         [n_reads][n_haps] log10 likelihoods and the keep mask of filterPoorlyModeledEvidence out."""

@@ -161,8 +161,9 @@ int mgx_pairhmm_sync(mgx_pairhmm_t* ctx);
  *   PairHMM               every read x every haplotype (`in` in cross-product form, raw qualities)
  *   normalizeLikelihoods  cap every haplotype at best + log10 mismapping rate  (AlleleLikelihoods.h:372-391)
  *   filterPoorlyModeledEvidence   out_keep[r] = 0 for reads it would drop      (AlleleLikelihoods.h:404-419)
- * out_log10 is [n_reads][n_haps]; mapq is one byte per read.  Parity of this row is pinned by the
- * oracle's restatement only (the reference TUs need the SAMRecord / VariantContext model). */
+ * out_log10 is [n_reads][n_haps]; mapq is one byte per read.  Parity of this row: the repeat counts of the PCR model are
+ * pinned to the reference's compiled findNumberOfRepetitions (tests/golden/read_model.npz), the rest to three independent
+ * restatements that agree. */
 typedef struct mgx_read_model {
     int pcr_rate_factor;            /* PCRErrorModel: 1 HOSTILE, 2 AGGRESSIVE, 3 CONSERVATIVE; 0 = off */
     int base_quality_threshold;     /* BASE_QUALITY_SCORE_THRESHOLD, 18 */
@@ -265,6 +266,16 @@ int mgx_pairhmm_wire_expand_host(const mgx_pairhmm_wire_t* wire, uint8_t* bases,
  * batch was created with: read_off[n_reads] each, hap_off[n_haps] for hap). */
 int mgx_pairhmm_batch_read_inputs(mgx_pairhmm_t* ctx, mgx_pairhmm_batch_t* batch, uint8_t* bases, uint8_t* qual, uint8_t* ins,
                                   uint8_t* del, uint8_t* gcp, uint8_t* hap);
+/* For tests: the four read arrays as pairhmm_read_model left them on the device.  Stages the regions exactly as
+ * mgx_pairhmm_regions does (the same upload and the same launch of the read model), does not run the recurrence, and copies
+ * region g's arrays back in the caller's read order: read_off[n_reads] - read_off[0] bytes to each of out_qual[g], out_ins[g],
+ * out_del[g], out_gcp[g].  A call without test cases (no region with both reads and haplotypes) uploads nothing and writes nothing.
+ * In a call that has test cases every region with reads is staged, modified and copied back, a region without haplotypes
+ * included: the four outputs of every region with reads must be given (-EINVAL otherwise, before anything is uploaded) and
+ * sized for it. */
+int mgx_pairhmm_regions_modified_inputs(mgx_pairhmm_t* ctx, uint32_t n_regions, const mgx_pairhmm_input_t* regions,
+                                        const uint8_t* const* mapq, const mgx_read_model_t* model, uint8_t* const* out_qual,
+                                        uint8_t* const* out_ins, uint8_t* const* out_del, uint8_t* const* out_gcp);
 
 /* The two probability tables as built by the product (for table-parity tests):
  * which = 0: ph2pr[128]; which = 1: matchToMatchProb[32640].  Returns the element count. */

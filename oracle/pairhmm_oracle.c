@@ -213,10 +213,14 @@ int ph_oracle_batch(int64_t n_pairs, const uint64_t* read_off, const uint8_t* ba
 
 /* ------------------------------------------------------------------------------------------------
  * Row F2 of SURVEY.md section 8f: the per-read quality model in front of the PairHMM and the
- * normalisation / filter behind it.  PARITY UNPINNED by a reference build: the translation units
- * (haplotypecaller/PairHMMLikelihoodCalculationEngine.cpp, utils/variant/GATKVariantContextUtils.cpp,
- * utils/genotyper/AlleleLikelihoods.h) need the whole SAMRecord / VariantContext model and htslib,
- * which cannot be built here; the restatement below follows them line by line.
+ * normalisation / filter behind it.  Parity: n_repetitions and equal_range below are pinned to the reference's own
+ * findNumberOfRepetitions (both overloads) and Utils::equalRange, compiled from utils/variant/GATKVariantContextUtils.cpp and
+ * utils/Utils.cpp where they lie (oracle/_ref/ref_read_model; answers in tests/golden/read_model.npz, compared through
+ * ph_oracle_n_repetitions on 100 000 triples).  MathUtils::fastRound does not build here (boost) and stays restated.
+ * Still restated, because haplotypecaller/PairHMMLikelihoodCalculationEngine.cpp needs the whole SAMRecord model:
+ * findTandemRepeatUnits :175-254 and the lines around it -- by three independent restatements that must agree byte for byte
+ * (this file, oracle/ref_harness/ref_read_model_harness.cpp around the linked search, tests/read_model_cases.py) -- and
+ * utils/genotyper/AlleleLikelihoods.h:153-166, 372-419 (A15), which is still boost-bound (this file and the Python).
  * ---------------------------------------------------------------------------------------------- */
 
 /* utils/Utils.cpp:9-17 */
@@ -317,3 +321,4 @@ void ph_oracle_normalize_filter(int64_t n_reads, int64_t n_haps, const uint64_t*
 }
 
 int ph_oracle_tandem_repeat(const uint8_t* bases, int length, int offset) { return tandem_repeat_units(bases, length, offset); }
+int ph_oracle_n_repetitions(const uint8_t* unit, int unit_len, const uint8_t* test, int test_len, int leading) { return n_repetitions(unit, 0, unit_len, test, 0, test_len, leading); }
