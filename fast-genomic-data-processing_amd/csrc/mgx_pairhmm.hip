@@ -299,12 +299,16 @@ void mgx_pairhmm_batch_destroy(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b) {
 
 namespace {
 
-// The plan's two environment knobs.  MGX_PAIRHMM_MIN_G=16 switches the narrow groups off (read once).  MGX_PAIRHMM_BLOCK is the
+// The plan's three environment knobs.  MGX_PAIRHMM_MIN_G=16 switches the narrow groups off (read once).  MGX_PAIRHMM_BLOCK is the
 // workgroup size of the single-class launches; 64, one wavefront per workgroup, packs LDS and VGPRs finest and needs no
-// cross-wave barriers (in-process A/B at 1 M pairs: 5.48 ms (64), 5.65 (128), 5.46 (256)).
+// cross-wave barriers (in-process A/B at 1 M pairs: 5.48 ms (64), 5.65 (128), 5.46 (256)).  MGX_PAIRHMM_MERGE_BELOW, 1 to 4096,
+// is the number of test cases below which a class is folded into the next one (merge_small_bins; anything else: kMergeBelow).
+// With 1 no class is folded, so that a test reaches the kernel of a class with a handful of test cases.  Like the workgroup
+// size it is read per batch.
 // (static, as every helper below that is new: in this file's extern "C" block a plain function of an unnamed namespace is exported)
 static int env_min_g() { static const int v = [] { const char* e = getenv("MGX_PAIRHMM_MIN_G"); return e ? atoi(e) : 4; }(); return v; }
 static uint32_t env_block() { const char* e = getenv("MGX_PAIRHMM_BLOCK"); const int v = e ? atoi(e) : 64; return v == 128 || v == 256 ? (uint32_t)v : 64u; }
+static uint64_t env_merge_below() { const char* e = getenv("MGX_PAIRHMM_MERGE_BELOW"); const long long v = e ? atoll(e) : 0; return v >= 1 && v <= (long long)kMergeBelow ? (uint64_t)v : kMergeBelow; }
 
 // the caller's six sequence arrays, in the order of SlabLayout::seq, wseq and mgx_pairhmm_batch::lay.seq
 static const uint8_t* seq_src(const mgx_pairhmm_input_t* in, int k) {
@@ -371,7 +375,7 @@ int create_cross(mgx_pairhmm_t* c, uint32_t n_regions, const mgx_pairhmm_input_t
     if (p.n == 0) return 0;
     uint64_t count[kBins] = {0};
     if ((rc = cross_tables(n_regions, regs, *out_base, env_min_g(), &p, count))) return rc;
-    if ((rc = cross_bins(&p, count, c->n_cu, env_block(), &b->bins))) return rc;      // before anything is enqueued
+    if ((rc = cross_bins(&p, count, c->n_cu, env_block(), &b->bins, env_merge_below()))) return rc;      // before anything is enqueued
     sum_stats(b);
     SlabLayout& L = b->lay;
     L.n = p.n; L.n_reads = p.nr; L.n_haps = p.nh; L.n_regions = n_regions; L.read_bytes = p.read_bytes; L.hap_bytes = p.hap_bytes;
@@ -487,7 +491,7 @@ int create_pairs(mgx_pairhmm_t* c, const mgx_pairhmm_input_t* in, const mgx::Pac
     b->n_pairs = v.n;
     b->stats.n_pairs = v.n;
     PairClasses pc;
-    if ((rc = classify_pairs(v, env_min_g(), &pc))) return rc;
+    if ((rc = classify_pairs(v, env_min_g(), &pc, env_merge_below()))) return rc;
     // one slab for everything; the layout is decided before the jobs are written so that they can be built directly in
     // the pinned mirror
     SlabLayout& L = b->lay;
@@ -835,10 +839,14 @@ int mgx_pairhmm_batch_stats(mgx_pairhmm_t* c, mgx_pairhmm_batch_t* b, mgx_pairhm
         }
         st.n_runs_timed = n_sets;
         st.ms_f32 = (float)(f32 / n_sets); st.ms_f64 = (float)(f64 / n_sets);
-        if (!force_f64) {
+        st.dominant_cells = cells_of(dom);
+        st.dominant_alg_bytes = acct ? b->acct_bytes[dom] : b->bins[dom].alg_bytes;
+        if (force_f64) {
+            // every class in its own fp64 launch (launch_class): no fp32 time
+            if (b->bins[dom].strip) snprintf(st.dominant_kernel, sizeof st.dominant_kernel, "pairhmm_fwd_strip<double>");
+            else snprintf(st.dominant_kernel, sizeof st.dominant_kernel, "pairhmm_fwd<double, %d, %d>", b->bins[dom].Gd, b->bins[dom].RPLd);
+        } else {
             st.ms_f32_dominant = (float)(domms / n_sets);
-            st.dominant_cells = cells_of(dom);
-            st.dominant_alg_bytes = acct ? b->acct_bytes[dom] : b->bins[dom].alg_bytes;
             if (acct && b->acct_multi[dom]) snprintf(st.dominant_kernel, sizeof st.dominant_kernel, "pairhmm_fwd_multi<%d>", b->acct_multi[dom] - 1);
             else snprintf(st.dominant_kernel, sizeof st.dominant_kernel, "pairhmm_fwd<float, %d, %d>", b->bins[dom].G, b->bins[dom].RPL);
         }

@@ -76,7 +76,7 @@ constexpr uint32_t kMaxLdsPerBlock = 64 * 1024;
 constexpr uint32_t kMaxLdsPerLaunch = 160 * 1024;
 constexpr size_t kStageLimit = 256u << 20;         // inputs + results beyond this are not staged through a pinned mirror
 constexpr size_t kSlabAlign = 256;                 // every array of a slab starts on a multiple of this and owns the bytes up to the next
-constexpr uint64_t kMergeBelow = 4096;             // classes with fewer test cases are folded into the next one
+constexpr uint64_t kMergeBelow = 4096;             // classes with fewer test cases are folded into the next one (default of the limit)
 constexpr uint32_t kExpandBlock = 256;             // threads per workgroup of pairhmm_expand_wire, 8 positions each
 // the last thread of an array stores its full 8 bytes, up to 7 past the array's length: they fall into the array's own
 // slab slot, which align_up rounds to a multiple of 8
@@ -163,12 +163,14 @@ inline int finalize_bin(Bin& bin, int n_cu, uint32_t block) {
 }
 // Fold sparsely populated bins into the next larger row class of the same group width (any RPL >= ceil(R / G) is
 // valid, it only leaves lanes unused): a region-sized batch then needs one fp32 + one fp64 launch instead of one pair
-// per read-length class.
-inline void merge_small_bins(uint64_t (&count)[kBins], int (&remap)[kBins]) {
+// per read-length class.  merge_below: classes of fewer test cases are folded; kMergeBelow unless MGX_PAIRHMM_MERGE_BELOW
+// says otherwise, and 1 folds none.  (The limit is the last parameter here and in classify_pairs and cross_bins, with kMergeBelow
+// as its default: the library passes it everywhere, a driver written before it existed still compiles and plans as before.)
+inline void merge_small_bins(uint64_t (&count)[kBins], int (&remap)[kBins], uint64_t merge_below = kMergeBelow) {
     for (int k = 0; k < kBins; ++k) remap[k] = k;
     for (int k = 0; k + 1 < kBins; ++k) {
         if (k + 1 == kBinG8 || k + 1 == kBinG16 || k + 1 == kBinG64 || k + 1 == kBinStrip) continue;   // never across a group-width boundary
-        if (count[k] && count[k] < kMergeBelow) { count[k + 1] += count[k]; count[k] = 0; remap[k] = k + 1; }
+        if (count[k] && count[k] < merge_below) { count[k + 1] += count[k]; count[k] = 0; remap[k] = k + 1; }
     }
     for (int k = 0; k < kBins; ++k) { int t = k; while (remap[t] != t) t = remap[t]; remap[k] = t; }
 }
@@ -192,7 +194,7 @@ struct PairClasses {
 };
 
 // bin by (G, RPL), small classes folded
-inline int classify_pairs(const PairView& v, int min_g, PairClasses* pc) {
+inline int classify_pairs(const PairView& v, int min_g, PairClasses* pc, uint64_t merge_below = kMergeBelow) {
     pc->bin_of.resize(v.n);
     for (uint64_t i = 0; i < v.n; ++i) {
         if (v.pr[i] >= v.n_reads || v.ph[i] >= v.n_haps) { set_error("test case %llu: index out of range", (unsigned long long)i); return -EINVAL; }
@@ -208,7 +210,7 @@ inline int classify_pairs(const PairView& v, int min_g, PairClasses* pc) {
         pc->max_h = std::max<uint32_t>(pc->max_h, (uint32_t)H);
     }
     int remap[kBins];
-    merge_small_bins(pc->count, remap);
+    merge_small_bins(pc->count, remap, merge_below);
     for (uint64_t i = 0; i < v.n; ++i) pc->bin_of[i] = (uint32_t)remap[pc->bin_of[i]];
     return 0;
 }
@@ -400,9 +402,9 @@ inline int cross_tables(uint32_t n_regions, const mgx_pairhmm_input_t* regs, con
 
 // Folds the small classes and makes the classes that hold any read, in job order: jobs are laid out in read-table order,
 // which is class order.
-inline int cross_bins(CrossPlan* p, uint64_t (&count)[kBins], int n_cu, uint32_t block, std::vector<Bin>* bins) {
+inline int cross_bins(CrossPlan* p, uint64_t (&count)[kBins], int n_cu, uint32_t block, std::vector<Bin>* bins, uint64_t merge_below = kMergeBelow) {
     int remap[kBins];
-    merge_small_bins(count, remap);
+    merge_small_bins(count, remap, merge_below);
     std::vector<uint64_t> sumH(p->regions.size(), 0);
     for (size_t g = 0; g < p->regions.size(); ++g)
         for (uint32_t h = 0; h < p->regions[g].n_haps; ++h) sumH[g] += p->haps[p->regions[g].hap_begin + h].len;

@@ -103,10 +103,12 @@ typedef struct mgx_pairhmm_stats {
     uint32_t n_runs_timed;
     float ms_f32;              /* sum of the fp32 recurrence kernels' durations */
     float ms_f64;              /* sum of the fp64 re-run kernels' durations */
-    float ms_f32_dominant;     /* duration of the largest fp32 launch ... */
+    float ms_f32_dominant;     /* duration of the largest fp32 launch (0 with MGX_PAIRHMM_FORCE_DOUBLE: there is none) ... */
     uint64_t dominant_cells;   /* ... and the cells / algorithmic bytes it processed */
     uint64_t dominant_alg_bytes;
-    char dominant_kernel[64];  /* its name as rocprofv3 prints it (prefix) */
+    char dominant_kernel[64];  /* its name as rocprofv3 prints it (prefix).  With MGX_PAIRHMM_FORCE_DOUBLE the three fields describe the
+                                * fp64 launch of the class that holds the most cells: pairhmm_fwd<double, G, RPL> with the class's
+                                * fp64 shape, or pairhmm_fwd_strip<double> */
     uint64_t n_exact;          /* test cases whose fp64 result was < 1e-280 (in reach of the flush-to-zero threshold) and
                                 * that were computed a third time in the reference's exact operation order (last run) */
     uint64_t n_nhap_f32;       /* test cases whose haplotype holds an N: computed by the five-code fp32 launch of their class

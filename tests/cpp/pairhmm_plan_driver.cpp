@@ -6,6 +6,7 @@
 //
 // Input, one command per line:
 //   n_cu N | min_g N | block N | stage 0/1 | model 0/1 | wire QUAL INS DEL GCP GCP_CONST      knobs (defaults 256, 4, 64, 0, 0, no wire)
+//   merge_below N                           the folding limit (MGX_PAIRHMM_MERGE_BELOW; default kMergeBelow, 1 folds nothing)
 //   reads L...   haps L...                  lengths, appended to the batch's global read / haplotype tables
 //   pairs R H R H ...                       test cases (indices), appended
 //   region R0 R1 H0 H1                      a region in the cross-product form: the sub-view reads [R0, R1) x haplotypes [H0, H1)
@@ -41,6 +42,7 @@ template <typename T> static std::unique_ptr<T[]> block(size_t n) { return std::
 
 struct Knobs {
     int n_cu = 256, min_g = 4;
+    uint64_t merge_below = kMergeBelow;
     uint32_t block = 64;
     bool stage = false, model = false, wire = false;
     mgx::wire::Widths ww;
@@ -136,7 +138,7 @@ static int plan_pairs(const Knobs& kn, const Batch& bt) {
     v.n = bt.pr.size(); v.n_reads = bt.roff.size() - 1; v.n_haps = bt.hoff.size() - 1;
     v.pr = bt.pr.data(); v.ph = bt.ph.data(); v.roff = bt.roff.data(); v.hoff = bt.hoff.data();
     PairClasses pc;
-    if (const int rc = classify_pairs(v, kn.min_g, &pc)) return fail(rc);
+    if (const int rc = classify_pairs(v, kn.min_g, &pc, kn.merge_below)) return fail(rc);
     SlabLayout L;
     L.n = v.n; L.n_reads = v.n_reads; L.n_haps = v.n_haps; L.read_bytes = bt.roff.back(); L.hap_bytes = bt.hoff.back();
     L.wire = kn.wire; L.ww = kn.ww;
@@ -163,7 +165,7 @@ static int plan_cross(const Knobs& kn, const Batch& bt) {
     uint64_t count[kBins] = {0};
     if (const int rc = cross_tables(n_regions, regs.data(), out_base, kn.min_g, &p, count)) return fail(rc);
     std::vector<Bin> bins;
-    if (const int rc = cross_bins(&p, count, kn.n_cu, kn.block, &bins)) return fail(rc);
+    if (const int rc = cross_bins(&p, count, kn.n_cu, kn.block, &bins, kn.merge_below)) return fail(rc);
     SlabLayout L;
     L.n = p.n; L.n_reads = p.nr; L.n_haps = p.nh; L.n_regions = n_regions; L.read_bytes = p.read_bytes; L.hap_bytes = p.hap_bytes;
     L.cross = true; L.model = kn.model; L.wire = kn.wire; L.ww = kn.ww;
@@ -205,6 +207,7 @@ int main(int argc, char** argv) {
         for (long long x; ss >> x;) v.push_back(x);
         if (cmd == "n_cu") kn.n_cu = (int)v.at(0);
         else if (cmd == "min_g") kn.min_g = (int)v.at(0);
+        else if (cmd == "merge_below") kn.merge_below = (uint64_t)v.at(0);
         else if (cmd == "block") kn.block = (uint32_t)v.at(0);
         else if (cmd == "stage") kn.stage = v.at(0) != 0;
         else if (cmd == "model") kn.model = v.at(0) != 0;
@@ -230,7 +233,7 @@ int main(int argc, char** argv) {
             uint64_t count[kBins];
             int remap[kBins];
             for (int k = 0; k < kBins; ++k) count[k] = (uint64_t)v.at((size_t)k);
-            merge_small_bins(count, remap);
+            merge_small_bins(count, remap, kn.merge_below);
             printf("merged");
             for (int k = 0; k < kBins; ++k) printf(" %llu", (unsigned long long)count[k]);
             printf("\nremap");

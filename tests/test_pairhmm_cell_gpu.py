@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from pairhmm_f64_cases import assert_fp64_tier_close
 from pairhmm_fiveop_cases import with_qualities
 from test_pairhmm_oracle import assert_log10_close
 
@@ -57,6 +58,7 @@ def test_strip_reads_with_varied_qualities(pkg, engine, oracle, synth, r_range, 
     eng64.close()
     assert used64.all()
     assert_log10_close(out64, want)
+    assert_fp64_tier_close(d, out64, "strip kernel, forced, varied qualities")
 
 
 def test_batch_composition_with_varied_qualities(engine, synth):

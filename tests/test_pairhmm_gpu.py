@@ -3,6 +3,7 @@ C ABI, against the CPU oracle and the reference's golden vectors."""
 import numpy as np
 import pytest
 
+from pairhmm_f64_cases import assert_fp64_tier_close
 from test_pairhmm_oracle import KEYS, TOL, assert_log10_close, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -263,6 +264,7 @@ def test_reads_longer_than_one_strip(pkg, engine, oracle, synth, r_range, h_rang
     eng64.close()
     assert used64.all()
     assert_log10_close(out64, want)
+    assert_fp64_tier_close(d, out64, "strip kernel, forced")
     q = pkg.PairHMMQueue(devices=(0,), lanes_per_device=2, batch_pairs=7)
     assert np.array_equal(q.run(d), out)
     q.close()

@@ -66,11 +66,13 @@ class PlanDriver:
         assert res.returncode == 0 and not res.stderr, res.stdout[-1000:] + res.stderr[-4000:]
         return [(ln.split()[0], ln.split()[1:]) for ln in res.stdout.splitlines()]
 
-    def plan(self, reads, haps, pairs=None, regions=None, n_cu=N_CU, min_g=4, block=64, stage=0, model=0, wire=None):
+    def plan(self, reads, haps, pairs=None, regions=None, n_cu=N_CU, min_g=4, block=64, stage=0, model=0, wire=None, merge_below=None):
         """-> dict(rc, msg, jobs, bins, slots, slab, expand, multi, narrow, order, launches, exact, + the cross tables)"""
         lines = [f"n_cu {n_cu}", f"min_g {min_g}", f"block {block}", f"stage {stage}", f"model {model}"]
         if wire:
             lines.append("wire %d %d %d %d %d" % tuple(wire))
+        if merge_below is not None:          # MGX_PAIRHMM_MERGE_BELOW; the default is the header's kMergeBelow
+            lines.append(f"merge_below {merge_below}")
         lines += ["reads " + " ".join(map(str, reads)), "haps " + " ".join(map(str, haps))]
         if pairs is not None:
             lines += ["pairs " + " ".join(f"{r} {h}" for r, h in pairs), "plan_pairs"]
@@ -153,6 +155,29 @@ def test_merge(driver):
             if c[k] >= 4096 or c[k] == 0:
                 assert rm[k] == k or m[k] == 0                            # a class is only ever folded because it is small
     assert merged[0] == [0] * 42 and merged[3] == [4096] * 42
+
+
+@pytest.mark.parametrize("limit", [1, 2, 17, 4095, 4096])
+def test_merge_limit(driver, limit):
+    """The limit as a parameter (MGX_PAIRHMM_MERGE_BELOW): classes of fewer test cases are folded, 1 folds none, 4096 is the default."""
+    rnd = random.Random(limit)
+    vectors = [[1] * 42, [limit - 1] * 42, [limit] * 42, [limit - 1, limit] * 21]
+    vectors += [[rnd.choice((0, 1, 2, 16, 17, limit - 1, limit, 5000)) for _ in range(42)] for _ in range(20)]
+    out = driver.run([f"merge_below {limit}"] + ["merge " + " ".join(map(str, c)) for c in vectors])
+    merged = [[int(x) for x in v] for kind, v in out if kind == "merged"]
+    remaps = [[int(x) for x in v] for kind, v in out if kind == "remap"]
+    assert len(merged) == len(remaps) == len(vectors)
+    for c, m, rm in zip(vectors, merged, remaps):
+        assert sum(m) == sum(c) and m == [sum(c[k] for k in range(42) if rm[k] == t) for t in range(42)]
+        for k in range(42):
+            assert m[k] == 0 or m[k] >= limit or k + 1 in WIDTH_FIRST, (k, m)
+            if c[k] >= limit or c[k] == 0:
+                assert rm[k] == k or m[k] == 0
+        if limit == 1:
+            assert m == c and rm == list(range(42))
+    if limit == 4096:          # the default: the same answer without the command
+        plain = driver.run(["merge " + " ".join(map(str, c)) for c in vectors])
+        assert [[int(x) for x in v] for kind, v in plain if kind == "merged"] == merged
 
 
 # ---- the pair-list plan ----------------------------------------------------------------------------------------------------
