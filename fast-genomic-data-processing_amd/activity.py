@@ -11,6 +11,7 @@ import numpy as np
 from . import native
 
 TIMING = 2      # MGX_PAIRHMM_TIMING
+BAND_TILE, MAX_FILTER = 256, 256      # MGX_ACTIVITY_BAND_TILE, MGX_ACTIVITY_MAX_FILTER
 READ_FIELDS = (("read_start", np.int32), ("flags", np.uint16), ("mate_start", np.int32), ("sample", np.uint8), ("act_start", np.int32),
                ("act_stop", np.int32))
 
@@ -64,6 +65,73 @@ class ActivityEngine:
     def stats(self):
         st = native.ActivityStats()
         native.check(self.lib.mgx_activity_stats(self.ctx, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in st._fields_}
+
+    def region_params(self, weights=None, **overrides):
+        """(ActivityRegionParams, the weight array it points into)"""
+        rp = native.ActivityRegionParams()
+        self.lib.mgx_activity_region_params_defaults(C.byref(rp))
+        for k, v in overrides.items():
+            setattr(rp, k, v)
+        hold = None
+        if weights is not None:
+            hold = np.ascontiguousarray(weights, dtype=np.float64)
+            rp.band_weights, rp.n_band_weights = hold.ctypes.data, len(hold)
+        return rp, hold
+
+    def band_weights(self, weights=None, **overrides):
+        """(the 2F + 1 weights a region call with these parameters uses, F); host only"""
+        rp, hold = self.region_params(weights, **overrides)
+        out, f = np.zeros(2 * MAX_FILTER + 1), C.c_int32(-1)
+        native.check(self.lib.mgx_activity_band_weights(C.byref(rp), _ptr(out), len(out), C.byref(f)))
+        del hold
+        return out[:2 * f.value + 1].copy(), int(f.value)
+
+    def profile_regions_rc(self, interval_start, prob, contig_length, weights=None, cap=None, profile=True, profile_cap=None, **overrides):
+        """The return code, the regions (int32 [n, 4]: start, end, ext_start, ext_end), the state values (or None), the counts the call
+        reported (n_regions, n_states); without raising."""
+        prob = np.ascontiguousarray(prob, dtype=np.float64)
+        rp, hold = self.region_params(weights, **overrides)
+        cap = len(prob) + 1 if cap is None else cap
+        profile_cap = len(prob) + MAX_FILTER if profile_cap is None else profile_cap
+        regions = np.full((max(cap, 1), 4), -1, dtype=np.int32)
+        values = np.full(max(profile_cap, 1), -1.0) if profile else None
+        n_regions, n_states = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.mgx_activity_profile_regions(self.ctx, int(interval_start), len(prob), _ptr(prob), int(contig_length), C.byref(rp), _ptr(regions), cap,
+                                                   C.byref(n_regions), _ptr(values) if profile else None, profile_cap, C.byref(n_states))
+        del hold
+        return rc, regions, values, (int(n_regions.value), int(n_states.value))
+
+    def profile_regions(self, interval_start, prob, contig_length, weights=None, profile=True, **overrides):
+        rc, regions, values, (n_regions, n_states) = self.profile_regions_rc(interval_start, prob, contig_length, weights, profile=profile, **overrides)
+        native.check(rc)
+        return regions[:n_regions].copy(), (values[:n_states].copy() if profile else None)
+
+    def interval_regions_rc(self, d, contig_length, weights=None, per_locus=True, profile=True, cap=None, region_params=None, **params):
+        """Reads to regions in one call.  The return code, the regions, the state values (or None), (active, log_odds, depth) (or None),
+        the counts (n_regions, n_states); without raising.  ``params`` are the per-locus parameters, ``region_params`` the regions'."""
+        inp, hold = make_input(d)
+        n = int(inp.n_loci)
+        rp, hold_w = self.region_params(weights, **(region_params or {}))
+        cap = n + 1 if cap is None else cap
+        regions = np.full((max(cap, 1), 4), -1, dtype=np.int32)
+        values = np.full(n + MAX_FILTER + 1, -1.0) if profile else None
+        loci = (np.full(n, 255, dtype=np.uint8), np.full(n, -1.0), np.full(n, 0xFFFFFFFF, dtype=np.uint32)) if per_locus else None
+        n_regions, n_states = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.mgx_activity_interval_regions(self.ctx, C.byref(inp), C.byref(self.params(**params)), int(contig_length), C.byref(rp), _ptr(regions), cap,
+                                                    C.byref(n_regions), _ptr(values) if profile else None, len(values) if profile else 0, C.byref(n_states),
+                                                    *([_ptr(a) for a in loci] if per_locus else [None, None, None]))
+        del hold, hold_w
+        return rc, regions, values, loci, (int(n_regions.value), int(n_states.value))
+
+    def interval_regions(self, d, contig_length, weights=None, per_locus=True, profile=True, region_params=None, **params):
+        rc, regions, values, loci, (n_regions, n_states) = self.interval_regions_rc(d, contig_length, weights, per_locus, profile, None, region_params, **params)
+        native.check(rc)
+        return regions[:n_regions].copy(), (values[:n_states].copy() if profile else None), loci
+
+    def region_stats(self):
+        st = native.ActivityRegionStats()
+        native.check(self.lib.mgx_activity_region_stats(self.ctx, C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in st._fields_}
 
     def last_elements(self):

@@ -24,7 +24,7 @@
 
 #include "../../include/mgx_activity.h"
 #include "activity_rule.h"
-#include "mgx_hip_util.h"      // HIP_TRY, Mirror
+#include "mgx_activity_internal.h"      // struct mgx_activity; HIP_TRY, Mirror
 #include "mgx_tables.h"
 
 using mgx::set_error;
@@ -131,29 +131,12 @@ size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
-struct mgx_activity {
-    int device = 0;
-    u32 max_depth = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // elements: 0-1, loci: 1-2
-    double* d_tables = nullptr;                          // [digamma | log10 factorial] (max_depth + 3 each) | eps | logEps | logOneMinusEps (128 each)
-    u8* d_elem = nullptr; size_t elem_cap = 0; u64 n_elem = 0;      // n_elem: what the last run wrote
-    Mirror up, down;                                     // [ReadJob | Window | running max | elements | bases | quals | reference] up | [log-odds | depth | active | too deep] down
-    mgx_activity_stats_t stats{};
-    ~mgx_activity() {
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_elem) (void)hipFree(d_elem);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 namespace {
 
 // ---- before anything is launched: the arguments, and per read its spans and its window
 struct Checked { u64 n_elements, n_cigar, n_bases; };
-int check(const mgx_activity_input_t* in, const mgx_activity_params_t* p, const u8* out_active, Checked* c) {
-    if (!in || !p || (in->n_loci && (!out_active || !in->ref_bases))) { set_error("NULL argument"); return -EINVAL; }
+int check(const mgx_activity_input_t* in, const mgx_activity_params_t* p, bool has_out_active, Checked* c) {
+    if (!in || !p || (in->n_loci && (!has_out_active || !in->ref_bases))) { set_error("NULL argument"); return -EINVAL; }
     const u64 n = in->n_reads;
     if (n && (!in->read_start || !in->cigar_off || !in->base_off || !in->flags || !in->mate_start || !in->sample || !in->act_start || !in->act_stop)) { set_error("NULL array"); return -EINVAL; }
     if (p->pcr_error_qual < 2 || p->pcr_error_qual > 254 || p->min_base_quality < 0 || p->min_base_quality > 127) { set_error("pcr_error_qual must lie in 2..254 and min_base_quality in 0..127"); return -EINVAL; }
@@ -216,12 +199,16 @@ int stage(mgx_activity* c, const mgx_activity_input_t* in, const Checked& k, Lay
     return 0;
 }
 
-int run(mgx_activity* c, const mgx_activity_input_t* in, const mgx_activity_params_t* p, u8* out_active, double* out_log_odds, u32* out_depth) {
+}  // namespace
+
+// validate -> host prefixes and the inputs into one pinned buffer -> one upload -> two launches on c->stream; nothing is downloaded
+int mgx_activity_launch_loci(mgx_activity* c, const mgx_activity_input_t* in, const mgx_activity_params_t* p, bool has_out_active, mgx_activity_loci* o) {
     if (!c) { set_error("NULL argument"); return -EINVAL; }
     c->stats = mgx_activity_stats_t{};
+    *o = mgx_activity_loci{};
     // 1. validate
     Checked k;
-    if (int rc = check(in, p, out_active, &k)) return rc;
+    if (int rc = check(in, p, has_out_active, &k)) return rc;
     const u32 n_loci = in->n_loci, n_reads = (u32)in->n_reads;
     c->stats.n_loci = n_loci; c->stats.n_elements = k.n_elements;
     if (n_loci == 0) return 0;
@@ -261,21 +248,31 @@ int run(mgx_activity* c, const mgx_activity_input_t* in, const mgx_activity_para
     c->n_elem = k.n_elements;
     if (timing) HIP_TRY(hipEventRecord(c->ev[2], s));
     HIP_TRY(hipGetLastError());
-    // 5. one download
-    HIP_TRY(hipMemcpyAsync(c->down.pin, down, down_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (timing) { HIP_TRY(hipEventElapsedTime(&c->stats.ms_elements, c->ev[0], c->ev[1])); HIP_TRY(hipEventElapsedTime(&c->stats.ms_locus, c->ev[1], c->ev[2])); }
-    const u8* pin = c->down.pin;
-    if (*(const u32*)(pin + o_deep)) { set_error("a locus is deeper than max_depth %u", c->max_depth); return -E2BIG; }
-    const u32* depth = (const u32*)(pin + o_depth);
-    for (u32 l = 0; l < n_loci; ++l) { c->stats.n_active += pin[o_active + l]; c->stats.n_callable += (int64_t)depth[l] > (int64_t)p->min_callable_depth; }
-    memcpy(out_active, pin + o_active, n_loci);
-    if (out_log_odds) memcpy(out_log_odds, pin, (size_t)n_loci * 8);
-    if (out_depth) memcpy(out_depth, depth, (size_t)n_loci * 4);
+    *o = mgx_activity_loci{n_loci, o_depth, o_active, o_deep, down_bytes};
     return 0;
 }
 
-}  // namespace
+// 5. one download: everything (`all`), or the depth flag alone; the outputs that were asked for.  n_active and n_callable are counted on the
+// host from the download, so they stay 0 without it.
+int mgx_activity_collect_loci(mgx_activity* c, const mgx_activity_loci& o, const mgx_activity_params_t* p, bool all, u8* out_active, double* out_log_odds,
+                              u32* out_depth) {
+    if (o.n_loci == 0) return 0;
+    hipStream_t s = c->stream;
+    const bool timing = (p->flags & MGX_PAIRHMM_TIMING) != 0;
+    if (all) HIP_TRY(hipMemcpyAsync(c->down.pin, c->down.dev, o.down_bytes, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(hipMemcpyAsync(c->down.pin + o.o_deep, c->down.dev + o.o_deep, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (timing) { HIP_TRY(hipEventElapsedTime(&c->stats.ms_elements, c->ev[0], c->ev[1])); HIP_TRY(hipEventElapsedTime(&c->stats.ms_locus, c->ev[1], c->ev[2])); }
+    const u8* pin = c->down.pin;
+    if (*(const u32*)(pin + o.o_deep)) { set_error("a locus is deeper than max_depth %u", c->max_depth); return -E2BIG; }
+    if (!all) return 0;
+    const u32* depth = (const u32*)(pin + o.o_depth);
+    for (u32 l = 0; l < o.n_loci; ++l) { c->stats.n_active += pin[o.o_active + l]; c->stats.n_callable += (int64_t)depth[l] > (int64_t)p->min_callable_depth; }
+    if (out_active) memcpy(out_active, pin + o.o_active, o.n_loci);
+    if (out_log_odds) memcpy(out_log_odds, pin, (size_t)o.n_loci * 8);
+    if (out_depth) memcpy(out_depth, depth, (size_t)o.n_loci * 4);
+    return 0;
+}
 
 extern "C" {
 
@@ -323,7 +320,9 @@ void mgx_activity_params_defaults(mgx_activity_params_t* p) {
 
 int mgx_activity_interval(mgx_activity_t* c, const mgx_activity_input_t* in, const mgx_activity_params_t* p, uint8_t* out_active,
                           double* out_log_odds, uint32_t* out_depth) {
-    return run(c, in, p, out_active, out_log_odds, out_depth);
+    mgx_activity_loci o;
+    if (int rc = mgx_activity_launch_loci(c, in, p, out_active != nullptr, &o)) return rc;
+    return mgx_activity_collect_loci(c, o, p, true, out_active, out_log_odds, out_depth);
 }
 
 int mgx_activity_stats(mgx_activity_t* c, mgx_activity_stats_t* out) {

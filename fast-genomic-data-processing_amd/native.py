@@ -381,7 +381,25 @@ class ActivityStats(C.Structure):
                 ("n_launches", C.c_uint32), ("ms_elements", C.c_float), ("ms_locus", C.c_float)]
 
 
+class ActivityRegionParams(C.Structure):
+    _fields_ = [("max_prob_propagation", C.c_int32), ("padding", C.c_int32), ("min_region_size", C.c_int32), ("max_region_size", C.c_int32),
+                ("max_filter_size", C.c_int32), ("adaptive_filter_size", C.c_int32), ("flags", C.c_uint32), ("n_band_weights", C.c_uint32),
+                ("active_prob_threshold", C.c_double), ("sigma", C.c_double), ("band_weights", C.c_void_p)]
+
+
+class ActivityRegionStats(C.Structure):
+    _fields_ = [("n_states", C.c_uint64), ("n_runs", C.c_uint64), ("n_regions", C.c_uint64), ("n_launches", C.c_uint32),
+                ("ms_band", C.c_float), ("ms_cut", C.c_float)]
+
+
 ACTIVITY_SYMBOLS = {
+    "mgx_activity_region_params_defaults": (None, [C.POINTER(ActivityRegionParams)]),
+    "mgx_activity_band_weights": (C.c_int, [C.POINTER(ActivityRegionParams), C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]),
+    "mgx_activity_profile_regions": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int64, C.POINTER(ActivityRegionParams), C.c_void_p,
+                                               C.c_uint64, _U64P, C.c_void_p, C.c_uint64, _U64P]),
+    "mgx_activity_interval_regions": (C.c_int, [C.c_void_p, C.POINTER(ActivityInput), C.POINTER(ActivityParams), C.c_int64, C.POINTER(ActivityRegionParams),
+                                                C.c_void_p, C.c_uint64, _U64P, C.c_void_p, C.c_uint64, _U64P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_activity_region_stats": (C.c_int, [C.c_void_p, C.POINTER(ActivityRegionStats)]),
     "mgx_activity_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mgx_activity_destroy": (None, [C.c_void_p]),
     "mgx_activity_params_defaults": (None, [C.POINTER(ActivityParams)]),

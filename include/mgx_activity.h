@@ -14,8 +14,8 @@
  *                             qualToLogProb (NaturalLogUtils.cpp:13-32)
  *
  * The rule is stated once in csrc/activity_rule.h.  What stays with the caller: the read filters, the down-sampler and the
- * adaptor boundary that give each read its pileup window (read/ReadCache.cpp:324-338), and everything behind the per-locus
- * value (ActivityProfile / BandPassActivityProfile smoothing, the cutting of regions).
+ * adaptor boundary that give each read its pileup window (read/ReadCache.cpp:324-338).  The step behind the per-locus value
+ * (ActivityProfile / BandPassActivityProfile smoothing, the cutting of regions) is mgx_activity_profile_regions below.
  * All functions return 0 or a negative errno-style code with mgx_last_error() set.  No CPU fallback.
  */
 #ifndef MGX_ACTIVITY_H
@@ -98,6 +98,66 @@ int mgx_activity_stats(mgx_activity_t* ctx, mgx_activity_stats_t* out);
  * position of its window (0 = in the pileup, not alt; 1..127 = the alt quality; 0 outside the interval).  n must be that
  * call's n_elements. */
 int mgx_activity_last_elements(mgx_activity_t* ctx, uint8_t* out, uint64_t n);
+
+/* ---- active regions from per-locus values: BandPassActivityProfile + ActivityProfile::popReadyAssemblyRegions as
+ * M2/main.cpp:267-328 drives them over ONE contiguous locus sequence (the rule: csrc/activity_profile_rule.h).  The profile is
+ * empty before the first locus and force-converted behind the last, so two halves of an interval do not compose to the whole:
+ * one call per contiguous stretch.  What stays with the caller: the `getStart() >= start && < end` filter of main.cpp:276,
+ * fillNextAssemblyRegionWithReads, and gaps in the locus sequence. */
+#define MGX_ACTIVITY_BAND_TILE 256       /* states per workgroup of the band-pass kernel */
+#define MGX_ACTIVITY_MAX_FILTER 256      /* the largest filter size F a call takes */
+
+typedef struct mgx_activity_region_params {
+    int32_t max_prob_propagation;        /* MTAC.maxProbPropagationDistance, 50; must be >= the filter size */
+    int32_t padding;                     /* assemblyRegionPadding, 100 */
+    int32_t min_region_size;             /* minAssemblyRegionSize, 50 */
+    int32_t max_region_size;             /* maxAssemblyRegionSize, 300 */
+    int32_t max_filter_size;             /* BandPassActivityProfile::MAX_FILTER_SIZE, 50 */
+    int32_t adaptive_filter_size;        /* 1 */
+    uint32_t flags;                      /* MGX_PAIRHMM_TIMING: HIP events around the band-pass kernel and around the rest */
+    uint32_t n_band_weights;             /* 2F + 1 when band_weights is given */
+    double active_prob_threshold;        /* 0.002 */
+    double sigma;                        /* BandPassActivityProfile::DEFAULT_SIGMA, 17.0 */
+    const double* band_weights;          /* NULL: makeKernel(F, sigma) as the reference builds it, in double on the host */
+} mgx_activity_region_params_t;
+
+typedef struct mgx_activity_region { int32_t start, end, ext_start, ext_end; } mgx_activity_region_t;      /* 0-based, ends inclusive */
+
+/* The region calls keep their counts in a struct and a call of their own, so that mgx_activity_stats_t keeps its layout. */
+typedef struct mgx_activity_region_stats {
+    uint64_t n_states, n_runs, n_regions;   /* of the last region call on the context */
+    uint32_t n_launches;                    /* kernels that call launched: 0 after an argument error */
+    float ms_band, ms_cut;                  /* HIP events, valid when the call asked for MGX_PAIRHMM_TIMING */
+} mgx_activity_region_stats_t;
+
+/* the values of main.cpp:197,447, band_weights NULL */
+void mgx_activity_region_params_defaults(mgx_activity_region_params_t* rp);
+/* Host only: the 2F + 1 weights a call with these parameters uses, and F.  -ENOSPC (filter_size written) when cap is too small. */
+int mgx_activity_band_weights(const mgx_activity_region_params_t* rp, double* out, uint32_t cap, int32_t* filter_size);
+/* prob[l]: the ActivityProfileState value of locus interval_start + l, in [0, 1].  out_regions: the active regions in order of
+ * start; out_profile (may be NULL): the smoothed value of every state, n_states of them (states may lie beyond the last locus,
+ * up to F behind the last locus with prob > 0, never beyond the contig).  Held equal to the reference's compiled ActivityProfile.cpp (regions equal, state
+ * values bit-equal; tests/golden/activity_regions.npz), the early return of popReadyAssemblyRegions behind an inactive piece
+ * included.  The device flushes subnormal products prob * weight.
+ * -EINVAL before anything is launched: max_prob_propagation below the filter size, a probability that is NaN or outside
+ * [0, 1], min_region_size < 1, max_region_size < min_region_size, padding < 0, contig_length not beyond the last locus, a
+ * threshold or weight that is not finite, sigma <= 0, a filter size above MGX_ACTIVITY_MAX_FILTER, an even n_band_weights.
+ * -E2BIG before anything is launched: the interval or the contig ends beyond 2^31.
+ * -ENOSPC after the run with no output written: more regions than cap (n_regions holds the count needed) or more states
+ * than profile_cap (n_states holds it). */
+int mgx_activity_profile_regions(mgx_activity_t* ctx, int32_t interval_start, uint32_t n_loci, const double* prob, int64_t contig_length,
+                                 const mgx_activity_region_params_t* rp, mgx_activity_region_t* out_regions, uint64_t cap,
+                                 uint64_t* n_regions, double* out_profile /* may be NULL */, uint64_t profile_cap, uint64_t* n_states);
+/* Reads to regions in one call: the two kernels of mgx_activity_interval, then the region kernels on the 0 / 1 bytes where the
+ * second left them on the device, on one stream.  The regions (and profile) are those of mgx_activity_profile_regions fed with
+ * out_active.  out_active, out_log_odds, out_depth may each be NULL; the per-locus arrays are downloaded only when one of them
+ * is asked for, and mgx_activity_stats' n_active / n_callable are counted only then.  Every argument error of either call
+ * before anything is launched; -E2BIG (a locus deeper than max_depth) before any region kernel, nothing written. */
+int mgx_activity_interval_regions(mgx_activity_t* ctx, const mgx_activity_input_t* in, const mgx_activity_params_t* p, int64_t contig_length,
+                                  const mgx_activity_region_params_t* rp, mgx_activity_region_t* out_regions, uint64_t cap,
+                                  uint64_t* n_regions, double* out_profile /* may be NULL */, uint64_t profile_cap, uint64_t* n_states,
+                                  uint8_t* out_active /* may be NULL */, double* out_log_odds /* may be NULL */, uint32_t* out_depth /* may be NULL */);
+int mgx_activity_region_stats(mgx_activity_t* ctx, mgx_activity_region_stats_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,11 @@
 // activity_host_pass.cpp -- csrc/activity_rule.h over one mgx_activity_input_t serially on one host thread: the yardstick tools/dev_activity.py
 // prints next to the device call (scale only; the input is taken as mgx_activity_interval has validated it).  Built by that tool into
-// tools/bin/; not part of libmgx.so.
+// tools/bin/; not part of libmgx.so.  activity_profile_host_pass is the same yardstick for the step behind it: csrc/activity_profile_rule.h's
+// serial pass over the 0 / 1 values with the default band.
 #include <cstdint>
 #include <vector>
 
+#include "activity_profile_rule.h"
 #include "activity_rule.h"
 #include "mgx_activity.h"
 #include "mgx_tables.h"
@@ -59,4 +61,20 @@ extern "C" int activity_host_pass(const mgx_activity_input_t* in, const mgx_acti
         out_active[l] = L.active; out_log_odds[l] = L.log_odds; out_depth[l] = L.depth;
     }
     return 0;
+}
+
+// out_regions: room for n_loci + 1 regions.  Returns the number of regions.
+extern "C" int64_t activity_profile_host_pass(int32_t interval_start, uint32_t n_loci, const uint8_t* active, int64_t contig_length,
+                                              const mgx_activity_region_params_t* rp, mgx_activity_region_t* out_regions) {
+    namespace PR = mgx_activity_profile_rule;
+    std::vector<double> w(2 * (size_t)rp->max_filter_size + 1);
+    const int filter = PR::band_weights(rp->max_filter_size, rp->sigma, rp->adaptive_filter_size != 0, w.data());
+    const PR::CutParams c{rp->min_region_size, rp->max_region_size, rp->max_prob_propagation, filter};
+    const int64_t upper = PR::states_upper(interval_start, n_loci, filter, contig_length);
+    std::vector<double> values((size_t)upper);
+    std::vector<uint32_t> heads((size_t)upper / 2 + 1), tails((size_t)upper / 2 + 1);
+    int64_t n = 0;
+    PR::serial_pass(interval_start, n_loci, [&](int64_t p) { return (double)active[p]; }, [&](int64_t k) { return w[k]; }, c, rp->active_prob_threshold, rp->padding,
+                    contig_length, values.data(), heads.data(), tails.data(), false, [&](const PR::Region& r) { out_regions[n++] = mgx_activity_region_t{r.start, r.end, r.ext_start, r.ext_end}; });
+    return n;
 }

@@ -25,10 +25,10 @@ READ_LEN = (100, 151)
 def build():
     os.makedirs(os.path.dirname(HOST), exist_ok=True)
     src = os.path.join(ROOT, "tools", "activity_host_pass.cpp")
-    deps = [src, os.path.join(PKGDIR, "csrc", "activity_rule.h"), os.path.join(PKGDIR, "csrc", "mgx_tables.cpp")]
+    deps = [src, os.path.join(PKGDIR, "csrc", "activity_rule.h"), os.path.join(PKGDIR, "csrc", "activity_profile_rule.h"), os.path.join(PKGDIR, "csrc", "mgx_tables.cpp")]
     if os.path.exists(HOST) and os.path.getmtime(HOST) >= max(os.path.getmtime(d) for d in deps):
         return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKGDIR, "csrc"), src,
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKGDIR, "csrc"), src,
                            os.path.join(PKGDIR, "csrc", "mgx_tables.cpp"), "-o", HOST])
 
 
@@ -95,12 +95,54 @@ def measure(pkg, host, name, d, rounds):
     return lines
 
 
+def measure_regions(pkg, host, name, d, rounds):
+    """interval_regions (reads to regions, one call) against interval + the header's serial profile pass on the host: wall times, the two
+    new kernel groups' times (HIP events), the bytes each way downloads, the regions compared"""
+    act = pkg.ActivityEngine(0)
+    n = len(d["ref_bases"])
+    contig = int(d["interval_start"]) + n + 1000
+
+    def wall(f):
+        t0 = time.perf_counter(); out = f(); return (time.perf_counter() - t0) * 1e3, out
+    fused = lambda: act.interval_regions(d, contig, per_locus=False, profile=False, has_normal=1)
+    wall(fused)                                                               # the warm-up
+    t_fused = [wall(fused)[0] for _ in range(rounds)]
+    ms_band, ms_cut = [], []
+    for _ in range(rounds):
+        act.interval_regions(d, contig, per_locus=False, profile=False, region_params=dict(flags=pkg.activity.TIMING), has_normal=1)
+        st = act.region_stats()
+        ms_band.append(st["ms_band"]); ms_cut.append(st["ms_cut"])
+    regions = fused()[0]
+    rp, _ = act.region_params()
+    out = np.zeros((n + 1, 4), np.int32)
+
+    def two_steps():
+        active = act.interval(d, has_normal=1)[0]
+        k = host.activity_profile_host_pass(int(d["interval_start"]), n, active.ctypes.data_as(C.c_void_p), contig, C.byref(rp), out.ctypes.data_as(C.c_void_p))
+        return out[:k]
+    wall(two_steps)
+    t_two = [wall(two_steps)[0] for _ in range(rounds)]
+    same = np.array_equal(two_steps(), regions)
+    st = act.region_stats()
+    lines = [f"== {name}: {n} loci, {len(d['read_start'])} reads; {int(st['n_states'])} states, {int(st['n_runs'])} runs, {len(regions)} regions",
+             f"mgx_activity_interval_regions, wall time of the call              {stat(t_fused)}; downloads {16 * len(regions) + 512} bytes",
+             f"  k_band_pass (HIP events)                                        {stat(ms_band)}",
+             f"  runs, k_cut_runs, regions (HIP events, one small download in)   {stat(ms_cut)}",
+             f"mgx_activity_interval + serial host pass of the profile rule      {stat(t_two)}; downloads {13 * n} bytes",
+             f"regions identical {same}", ""]
+    act.close()
+    print("\n".join(lines), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "activity_ab.txt"))
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--loci", type=int, default=1_000_000)
     ap.add_argument("--build-only", action="store_true")
+    ap.add_argument("--regions-out", default=os.path.join(ROOT, "profiles", "activity_regions_ab.txt"))
+    ap.add_argument("--regions-only", action="store_true")
     a = ap.parse_args()
     build()
     if a.build_only:
@@ -114,11 +156,19 @@ def main():
     base = pkg.synth.gen_activity_interval(int(a.loci * 30 / mean_len), a.loci, 0xAC7, len_range=READ_LEN)
     text = ["mgx_activity_interval on one MI355X: one interval per call, one warm-up, then %d rounds; median and max - min." % a.rounds,
             "HBM bytes by hardware counters: not measured; the bytes below are what the algorithm needs.", ""]
-    text += measure(pkg, host, "depth 30", base, a.rounds)
-    text += measure(pkg, host, "depth 300", repeated(base, 10), a.rounds)
+    host.activity_profile_host_pass.restype = C.c_int64
+    host.activity_profile_host_pass.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    rtext = ["Reads to regions on one MI355X: one interval per call, one warm-up, then %d rounds; median and max - min." % a.rounds, ""]
+    for name, d in (("depth 30", base), ("depth 300", repeated(base, 10))):
+        if not a.regions_only:
+            text += measure(pkg, host, name, d, a.rounds)
+        rtext += measure_regions(pkg, host, name, d, a.rounds)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(text))
+    if not a.regions_only:
+        with open(a.out, "w") as f:
+            f.write("\n".join(text))
+    with open(a.regions_out, "w") as f:
+        f.write("\n".join(rtext))
     return 0
 
 
