@@ -218,13 +218,7 @@ int mgx_activity_launch_loci(mgx_activity* c, const mgx_activity_input_t* in, co
     if (int rc = stage(c, in, k, &L)) return rc;
     const size_t o_depth = up256((size_t)n_loci * 8), o_active = o_depth + up256((size_t)n_loci * 4), o_deep = o_active + up256(n_loci), down_bytes = o_deep + 256;
     if (int rc = c->down.reserve(down_bytes)) return rc;
-    if (k.n_elements > c->elem_cap) {
-        if (c->d_elem) (void)hipFree(c->d_elem);
-        c->d_elem = nullptr; c->elem_cap = 0;
-        const size_t want = k.n_elements + k.n_elements / 4 + 256;
-        HIP_TRY(hipMalloc((void**)&c->d_elem, want));
-        c->elem_cap = want;
-    }
+    if (int rc = c->elem.reserve(k.n_elements, k.n_elements + k.n_elements / 4 + 256)) return rc;
     // 3. one upload
     hipStream_t s = c->stream;
     const bool timing = (p->flags & MGX_PAIRHMM_TIMING) != 0;
@@ -235,14 +229,14 @@ int mgx_activity_launch_loci(mgx_activity* c, const mgx_activity_input_t* in, co
     if (timing) HIP_TRY(hipEventRecord(c->ev[0], s));
     if (k.n_elements) {
         hipLaunchKernelGGL(k_pileup_elements, dim3((n_reads + 3) / 4), dim3(256), 0, s, (const ReadJob*)up, (const u32*)(up + L.o_cigar), up + L.o_bases,
-                           up + L.o_quals, up + L.o_ref, in->interval_start, n_loci, n_reads, R::ElementParams{p->pcr_error_qual, p->min_base_quality}, c->d_elem);
+                           up + L.o_quals, up + L.o_ref, in->interval_start, n_loci, n_reads, R::ElementParams{p->pcr_error_qual, p->min_base_quality}, c->elem.p);
         c->stats.n_launches++;
     }
     if (timing) HIP_TRY(hipEventRecord(c->ev[1], s));
     const u32 n_counts = c->max_depth + 3;
     const R::Tables T{c->d_tables, c->d_tables + n_counts, c->d_tables + 2 * (size_t)n_counts, c->d_tables + 2 * (size_t)n_counts + 128, c->d_tables + 2 * (size_t)n_counts + 256};
     hipLaunchKernelGGL(k_locus_activity, dim3((n_loci + 255) / 256), dim3(256), 0, s, (const Window*)(up + L.o_win), (const int32_t*)(up + L.o_max), n_reads,
-                       c->d_elem, in->interval_start, n_loci, T, R::LocusParams{p->has_normal, p->genotype_germline_sites, p->initial_log_odds}, c->max_depth,
+                       c->elem.p, in->interval_start, n_loci, T, R::LocusParams{p->has_normal, p->genotype_germline_sites, p->initial_log_odds}, c->max_depth,
                        down + o_active, (double*)down, (u32*)(down + o_depth), (u32*)(down + o_deep));
     c->stats.n_launches++;
     c->n_elem = k.n_elements;
@@ -279,25 +273,19 @@ extern "C" {
 int mgx_activity_create(int device, uint32_t max_depth, mgx_activity_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        set_error("no HIP device is visible (this library has no CPU fallback)");
-        return -ENODEV;
-    }
-    if (device == -1) device = 0;
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range", device); return -EINVAL; }
+    if (const int rc = mgx_hip::pick_device(&device, nullptr)) return rc;
     if (max_depth == 0) max_depth = MGX_ACTIVITY_DEFAULT_MAX_DEPTH;
     if (max_depth > (1u << 24)) { set_error("max_depth above 2^24"); return -E2BIG; }
-    HIP_TRY(hipSetDevice(device));
     std::unique_ptr<mgx_activity> c(new (std::nothrow) mgx_activity);
     if (!c) return -ENOMEM;
     c->device = device; c->max_depth = max_depth;
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
+    mgx_hip::Owner& m = c->own;
+    m.stream(&c->stream);
+    for (auto& e : c->ev) m.event(&e);
     mgx::ActivityTables t;
     const u32 n_counts = max_depth + 3;
     mgx::build_activity_tables(n_counts, &t);
-    HIP_TRY(hipMalloc((void**)&c->d_tables, (2 * (size_t)n_counts + 3 * 128) * sizeof(double)));
+    if (!m.device(&c->d_tables, (2 * (size_t)n_counts + 3 * 128) * sizeof(double))) return m.error("an activity context");
     HIP_TRY(hipMemcpy(c->d_tables, t.digamma.data(), n_counts * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_tables + n_counts, t.log10_factorial.data(), n_counts * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_tables + 2 * (size_t)n_counts, t.eps, 128 * sizeof(double), hipMemcpyHostToDevice));
@@ -335,7 +323,7 @@ int mgx_activity_last_elements(mgx_activity_t* c, uint8_t* out, uint64_t n) {
     if (!c || (n && !out)) { set_error("NULL argument"); return -EINVAL; }
     if (n != c->n_elem) { set_error("the last call wrote %llu elements, not %llu", (unsigned long long)c->n_elem, (unsigned long long)n); return -EINVAL; }
     HIP_TRY(hipSetDevice(c->device));
-    if (n) HIP_TRY(hipMemcpy(out, c->d_elem, n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(out, c->elem.p, n, hipMemcpyDeviceToHost));
     return 0;
 }
 

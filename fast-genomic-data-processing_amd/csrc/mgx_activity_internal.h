@@ -2,37 +2,29 @@
 // mgx_activity_regions.hip (band-pass profile and region cutting).  Internal to libmgx.so, HIP only.
 #pragma once
 #include "../../include/mgx_activity.h"
-#include "mgx_hip_util.h"      // HIP_TRY, Mirror
+#include "mgx_hip_util.h"      // HIP_TRY, Owner, Mirror, DevArray
 
 // what the region calls keep between calls: [weights | probabilities] up, [counts | state values] down, the regions down, and the
 // device-only arrays (flags, piece ends, run heads, scan output and its partial sums) in one block
 struct mgx_activity_regions_work {
     mgx_hip::Mirror up, down, out;
-    uint8_t* d_work = nullptr; size_t work_cap = 0;
+    mgx_hip::DevArray<uint8_t> work;
     mgx_activity_region_stats_t stats{};
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // band-pass: 0-1, run heads + cutter + compaction: 1-2
-    ~mgx_activity_regions_work() {
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (d_work) (void)hipFree(d_work);
-    }
+    ~mgx_activity_regions_work() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 struct mgx_activity {
+    mgx_hip::Owner own;                                  // of the stream, the events and the tables; the first member: the stream goes last
     int device = 0;
     uint32_t max_depth = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // elements: 0-1, loci: 1-2
     double* d_tables = nullptr;                          // [digamma | log10 factorial] (max_depth + 3 each) | eps | logEps | logOneMinusEps (128 each)
-    uint8_t* d_elem = nullptr; size_t elem_cap = 0; uint64_t n_elem = 0;      // n_elem: what the last run wrote
+    mgx_hip::DevArray<uint8_t> elem; uint64_t n_elem = 0;                     // n_elem: what the last run wrote
     mgx_hip::Mirror up, down;                                     // [ReadJob | Window | running max | elements | bases | quals | reference] up | [log-odds | depth | active | too deep] down
     mgx_activity_stats_t stats{};
     mgx_activity_regions_work regions;                   // mgx_activity_regions.hip
-    ~mgx_activity() {
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_elem) (void)hipFree(d_elem);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 // mgx_activity.hip's two halves of a call, for the fused call of mgx_activity_regions.hip: where the per-locus arrays lie in ctx->down.dev

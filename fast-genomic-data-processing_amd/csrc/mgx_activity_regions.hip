@@ -197,12 +197,7 @@ int regions_of(mgx_activity* c, int32_t interval_start, u32 n_loci, const double
                  work_bytes = o_part + up256((n / mgx_hip::kScanChunk + 2) * 8);
     if (int rc = W.up.reserve(up_bytes)) return rc;
     if (int rc = W.down.reserve(down_bytes)) return rc;
-    if (work_bytes > W.work_cap) {
-        if (W.d_work) (void)hipFree(W.d_work);
-        W.d_work = nullptr; W.work_cap = 0;
-        HIP_TRY(hipMalloc((void**)&W.d_work, work_bytes + work_bytes / 4));
-        W.work_cap = work_bytes + work_bytes / 4;
-    }
+    if (int rc = W.work.reserve(work_bytes, work_bytes + work_bytes / 4)) return rc;
     memcpy(W.up.pin, w, n_w * 8);
     if (prob) memcpy(W.up.pin + o_prob, prob, (size_t)n_loci * 8);
     // 3. one upload, then the kernels on one stream
@@ -210,8 +205,8 @@ int regions_of(mgx_activity* c, int32_t interval_start, u32 n_loci, const double
     const bool timing = (rp->flags & MGX_PAIRHMM_TIMING) != 0;
     const double* d_w = (const double*)W.up.dev; const double* d_prob = (const double*)(W.up.dev + o_prob);          // d_active: the fused call's source
     u64* d_counts = (u64*)W.down.dev; double* d_value = (double*)(W.down.dev + o_value);
-    u8* d_flag = W.d_work; int32_t* d_piece = (int32_t*)(W.d_work + o_piece); u32* d_heads = (u32*)(W.d_work + o_heads); u32* d_tails = (u32*)(W.d_work + o_tails);
-    u64* d_rank = (u64*)(W.d_work + o_rank); u64* d_part = (u64*)(W.d_work + o_part);
+    u8* d_flag = W.work.p; int32_t* d_piece = (int32_t*)(W.work.p + o_piece); u32* d_heads = (u32*)(W.work.p + o_heads); u32* d_tails = (u32*)(W.work.p + o_tails);
+    u64* d_rank = (u64*)(W.work.p + o_rank); u64* d_part = (u64*)(W.work.p + o_part);
     HIP_TRY(hipMemcpyAsync(W.up.dev, W.up.pin, up_bytes, hipMemcpyHostToDevice, s));
     if (timing) HIP_TRY(hipEventRecord(W.ev[0], s));
     const dim3 tiles((u32)((n + 1 + PR::kBandTile - 1) / PR::kBandTile));

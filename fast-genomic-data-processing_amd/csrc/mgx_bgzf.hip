@@ -808,15 +808,6 @@ int check_block_range(const u64* offsets, u64 first, u64 count) {
     return 0;
 }
 
-// *device (negative: 0) is one of the HIP devices
-int check_device(int* device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device: the BGZF compressor has no CPU path"); return -ENODEV; }
-    if (*device < 0) *device = 0;
-    if (*device >= n_dev) { set_error("device %d of %d", *device, n_dev); return -EINVAL; }
-    return 0;
-}
-
 // ---- host: the steps of a batch's submit --------------------------------------------------------------------------------------
 int validate_batch(const mgx_bgzf_batch_t* b, u32 n_blocks) {
     if (n_blocks > b->max_blocks) { set_error("%u blocks in a batch made for %u", n_blocks, b->max_blocks); return -EINVAL; }
@@ -920,8 +911,7 @@ uint64_t mgx_bgzf_bound(uint64_t n_bytes, uint64_t n_blocks) { return n_bytes + 
 int mgx_bgzf_create(int device, unsigned flags, mgx_bgzf_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
-    if (const int rc = check_device(&device)) return rc;
-    HIP_TRY(hipSetDevice(device));
+    if (const int rc = mgx_hip::pick_device(&device, nullptr, true)) return rc;      // every negative ordinal: device 0
     std::unique_ptr<mgx_bgzf> c(new (std::nothrow) mgx_bgzf);
     if (!c) { set_error("out of memory"); return -ENOMEM; }
     c->device = device;
@@ -932,9 +922,8 @@ int mgx_bgzf_create(int device, unsigned flags, mgx_bgzf_t** out) {
     if (const char* e = getenv("MGX_BGZF_LAZY")) c->lazy = atoi(e) != 0;
     if (const char* e = getenv("MGX_BGZF_COST_BASE")) c->cost_base = (u32)atoi(e);
     if (const char* e = getenv("MGX_BGZF_COST_RLE")) c->cost_rle = (u32)atoi(e);
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c->up, hipStreamNonBlocking));
+    c->own.stream(&c->stream); c->own.stream(&c->copy); c->own.stream(&c->up);
+    if (!c->own.ok()) return c->own.error("a BGZF context");
     // one workgroup per CU (157 KB of LDS, 1024 threads x 128 registers: a CU that runs one has no register left for anything
     // else, so the pack kernel of the batch before cannot run BESIDE a deflate kernel, only between two).  Leaving 8 or 16 CUs
     // free for it was measured: the deflate kernel then takes 9 rounds instead of 8 over a 2048-block batch (3.39 against
@@ -953,13 +942,14 @@ int mgx_bgzf_prepare(mgx_bgzf_t* c) {
     std::lock_guard<std::mutex> g(c->prep_mu);
     if (c->prepared) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc((void**)&c->d_scratch, (size_t)c->grid * kScratchPerWg * sizeof(u32)));
-    HIP_TRY(hipMalloc((void**)&c->d_n_stored, sizeof(u32)));
+    mgx_hip::Owner& m = c->own;
+    const char* prof = getenv("MGX_BGZF_PROF");
+    m.device(&c->d_scratch, (size_t)c->grid * kScratchPerWg * sizeof(u32));
+    m.device(&c->d_n_stored, sizeof(u32));
+    if (prof && atoi(prof)) m.device(&c->d_prof, kProfSlots * sizeof(unsigned long long));
+    if (!m.ok()) { c->d_n_stored = nullptr; return m.error("the compressor's scratch"); }
     HIP_TRY(hipMemsetAsync(c->d_n_stored, 0, sizeof(u32), c->stream));
-    if (const char* e = getenv("MGX_BGZF_PROF")) if (atoi(e)) {
-        HIP_TRY(hipMalloc((void**)&c->d_prof, kProfSlots * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(c->d_prof, 0, kProfSlots * sizeof(unsigned long long), c->stream));
-    }
+    if (c->d_prof) HIP_TRY(hipMemsetAsync(c->d_prof, 0, kProfSlots * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipFuncSetAttribute((const void*)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Lds)));
     c->prepared = true;
     return 0;
@@ -967,8 +957,7 @@ int mgx_bgzf_prepare(mgx_bgzf_t* c) {
 
 int mgx_bgzf_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
     if (!free_bytes || !total_bytes) { set_error("NULL argument"); return -EINVAL; }
-    if (const int rc = check_device(&device)) return rc;
-    HIP_TRY(hipSetDevice(device));
+    if (const int rc = mgx_hip::pick_device(&device, nullptr, true)) return rc;      // every negative ordinal: device 0
     size_t f = 0, t = 0;
     HIP_TRY(hipMemGetInfo(&f, &t));
     *free_bytes = f; *total_bytes = t;
@@ -978,11 +967,7 @@ int mgx_bgzf_device_memory(int device, uint64_t* free_bytes, uint64_t* total_byt
 void mgx_bgzf_destroy(mgx_bgzf_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
-    if (c->up) { (void)hipStreamSynchronize(c->up); (void)hipStreamDestroy(c->up); }
-    (void)hipFree(c->d_scratch);
-    (void)hipFree(c->d_n_stored);
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy); (void)hipStreamSynchronize(c->up);
     if (c->d_prof) {
         unsigned long long p[kProfSlots];
         if (hipMemcpy(p, c->d_prof, sizeof p, hipMemcpyDeviceToHost) == hipSuccess && c->n_blocks) {
@@ -993,7 +978,6 @@ void mgx_bgzf_destroy(mgx_bgzf_t* c) {
                     p[P_A_MATCH], p[P_A_PARSE], p[P_A_PRODUCE], p[P_B_TOKENS]);
             fprintf(stderr, "   literal/length code: setup %llu, rank %llu, merge rounds %llu, depths %llu, limit + code values %llu\n", p[P_LL_SETUP], p[P_LL_RANK], p[P_LL_MERGE], p[P_LL_DEPTHS], p[P_LL_ASSIGN]);
         }
-        (void)hipFree(c->d_prof);
     }
     delete c;
 }

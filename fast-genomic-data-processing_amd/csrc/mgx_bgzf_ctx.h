@@ -9,6 +9,7 @@
 #include "mgx_hip_util.h"
 
 struct mgx_bgzf {
+    mgx_hip::Owner own;                        // of the streams and the compressor's device state; the first member: the streams go last
     int device = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;              // all batches of a context run in order on one stream

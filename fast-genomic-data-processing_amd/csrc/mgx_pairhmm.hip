@@ -49,6 +49,7 @@ constexpr size_t kMinSlab = 1u << 20;
 }  // namespace
 
 struct mgx_pairhmm {
+    mgx_hip::Owner own;          // of the streams and the tables below; the first member: the streams go last
     int device = 0;
     unsigned flags = 0;
     hipStream_t compute = nullptr, copy = nullptr, d2h = nullptr;   // kernels | uploads | result downloads
@@ -58,8 +59,12 @@ struct mgx_pairhmm {
     int n_cu = 256;
     bool wire = false;           // MGX_PAIRHMM_WIRE, or its environment override: staged pair-list batches upload the wire form
     std::vector<Slab> free_slabs;
-    void* d_strip = nullptr; size_t strip_cap = 0;      // boundary rows of the strip-mined class (one compute stream: launches do not overlap)
+    mgx_hip::DevArray<uint8_t> strip;                   // boundary rows of the strip-mined class (one compute stream: launches do not overlap)
     mgx_internal::PairhmmExt ext;                       // mgx_realign.hip's buffers and statistics
+    ~mgx_pairhmm() {
+        if (ext.p && ext.free_fn) ext.free_fn(ext.p);
+        for (auto& sl : free_slabs) { (void)hipFree(sl.dev); if (sl.pin) (void)hipHostFree(sl.pin); }
+    }
 };
 
 struct mgx_pairhmm_batch {
@@ -96,13 +101,10 @@ BatchPtr new_batch() {
     return BatchPtr(new (std::nothrow) mgx_pairhmm_batch, [](mgx_pairhmm_batch* p) { mgx_pairhmm_batch_destroy(nullptr, p); });
 }
 
+// a table of the context, owned by `own`; the copy is queued on s
 template <typename T>
-int upload(T** dst, const void* src, size_t bytes, hipStream_t s) {
-    *dst = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc((void**)dst, bytes));
-    if (src) HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
+void upload(mgx_hip::Owner& own, T** dst, const std::vector<T>& src, hipStream_t s) {
+    if (own.device(dst, src.size() * sizeof(T))) own.note(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s), "hipMemcpyAsync");
 }
 
 // ---- the wire form's device side (pairhmm_wire.h): one launch on the copy stream, right behind the H2D copy, turns
@@ -211,17 +213,8 @@ int mgx_pairhmm_table_f64(int which, const double** out) { return host_table(whi
 int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        set_error("no HIP device is visible (this library has no CPU fallback)");
-        return -ENODEV;
-    }
-    if (device == -1) {                 // MGX_DEVICE_AUTO: contexts are dealt round-robin over the visible GPUs
-        static std::atomic<unsigned> next{0};
-        device = (int)(next.fetch_add(1) % (unsigned)n_dev);
-    }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (0..%d)", device, n_dev - 1); return -EINVAL; }
-    HIP_TRY(hipSetDevice(device));
+    static std::atomic<unsigned> next{0};      // MGX_DEVICE_AUTO: contexts are dealt round-robin over the visible GPUs
+    if (const int rc = mgx_hip::pick_device(&device, &next)) return rc;
     std::unique_ptr<mgx_pairhmm> c(new (std::nothrow) mgx_pairhmm);
     if (!c) return -ENOMEM;
     c->device = device;
@@ -231,36 +224,19 @@ int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     c->n_cu = prop.multiProcessorCount;
-    {
-        // optional CU partition (flags bits 8..15: an 8-bit pattern repeated over the CU index): lets a
-        // VALU-bound PairHMM context and an HBM-bound sort context share one GPU side by side instead
-        // of queueing behind each other (BASELINE.json configs[4])
-        const unsigned pat = (flags >> 8) & 0xFFu;
-        if (pat != 0 && pat != 0xFFu) {
-            const int n_words = (c->n_cu + 31) / 32;
-            std::vector<uint32_t> mask(n_words, 0);
-            for (int cu = 0; cu < c->n_cu; ++cu) if ((pat >> (cu & 7)) & 1u) mask[cu >> 5] |= 1u << (cu & 31);
-            HIP_TRY(hipExtStreamCreateWithCUMask(&c->compute, (uint32_t)n_words, mask.data()));
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(&c->compute, hipStreamNonBlocking));
-        }
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c->d2h, hipStreamNonBlocking));
+    mgx_hip::Owner& m = c->own;
+    m.stream(&c->compute, c->n_cu, (flags >> 8) & 0xFFu);
+    m.stream(&c->copy); m.stream(&c->d2h);
     const auto& tf = mgx::tables<float>();
     const auto& td = mgx::tables<double>();
-    int rc;
-    if ((rc = upload(&c->d_ph2pr_f, tf.ph2pr.data(), tf.ph2pr.size() * 4, c->compute))) return rc;
-    if ((rc = upload(&c->d_mm_f, tf.mm.data(), tf.mm.size() * 4, c->compute))) return rc;
-    if ((rc = upload(&c->d_ph2pr_d, td.ph2pr.data(), td.ph2pr.size() * 8, c->compute))) return rc;
-    if ((rc = upload(&c->d_mm_d, td.mm.data(), td.mm.size() * 8, c->compute))) return rc;
-    if ((rc = upload(&c->d_div3_f, tf.ph2pr_div3.data(), tf.ph2pr_div3.size() * 4, c->compute))) return rc;
-    if ((rc = upload(&c->d_ratio_f, tf.gap_ratio.data(), tf.gap_ratio.size() * 4, c->compute))) return rc;
-    if ((rc = upload(&c->d_div3_d, td.ph2pr_div3.data(), td.ph2pr_div3.size() * 8, c->compute))) return rc;
-    if ((rc = upload(&c->d_ratio_d, td.gap_ratio.data(), td.gap_ratio.size() * 8, c->compute))) return rc;
+    upload(m, &c->d_ph2pr_f, tf.ph2pr, c->compute); upload(m, &c->d_mm_f, tf.mm, c->compute);
+    upload(m, &c->d_ph2pr_d, td.ph2pr, c->compute); upload(m, &c->d_mm_d, td.mm, c->compute);
+    upload(m, &c->d_div3_f, tf.ph2pr_div3, c->compute); upload(m, &c->d_ratio_f, tf.gap_ratio, c->compute);
+    upload(m, &c->d_div3_d, td.ph2pr_div3, c->compute); upload(m, &c->d_ratio_d, td.gap_ratio, c->compute);
     c->log10_initial_f = tf.log10_initial;
     c->log10_initial_d = td.log10_initial;
-    HIP_TRY(hipStreamSynchronize(c->compute));
+    if (m.ok()) m.note(hipStreamSynchronize(c->compute), "hipStreamSynchronize");
+    if (!m.ok()) return m.error("a PairHMM context");
     *out = c.release();
     return 0;
 }
@@ -268,15 +244,6 @@ int mgx_pairhmm_create(int device, unsigned flags, mgx_pairhmm_t** out) {
 void mgx_pairhmm_destroy(mgx_pairhmm_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->ext.p && c->ext.free_fn) c->ext.free_fn(c->ext.p);
-    (void)hipFree(c->d_ph2pr_f); (void)hipFree(c->d_mm_f);
-    (void)hipFree(c->d_ph2pr_d); (void)hipFree(c->d_mm_d);
-    (void)hipFree(c->d_div3_f); (void)hipFree(c->d_ratio_f); (void)hipFree(c->d_div3_d); (void)hipFree(c->d_ratio_d);
-    for (auto& sl : c->free_slabs) { (void)hipFree(sl.dev); if (sl.pin) (void)hipHostFree(sl.pin); }
-    (void)hipFree(c->d_strip);
-    if (c->compute) (void)hipStreamDestroy(c->compute);
-    if (c->copy) (void)hipStreamDestroy(c->copy);
-    if (c->d2h) (void)hipStreamDestroy(c->d2h);
     delete c;
 }
 
@@ -541,12 +508,9 @@ struct Run {
 
 // boundary rows of the strip-mined class and of the exact tier: one array per context, grown on demand
 int ensure_strip_scratch(mgx_pairhmm* c, size_t bytes) {
-    if (bytes <= c->strip_cap) return 0;
+    if (bytes <= c->strip.cap) return 0;
     HIP_TRY(hipStreamSynchronize(c->compute));           // an earlier launch may still be using the old array
-    (void)hipFree(c->d_strip); c->d_strip = nullptr; c->strip_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_strip, bytes));
-    c->strip_cap = bytes;
-    return 0;
+    return c->strip.reserve(bytes);
 }
 
 // this run's event set out of the batch's ring
@@ -651,7 +615,7 @@ int launch_class(Run& r, size_t k) {
     if (bin.strip) {
         a.strip_stride = (bin.max_h + 63u) & ~63u;
         if (const int rc = ensure_strip_scratch(c, (size_t)bin.grid_f32 * 6u * a.strip_stride * sizeof(double))) return rc;
-        a.strip_scratch = c->d_strip;
+        a.strip_scratch = c->strip.p;
     }
     a.rerun_list = shared ? b->rerun_list() : b->rerun_list() + bin.job_begin;
     a.rerun_count = b->counters() + (shared ? kSharedCount : (int)k);
@@ -727,7 +691,7 @@ int launch_exact(Run& r) {
     const size_t per_wg = 6u * (size_t)a.strip_stride * sizeof(double);
     const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)b->n_pairs, (size_t)c->n_cu * 2u, (size_t)(256u << 20) / per_wg}));
     if (const int rc = ensure_strip_scratch(c, (size_t)grid * per_wg)) return rc;
-    a.strip_scratch = c->d_strip;
+    a.strip_scratch = c->strip.p;
     hipLaunchKernelGGL(pairhmm_fwd_exact, dim3(grid), dim3(64), a.lds_stride, r.s, a);
     return 0;
 }

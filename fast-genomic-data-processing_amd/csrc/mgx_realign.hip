@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -157,10 +158,10 @@ struct Realign {
 };
 int realign_of(const PairhmmView& v, Realign** out) {
     if (!v.ext->p) {
-        Realign* r = new (std::nothrow) Realign;
+        std::unique_ptr<Realign> r(new (std::nothrow) Realign);      // whole before the context sees it
         if (!r) return -ENOMEM;
-        v.ext->p = r; v.ext->free_fn = [](void* p) { delete static_cast<Realign*>(p); };
         for (auto& e : r->ev) HIP_TRY(hipEventCreate(&e));
+        v.ext->p = r.release(); v.ext->free_fn = [](void* p) { delete static_cast<Realign*>(p); };
     }
     *out = static_cast<Realign*>(v.ext->p);
     return 0;

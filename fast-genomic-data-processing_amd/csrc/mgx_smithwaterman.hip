@@ -499,47 +499,25 @@ struct Knobs {
 };
 constexpr int kCompactElems = 16;             // merged CIGAR elements copied back per pair without a second look
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr; size_t cap = 0;
-    int reserve(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = n + n / 4 + 64;
-        if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %zu bytes failed", want * sizeof(T)); return -ENOMEM; }
-        cap = want;
-        return 0;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-// pinned host memory; `want` >= n is what a growing buffer asks for (each user keeps its growth factor)
-struct PinBuf {
-    char* p = nullptr; size_t cap = 0;
-    int reserve(size_t n, size_t want) {
-        if (n <= cap) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
-        cap = want;
-        return 0;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
+using mgx_hip::PinBuf;
+using mgx_hip::DevArray;
+// the context's device arrays grow by a quarter and 64 elements over what is asked
+template <typename T> int grow(DevArray<T>& a, size_t n) { return a.reserve(n, n + n / 4 + 64); }
 
 }  // namespace
 
 struct mgx_sw {
+    mgx_hip::Owner own;           // of the stream and the events; the first member: the stream goes last
     int device = 0;
     unsigned flags = 0;           // MGX_SW_*
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    DevBuf<u8> d_s1, d_s2, d_bt;
-    DevBuf<SwJob> d_jobs;
-    DevBuf<int32_t> d_sc;
-    DevBuf<int16_t> d_el, d_cel, d_dense;
-    DevBuf<GatherRef> d_gather;
-    DevBuf<SwResult> d_res;
+    DevArray<u8> d_s1, d_s2, d_bt;
+    DevArray<SwJob> d_jobs;
+    DevArray<int32_t> d_sc;
+    DevArray<int16_t> d_el, d_cel, d_dense;
+    DevArray<GatherRef> d_gather;
+    DevArray<SwResult> d_res;
     mgx_sw_stats_t stats{};
     PinBuf pin;                   // pinned staging for the uploads (a pageable source is copied at a few GB/s)
     PinBuf pin_out;               // pinned landing area of the results (a pageable target goes through the runtime's own staging)
@@ -571,7 +549,7 @@ struct Stager {                   // the helper threads of stage_sequences: uplo
 int stage_sequences(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, Stager& st) {
     const size_t total = k.a1 + k.a2 + max_jobs(k.n) * sizeof(SwJob);
     int rc;
-    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = c->d_s1.reserve(k.n1 + 16)) || (rc = c->d_s2.reserve(k.n2 + 16))) return rc;
+    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = grow(c->d_s1, k.n1 + 16)) || (rc = grow(c->d_s2, k.n2 + 16))) return rc;
     char* const pin = c->pin.p;
     st.apart = k.n1 + k.n2 >= (1u << 20);
     if (!st.apart) { memcpy(pin, in->ref + k.base1, k.n1); memcpy(pin + k.a1, in->alt + k.base2, k.n2); return 0; }
@@ -589,7 +567,7 @@ int stage_sequences(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, Stager&
 int gather_sequences(mgx_sw* c, const SwDeviceSource& src, const Chunk& k, Stager& st) {
     const size_t total = k.a1 + k.a2 + max_jobs(k.n) * sizeof(SwJob);
     int rc;
-    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = c->d_s1.reserve(k.n1 + 16)) || (rc = c->d_s2.reserve(k.n2 + 16))) return rc;
+    if ((rc = c->pin.reserve(total, total + total / 4)) || (rc = grow(c->d_s1, k.n1 + 16)) || (rc = grow(c->d_s2, k.n2 + 16))) return rc;
     st.on_device = true;
     if (src.ready) HIP_TRY(hipStreamWaitEvent(c->stream, src.ready, 0));
     return src.gather(src.user, c->stream, k.lo, k.hi, c->d_s1.p, c->d_s2.p);
@@ -607,8 +585,8 @@ int upload_jobs(mgx_sw* c, const Chunk& k, Stager& st, const Layout& L, const Sw
     hipStream_t s = c->stream;
     const u64 scn = k.n1 + k.n2 + 2ull * k.n, eln = 2 * scn;
     int rc;
-    if ((rc = c->d_bt.reserve(L.bt_bytes + 16)) || (rc = c->d_jobs.reserve(L.n_jobs)) || (rc = c->d_sc.reserve(scn)) || (rc = c->d_el.reserve(eln)) ||
-        (rc = c->d_res.reserve(k.n)) || (rc = c->d_cel.reserve((size_t)k.n * 2 * kCompactElems))) return rc;
+    if ((rc = grow(c->d_bt, L.bt_bytes + 16)) || (rc = grow(c->d_jobs, L.n_jobs)) || (rc = grow(c->d_sc, scn)) || (rc = grow(c->d_el, eln)) ||
+        (rc = grow(c->d_res, k.n)) || (rc = grow(c->d_cel, (size_t)k.n * 2 * kCompactElems))) return rc;
     st.join();                                    // the helpers have queued the sequences: the jobs follow them on the stream
     if (st.err.load()) { (void)hipGetLastError(); set_error("upload of the sequences failed"); return -EIO; }
     if (!st.apart && !st.on_device) {
@@ -693,7 +671,7 @@ int fetch_results(mgx_sw* c, const mgx_sw_input_t* in, const Chunk& k, u64 bt_by
     f.big.reset(new (std::nothrow) int16_t[dense_n + 1]);
     if (!f.big) return -ENOMEM;
     if (!big_refs.empty()) {
-        if ((rc = c->d_gather.reserve(big_refs.size())) || (rc = c->d_dense.reserve(dense_n))) return rc;
+        if ((rc = grow(c->d_gather, big_refs.size())) || (rc = grow(c->d_dense, dense_n))) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_gather.p, big_refs.data(), big_refs.size() * sizeof(GatherRef), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_sw_gather, dim3((u32)std::min<size_t>(big_refs.size(), 65535)), dim3(256), 0, s, c->d_gather.p,
                            (u32)big_refs.size(), c->d_el.p, c->d_dense.p);
@@ -776,20 +754,14 @@ extern "C" {
 int mgx_sw_create(int device, unsigned flags, mgx_sw_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        set_error("no HIP device is visible (this library has no CPU fallback)");
-        return -ENODEV;
-    }
-    if (device == -1) device = 0;
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range", device); return -EINVAL; }
-    HIP_TRY(hipSetDevice(device));
+    if (const int rc = mgx_hip::pick_device(&device, nullptr)) return rc;
     std::unique_ptr<mgx_sw> c(new (std::nothrow) mgx_sw);
     if (!c) return -ENOMEM;
     c->device = device;
     c->flags = flags;
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
+    c->own.stream(&c->stream);
+    for (auto& e : c->ev) c->own.event(&e);
+    if (!c->own.ok()) return c->own.error("a Smith-Waterman context");
     *out = c.release();
     return 0;
 }
@@ -797,8 +769,7 @@ int mgx_sw_create(int device, unsigned flags, mgx_sw_t** out) {
 void mgx_sw_destroy(mgx_sw_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
+    (void)hipStreamSynchronize(c->stream);
     delete c;
 }
 

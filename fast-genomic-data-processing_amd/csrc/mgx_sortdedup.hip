@@ -1027,19 +1027,9 @@ inline int bits_of(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b
 }  // namespace
 
 struct mgx_sortdedup {
-    // a device array that only grows; growing discards the contents.  A plain pair, no destructor: ensure_recs assigns one over another
-    template <typename T>
-    struct Grow {
-        T* p = nullptr; size_t cap = 0;
-        void release() { (void)hipFree(p); p = nullptr; cap = 0; }
-        int grow(size_t count) {
-            if (count <= cap) return 0;
-            release();
-            HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-            cap = count;
-            return 0;
-        }
-    };
+    template <typename T> using DevArray = mgx_hip::DevArray<T>;      // each grown to the exact count
+    mgx_hip::Owner own;                    // of the streams, the events and d_sc; the first member: the streams go last
+    mgx_hip::Owner work;                   // of the work buffers below, released and refilled as a whole (ensure_capacity)
     int device = 0;
     unsigned flags = 0;
     hipStream_t compute = nullptr, copy = nullptr;
@@ -1048,11 +1038,11 @@ struct mgx_sortdedup {
     u32 n = 0;                             // records the duplicate search works on (the marking half of a shard)
     u32 n_order = 0;                       // records the coordinate sort orders (== n unless the input is a shard)
     bool sharded = false;
-    Grow<u64> ocoord; Grow<u32> oarr;      // a shard's ordering half as uploaded
-    Grow<u64> marks; u32 n_marks = 0;      // indicator marks routed from other shards
+    DevArray<u64> ocoord; DevArray<u32> oarr;          // a shard's ordering half as uploaded
+    DevArray<u64> marks; u32 n_marks = 0;  // indicator marks routed from other shards
     size_t cap = 0;                        // record capacity of the work buffers below
-    Grow<mgx_rec_t> recs;                  // the uploaded records (a streamed upload grows it by hand: ensure_recs keeps the contents)
-    void* d_wire[2] = {nullptr, nullptr};  // device side of the staging buffers: compact 24-byte records before expansion
+    DevArray<mgx_rec_t> recs;              // the uploaded records (a streamed upload grows it by hand: ensure_recs keeps the contents)
+    mgx_hip::Mirror stage[2];              // staging buffers of the exact chunk size; device side: compact 24-byte records before expansion
     uint64_t up_L = 0, up_high = 0;        // streamed upload in progress: reference length, highest record index seen + 1
     bool uploading = false;
     u64 *d_ckey[2] = {nullptr, nullptr}; u32* d_cval[2] = {nullptr, nullptr};
@@ -1064,13 +1054,11 @@ struct mgx_sortdedup {
     struct Scratch { u32 *hist = nullptr, *chunk = nullptr, *longl = nullptr, *multi = nullptr; } scr[3];
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_ind = nullptr, ev_side[2] = {nullptr, nullptr};
-    Grow<u32> indicator; uint64_t indicator_bits = 0;    // the bitmap, in 32-bit words
-    Grow<u32> sub_start;                                 // first near entry per kNearSpan positions (bitmap pass)
+    DevArray<u32> indicator; uint64_t indicator_bits = 0;      // the bitmap, in 32-bit words
+    DevArray<u32> sub_start;                                   // first near entry per kNearSpan positions (bitmap pass)
     uint8_t* d_dup = nullptr;
     u32* d_half_hist = nullptr;            // [ceil(n / kBuildBlock)][256], written by the build kernel
     Scalars* d_sc = nullptr;
-    void* pinned[2] = {nullptr, nullptr};
-    size_t pinned_cap = 0;
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     std::vector<hipEvent_t> ev_scatter;    // pairs (start, stop) per scatter launch
@@ -1091,46 +1079,29 @@ namespace {
 
 constexpr size_t kPinnedChunk = 64u << 20;
 
-template <typename T>
-void dfree(T*& p) { (void)hipFree(p); p = nullptr; }
-
-void free_buffers(mgx_sortdedup* c) {
-    for (int i = 0; i < 2; ++i) {
-        dfree(c->d_ckey[i]); dfree(c->d_cval[i]); dfree(c->d_k1[i]); dfree(c->d_k2[i]); dfree(c->d_prec[i]);
-        dfree(c->d_sk1[i]); dfree(c->d_srec[i]); dfree(c->d_nk[i]); dfree(c->d_nrec[i]);
-    }
-    for (auto& q : c->scr) { dfree(q.hist); dfree(q.chunk); dfree(q.longl); dfree(q.multi); }
-    dfree(c->d_dup); dfree(c->d_half_hist);
-    c->cap = 0;
-}
-
-template <typename T>
-int dalloc(T** p, size_t count) {
-    HIP_TRY(hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-    return 0;
-}
-
 int ensure_capacity(mgx_sortdedup* c, size_t n) {
     if (n <= c->cap) return 0;
-    free_buffers(c);
-    int rc = 0;
+    mgx_hip::Owner& w = c->work;
+    w.reset();
+    c->cap = 0;
     const size_t half = n / 2 + 1;
     const size_t n_tiles = (n + kTile - 1) / kTile + 1;
-    for (int i = 0; i < 2 && !rc; ++i) {
-        rc |= dalloc(&c->d_ckey[i], n); rc |= dalloc(&c->d_cval[i], n);
-        rc |= dalloc(&c->d_k1[i], half); rc |= dalloc(&c->d_k2[i], half); rc |= dalloc(&c->d_prec[i], half);
-        rc |= dalloc(&c->d_sk1[i], n); rc |= dalloc(&c->d_srec[i], n);
-        rc |= dalloc(&c->d_nk[i], half); rc |= dalloc(&c->d_nrec[i], half);
+    auto dev = [&w](auto** p, size_t count) { w.device(p, std::max<size_t>(count, 1) * sizeof(**p)); };
+    for (int i = 0; i < 2; ++i) {
+        dev(&c->d_ckey[i], n); dev(&c->d_cval[i], n);
+        dev(&c->d_k1[i], half); dev(&c->d_k2[i], half); dev(&c->d_prec[i], half);
+        dev(&c->d_sk1[i], n); dev(&c->d_srec[i], n);
+        dev(&c->d_nk[i], half); dev(&c->d_nrec[i], half);
     }
     for (auto& q : c->scr) {
-        rc |= dalloc(&q.hist, n_tiles * 256);                          // tile histograms, then offsets
-        rc |= dalloc(&q.chunk, ((n_tiles + kChunkTiles - 1) / kChunkTiles + 1) * 256);
-        rc |= dalloc(&q.longl, n / kWalkCap + 16);
-        rc |= dalloc(&q.multi, n / 2 + 16);          // heads of runs with >= 2 entries
+        dev(&q.hist, n_tiles * 256);                          // tile histograms, then offsets
+        dev(&q.chunk, ((n_tiles + kChunkTiles - 1) / kChunkTiles + 1) * 256);
+        dev(&q.longl, n / kWalkCap + 16);
+        dev(&q.multi, n / 2 + 16);          // heads of runs with >= 2 entries
     }
-    rc |= dalloc(&c->d_dup, n);
-    rc |= dalloc(&c->d_half_hist, (n / kBuildBlock + 2) * 256);
-    if (rc) { free_buffers(c); return -ENOMEM; }
+    dev(&c->d_dup, n);
+    dev(&c->d_half_hist, (n / kBuildBlock + 2) * 256);
+    if (!w.ok()) { w.release(); return -ENOMEM; }
     c->cap = n;
     return 0;
 }
@@ -1252,17 +1223,8 @@ extern "C" {
 int mgx_sortdedup_create(int device, unsigned flags, mgx_sortdedup_t** out) {
     if (!out) { set_error("out is NULL"); return -EINVAL; }
     *out = nullptr;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        set_error("no HIP device is visible (this library has no CPU fallback)");
-        return -ENODEV;
-    }
-    if (device == -1) {                 // MGX_DEVICE_AUTO: contexts are dealt round-robin over the visible GPUs
-        static std::atomic<unsigned> next{0};
-        device = (int)(next.fetch_add(1) % (unsigned)n_dev);
-    }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range", device); return -EINVAL; }
-    HIP_TRY(hipSetDevice(device));
+    static std::atomic<unsigned> next{0};      // MGX_DEVICE_AUTO: contexts are dealt round-robin over the visible GPUs
+    if (const int rc = mgx_hip::pick_device(&device, &next)) return rc;
     std::unique_ptr<mgx_sortdedup> c(new (std::nothrow) mgx_sortdedup);
     if (!c) return -ENOMEM;
     c->device = device; c->flags = flags;
@@ -1270,37 +1232,18 @@ int mgx_sortdedup_create(int device, unsigned flags, mgx_sortdedup_t** out) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     c->n_cu = prop.multiProcessorCount;
     // MGX_STREAM_HIGH_PRIORITY (bit 16): the pipeline's short HBM-bound kernels go ahead of a co-resident PairHMM context's
-    int prio_least = 0, prio_greatest = 0;
     const bool high = (flags & (1u << 16)) != 0;
-    if (high) HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    auto make_stream = [&](hipStream_t* st) {
-        return high ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_greatest) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    };
-    {
-        // optional CU partition (flags bits 8..15: an 8-bit pattern repeated over the CU index): lets a
-        // VALU-bound PairHMM context and an HBM-bound sort context share one GPU side by side instead
-        // of queueing behind each other (BASELINE.json configs[4])
-        const unsigned pat = (flags >> 8) & 0xFFu;
-        if (pat != 0 && pat != 0xFFu) {
-            const int n_words = (c->n_cu + 31) / 32;
-            std::vector<uint32_t> mask(n_words, 0);
-            for (int cu = 0; cu < c->n_cu; ++cu) if ((pat >> (cu & 7)) & 1u) mask[cu >> 5] |= 1u << (cu & 31);
-            HIP_TRY(hipExtStreamCreateWithCUMask(&c->compute, (uint32_t)n_words, mask.data()));
-        } else {
-            HIP_TRY(make_stream(&c->compute));
-        }
-    }
-    HIP_TRY(make_stream(&c->copy));
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(make_stream(&c->side[i]));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_side[i], hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_ind, hipEventDisableTiming));
-    HIP_TRY(hipMalloc((void**)&c->d_sc, sizeof(Scalars)));
-    HIP_TRY(hipEventCreate(&c->ev_start)); HIP_TRY(hipEventCreate(&c->ev_stop));
+    mgx_hip::Owner& m = c->own;
+    m.stream(&c->compute, c->n_cu, (flags >> 8) & 0xFFu, high);
+    m.stream(&c->copy, 0, 0, high);
+    for (int i = 0; i < 2; ++i) { m.stream(&c->side[i], 0, 0, high); m.event(&c->ev_side[i], hipEventDisableTiming); }
+    m.event(&c->ev_ind, hipEventDisableTiming);
+    m.device(&c->d_sc, sizeof(Scalars));
+    m.event(&c->ev_start); m.event(&c->ev_stop);
     c->ev_scatter.resize(64);
-    for (auto& e : c->ev_scatter) HIP_TRY(hipEventCreate(&e));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&c->pin_ev[i]));   // staging buffers: on first upload
+    for (auto& e : c->ev_scatter) m.event(&e);
+    for (int i = 0; i < 2; ++i) m.event(&c->pin_ev[i]);   // staging buffers: on first upload
+    if (!m.ok()) return m.error("a sort context");
     *out = c.release();
     return 0;
 }
@@ -1308,17 +1251,6 @@ int mgx_sortdedup_create(int device, unsigned flags, mgx_sortdedup_t** out) {
 void mgx_sortdedup_destroy(mgx_sortdedup_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    free_buffers(c);
-    c->recs.release(); c->indicator.release(); c->sub_start.release(); c->ocoord.release(); c->oarr.release(); c->marks.release();
-    (void)hipFree(c->d_wire[0]); (void)hipFree(c->d_wire[1]); (void)hipFree(c->d_sc);
-    for (int i = 0; i < 2; ++i) { if (c->pinned[i]) (void)hipHostFree(c->pinned[i]); if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]); }
-    for (auto e : c->ev_scatter) (void)hipEventDestroy(e);
-    if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-    if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
-    for (int i = 0; i < 2; ++i) { if (c->side[i]) (void)hipStreamDestroy(c->side[i]); if (c->ev_side[i]) (void)hipEventDestroy(c->ev_side[i]); }
-    if (c->ev_ind) (void)hipEventDestroy(c->ev_ind);
-    if (c->compute) (void)hipStreamDestroy(c->compute);
-    if (c->copy) (void)hipStreamDestroy(c->copy);
     delete c;
 }
 
@@ -1330,13 +1262,13 @@ namespace {
 int ensure_recs(mgx_sortdedup_t* c, size_t n, size_t keep) {
     if (n <= c->recs.cap) return 0;
     const size_t cap = std::max<size_t>(n, keep ? c->recs.cap + c->recs.cap / 2 : 0);
-    mgx_sortdedup::Grow<mgx_rec_t> fresh;
-    if (fresh.grow(cap)) { set_error("out of device memory for %zu records", cap); return -ENOMEM; }
+    mgx_hip::DevArray<mgx_rec_t> fresh;
+    if (fresh.reserve(cap)) { set_error("out of device memory for %zu records", cap); return -ENOMEM; }
     if (keep && c->recs.p) {
         HIP_TRY(hipMemcpyAsync(fresh.p, c->recs.p, keep * sizeof(mgx_rec_t), hipMemcpyDeviceToDevice, c->copy));
         HIP_TRY(hipStreamSynchronize(c->copy));
     }
-    c->recs.release(); c->recs = fresh;
+    c->recs.swap(fresh);      // the old array goes with `fresh`
     return 0;
 }
 
@@ -1347,8 +1279,8 @@ int prepare_input(mgx_sortdedup_t* c, uint64_t L, size_t capacity) {
     // double_pair_indicator: 4L bits like the reference (main.cpp:115), or the two tile-aligned halves
     const uint64_t Lp = tile_aligned(L);
     const uint64_t bits = std::max<uint64_t>(4 * L + 64, 2 * Lp + 2 * (uint64_t)kIndTile);
-    if ((rc = c->indicator.grow((size_t)((bits + 31) / 32)))) return rc;
-    if ((rc = c->sub_start.grow((size_t)(Lp / kNearSpan) + 2))) return rc;
+    if ((rc = c->indicator.reserve((size_t)((bits + 31) / 32)))) return rc;
+    if ((rc = c->sub_start.reserve((size_t)(Lp / kNearSpan) + 2))) return rc;
     c->indicator_bits = 4 * L; c->L = L; c->ran = false;
     c->near_by_position = true;             // decided again for every input (see finish_run)
     c->packed_coord = L < 0xFFFFFFFFull;     // coord <= L (bam_record.cpp:18-24)
@@ -1357,15 +1289,10 @@ int prepare_input(mgx_sortdedup_t* c, uint64_t L, size_t capacity) {
 }
 
 int ensure_staging(mgx_sortdedup_t* c, size_t chunk) {
-    if (chunk <= c->pinned_cap) return 0;
+    if (chunk <= c->stage[1].cap) return 0;      // [1] is filled last: both are there or neither
     HIP_TRY(hipStreamSynchronize(c->copy));
-    for (int i = 0; i < 2; ++i) { if (c->pinned[i]) (void)hipHostFree(c->pinned[i]); c->pinned[i] = nullptr; dfree(c->d_wire[i]); }
-    c->pinned_cap = 0;
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipHostMalloc(&c->pinned[i], chunk, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&c->d_wire[i], chunk));
-    }
-    c->pinned_cap = chunk;
+    for (auto& st : c->stage) st.release();
+    for (auto& st : c->stage) if (const int rc = st.reserve(chunk, chunk)) { c->stage[0].release(); return rc; }
     return 0;
 }
 
@@ -1385,17 +1312,17 @@ int staged_upload(mgx_sortdedup_t* c, void* dst_, const void* src_, size_t n_ite
     const size_t total = n_items * item_bytes;
     int rc = ensure_staging(c, std::min(kPinnedChunk, std::max<size_t>((total + 1) / 2, 1u << 20)));
     if (rc) return rc;
-    const size_t piece = c->pinned_cap / item_bytes;
+    const size_t piece = c->stage[0].cap / item_bytes;
     mgx_stage::Gang gang(total >= (32u << 20) ? n_thr : 1);
     int buf = 0;
     for (size_t off = 0; off < n_items; off += piece, buf ^= 1) {
         const size_t m = std::min(piece, n_items - off), len = m * item_bytes;
         const char* src = static_cast<const char*>(src_) + off * item_bytes;
-        char *dst = static_cast<char*>(dst_) + off * item_bytes, *stage = static_cast<char*>(c->pinned[buf]);
+        char *dst = static_cast<char*>(dst_) + off * item_bytes, *stage = reinterpret_cast<char*>(c->stage[buf].pin);
         HIP_TRY(hipEventSynchronize(c->pin_ev[buf]));
         if (wire && !mgx_stage::pack24(gang, reinterpret_cast<const mgx_rec_t*>(src), m, stage)) {
-            HIP_TRY(hipMemcpyAsync(c->d_wire[buf], stage, m * sizeof(Wire24), hipMemcpyHostToDevice, c->copy));
-            hipLaunchKernelGGL(k_expand24, dim3((u32)((m + 255) / 256)), dim3(256), 0, c->copy, (const Wire24*)c->d_wire[buf], (mgx_rec_t*)dst, (u32)m);
+            HIP_TRY(hipMemcpyAsync(c->stage[buf].dev, stage, m * sizeof(Wire24), hipMemcpyHostToDevice, c->copy));
+            hipLaunchKernelGGL(k_expand24, dim3((u32)((m + 255) / 256)), dim3(256), 0, c->copy, (const Wire24*)c->stage[buf].dev, (mgx_rec_t*)dst, (u32)m);
         } else {
             gang.run(len, 4u << 20, [=](size_t a, size_t b) { memcpy(stage + a, src + a, b - a); });
             HIP_TRY(hipMemcpyAsync(dst, stage, len, hipMemcpyHostToDevice, c->copy));
@@ -1636,9 +1563,9 @@ int mgx_sortdedup_upload_shard(mgx_sortdedup_t* c, uint64_t L, const mgx_sortded
     c->uploading = false;
     int rc = ensure_recs(c, (size_t)sh->n_mark, 0);
     if (!rc) rc = prepare_input(c, L, (size_t)std::max(sh->n_order, sh->n_mark));
-    if (!rc) rc = c->ocoord.grow((size_t)sh->n_order);
-    if (!rc) rc = c->oarr.grow((size_t)sh->n_order);
-    if (!rc) rc = c->marks.grow((size_t)sh->n_marks);
+    if (!rc) rc = c->ocoord.reserve((size_t)sh->n_order);
+    if (!rc) rc = c->oarr.reserve((size_t)sh->n_order);
+    if (!rc) rc = c->marks.reserve((size_t)sh->n_marks);
     if (rc) return rc;
     c->n = (u32)sh->n_mark; c->n_order = (u32)sh->n_order; c->n_marks = (u32)sh->n_marks; c->sharded = true;
     if ((rc = staged_upload(c, c->recs.p, sh->mark_recs, (size_t)sh->n_mark, sizeof(mgx_rec_t), true))) return rc;

@@ -120,7 +120,9 @@ typedef struct mgx_pairhmm_stats {
 
 const char* mgx_last_error(void);
 
-#define MGX_DEVICE_AUTO (-1)   /* device argument of the create functions: next GPU, round-robin per process */
+/* device argument of a create function.  mgx_pairhmm_create and mgx_sortdedup_create: the next GPU, round-robin per process and
+ * per kind of context.  mgx_sw_create and mgx_activity_create: device 0.  (The BGZF calls take any negative ordinal as device 0.) */
+#define MGX_DEVICE_AUTO (-1)
 
 /* device: HIP device ordinal or MGX_DEVICE_AUTO (one context per worker thread then spreads the
  * threads over the GPUs of the node -- the host work queue of the reference's threadFunc,
