@@ -42,6 +42,15 @@
 //  insertion qualities differ by tens of dB can overflow fp32: every term is non-negative, an overflow reaches
 //  the last row's sums as inf or NaN, and such a result is deferred after the sweep (five_overflowed).  Both per test
 //  case, to the second launch of its class, which computes it in the forms above.
+//  What crosses from a row to the row below, in the five-operation form.  The row below reads its row above in two expressions only:
+//  the three paths into m, fma(q', yb2, fma(a, x2, m2)), whose m2 x2 yb2 are all of ONE column of the row above, and x = fma(x1, B', m1),
+//  whose m1 x1 are of one column too.  So the row above can evaluate both itself, with the lower row's a, q' and B', and hand down two
+//  values (five_paths_down, five_x_down) instead of three: the same operations on the same operand bits wherever they are computed.
+//  Above read row 0 the paths value is the constant five_boundary_paths = round(q' * INITIAL/H) (0 under a row-0 clone, whose q' is 0),
+//  and x is 0.
+//  Sum of m along read row R.  Nothing reads row R's yb.  With pYY := 1 in that one row (Edge::pYY_sum_row) the row's own
+//  yb = fma(ybl, 1, ml) = round(ybl + ml) makes, column by column from yb = 0, the very additions of sum += m: after the last column
+//  yb holds the sum of every m but the last, and sum m = five_sum_m(yb, m) = round(yb + m).
 // A row-0 clone (a spare row above read row 0) has every coefficient 0 and pYY = 1: it hands the boundary row on unchanged.
 #pragma once
 
@@ -102,6 +111,7 @@ template <typename T> struct Edge {
     static MGX_CELL_FN constexpr T s_below() { return 1; }
     static MGX_CELL_FN constexpr T pMY_above() { return 1; }
     static MGX_CELL_FN constexpr T A_above() { return 0; }
+    static MGX_CELL_FN constexpr T pYY_sum_row() { return 1; }      // five: read row R sums its m in its yb
 };
 
 // ---- per-row coefficients; gb = g of the row below, every product and quotient rounded on its own
@@ -132,6 +142,11 @@ template <class A, typename T> MGX_CELL_FN T six_M_paths(T M2, T X2, T y2, T pMM
 template <class A, typename T> MGX_CELL_FN T six_y(T Ml, T yl, T pYY) { return A::fma(yl, pYY, Ml); }                          // the five-operation form's yb too
 template <class A, typename T> MGX_CELL_FN T five_m_paths(T m2, T x2, T yb2, T a, T q) { return A::fma(q, yb2, A::fma(a, x2, m2)); }
 template <class A, typename T> MGX_CELL_FN T five_x(T m1, T x1, T Bp) { return A::fma(x1, Bp, m1); }
+// the two values a row hands to the row below (a, q, Bp: the LOWER row's), and what read row 0 gets from the boundary row
+template <class A, typename T> MGX_CELL_FN T five_paths_down(T m, T x, T yb, T a_below, T q_below) { return five_m_paths<A>(m, x, yb, a_below, q_below); }
+template <class A, typename T> MGX_CELL_FN T five_x_down(T m, T x, T Bp_below) { return five_x<A>(m, x, Bp_below); }
+template <class A, typename T> MGX_CELL_FN T five_boundary_paths(T init_y, T a, T q) { return five_m_paths<A>((T)0, (T)0, init_y, a, q); }
+template <class A, typename T> MGX_CELL_FN T five_sum_m(T yb_last, T m_last) { return A::add(yb_last, m_last); }      // read row R, pYY = pYY_sum_row
 
 // ---- the rules around the cell
 MGX_CELL_FN bool row_needs_plain(int qc) { return qc == 0; }                                    // a test case with such a row takes the plain form

@@ -19,7 +19,8 @@
 //     d - j for all of its RPL rows, top to bottom.  Inside a lane every dependency is a
 //     register of the previous column (or of the row just computed); between lanes only the
 //     bottom row's (M, X, Y) moves, one lane to the right, with a DPP shift
-//     (row_shr:1 for G = 16, wave_shr:1 for G = 64): 3 cross-lane moves per RPL cells.
+//     (row_shr:1 for G = 16, wave_shr:1 for G = 64): 3 cross-lane moves per RPL cells (2 in the five-operation sweep,
+//     where the bottom row evaluates what the next lane's top row needs of it: column5 below).
 //   * Fill/drain costs nl-1 steps per pair (nl = lanes in use <= G) instead of 63: with G = 16
 //     a 128x256 pair keeps 94 % of its lane-steps busy (80 % with two 64-row stripes).
 //   * Rows are packed against the LAST used lane so that read row R is always that lane's
@@ -28,7 +29,8 @@
 //   * The haplotype is staged once per pair into LDS as base codes; each lane reads its own
 //     column's code with one ds_read_u8 per step, prefetched one step ahead.
 //   * The last-row sums are accumulated on the bottom row of every lane, in column order,
-//     sumM and sumX apart, and read from lane nl-1 at the end (as the reference does).
+//     sumM and sumX apart, and read from lane nl-1 at the end (as the reference does).  (Five-operation sweep: read
+//     row R makes the additions of sumM in its own, otherwise unread, y.)
 //   * fp32 results < 1e-28f are appended to a re-run list; the same template instantiated for
 //     double processes that list (IntelPairHmm.cc:338-350).
 //   * The cell is not computed in the reference's 8-operation order but in an algebraically equal
@@ -252,6 +254,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
         bool zero_mm = false;                             // (FIVE) some row has pMM == 0
         bool defer = group_hap_n;                         // the test case is left to the class's second launch
         T res_scale = 1;                                  // (FIVE) A' of this lane's bottom row: the last lane's turns sum x into sum X
+        T dn_a = 0, dn_B = 0, dn_q = 0;                   // (FIVE) a, B', q' of the next lane's top row: what this lane's bottom row hands down with
+        T paths0 = 0;                                     // (FIVE) group lane 0: the paths value its top row gets from the boundary row
         if constexpr (STRIP) {                            // every strip of a pair must take the same algebraic form
             for (int rr = lane; rr < R; rr += 64) zero_gap |= cell::row_needs_plain(a.gcp[job.read_off + (uint64_t)rr] & 127);
         }
@@ -346,6 +350,14 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 if (clone[s]) { k1[s] = 0; k2[s] = 0; k3[s] = 0; k4[s] = 1; }
             }
             res_scale = Ap[RPL - 1];
+            // The hand-off (pairhmm_cell.h): a lane's bottom row evaluates the next lane's top-row paths value and x itself, so it
+            // keeps that row's a, B' and q' and the top row's own three are used once more, for the boundary value of group lane 0.
+            // The last used lane hands on with zeros, to a lane that is not in use (or to none).  Its bottom row is read row R,
+            // which sums its m in its yb.
+            const T a_dn = shr1_down<G>(k1[0]), B_dn = shr1_down<G>(k2[0]), q_dn = shr1_down<G>(k3[0]);
+            dn_a = last_lane ? (T)0 : a_dn; dn_B = last_lane ? (T)0 : B_dn; dn_q = last_lane ? (T)0 : q_dn;
+            paths0 = cell::five_boundary_paths<Ar>(init_y, k1[0], k3[0]);
+            if (last_lane) k4[RPL - 1] = Edge::pYY_sum_row();
         }
         if constexpr (kETab) {
             // one store per read of the column loop (pairhmm_etab.h) and code
@@ -484,8 +496,8 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 }
             }
 
-            // one column: o2* = values shifted in two steps ago (M,X,Y), o1* = last step (M,X); the
-            // new shifted-in set overwrites o2's registers.  The DPP `old` operand is the register's
+            // one column (every form but the five-operation one: column5 below): o2* = values shifted in two
+            // steps ago (M,X,Y), o1* = last step (M,X); the new shifted-in set overwrites o2's registers.  The DPP `old` operand is the register's
             // own previous content, so the group's lane 0 keeps (0, 0, y_above) for ever.
             auto column = [&](const T (&ec)[RPL], T& o2M, T& o2X, T& o2Y, const T o1M, const T o1X, bool count, const int dcol) {
                 // Every multiply-add below is an explicit fma (the file is built with
@@ -506,20 +518,6 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                     px[0] = cell::scaled_X<Ar>(o1M, o1X, k1[0], k2[0]);
 #pragma unroll
                     for (int s = 1; s < RPL; ++s) px[s] = cell::scaled_X<Ar>(pm[s - 1], px[s - 1], k1[s], k2[s]);
-#pragma unroll
-                    for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
-                } else if constexpr (FIV) {
-                    // in place like the 6-operation cell: m and yb bottom row first, then x top down from the new m
-#pragma unroll
-                    for (int s = RPL - 1; s >= 0; --s) {
-                        const T t = s ? cell::five_m_paths<Ar>(pm[s - 1], px[s - 1], py[s - 1], k1[s], k3[s])
-                                      : cell::five_m_paths<Ar>(o2M, o2X, o2Y, k1[0], k3[0]);
-                        py[s] = cell::six_y<Ar>(pm[s], py[s], k4[s]);
-                        pm[s] = cell::emit<Ar>(t, ec[s]);
-                    }
-                    px[0] = cell::five_x<Ar>(o1M, o1X, k2[0]);
-#pragma unroll
-                    for (int s = 1; s < RPL; ++s) px[s] = cell::five_x<Ar>(pm[s - 1], px[s - 1], k2[s]);
 #pragma unroll
                     for (int s = 0; s < RPL; ++s) { Mn[s] = pm[s]; Xn[s] = px[s]; Yn[s] = py[s]; }
                 } else if constexpr (SC) {
@@ -575,6 +573,29 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 }
             };
 
+            // The five-operation column.  Two values cross to the next lane (pairhmm_cell.h): the paths value of its top row, which it
+            // needs two steps later (`tin`: two registers alternate, as ua* / ub* do; group lane 0 keeps the boundary value for
+            // ever), and its top row's x, which it needs at the next step (`x_dn`, shifted into px[0] there: after the m phase,
+            // which still reads the old px[0] for row 1, and before the x chain; group lane 0's px[0] stays 0).  Read row R -- the
+            // last used lane's bottom row -- sums its m in its yb (sum_m_of_row below), so only sum x is added here.
+            T ta = (j == 0) ? paths0 : (T)0, tb = ta, x_dn = 0;
+            auto column5 = [&](const T (&ec)[RPL], T& tin, bool count) {
+#pragma unroll
+                for (int s = RPL - 1; s >= 0; --s) {
+                    const T t = s ? cell::five_m_paths<Ar>(pm[s - 1], px[s - 1], py[s - 1], k1[s], k3[s]) : tin;
+                    py[s] = cell::six_y<Ar>(pm[s], py[s], k4[s]);
+                    pm[s] = cell::emit<Ar>(t, ec[s]);
+                }
+                px[0] = shr1<G>(px[0], x_dn);
+#pragma unroll
+                for (int s = 1; s < RPL; ++s) px[s] = cell::five_x<Ar>(pm[s - 1], px[s - 1], k2[s]);
+                if (count) sumX += px[RPL - 1];
+                tin = shr1<G>(tin, cell::five_paths_down<Ar>(pm[RPL - 1], px[RPL - 1], py[RPL - 1], dn_a, dn_q));
+                x_dn = cell::five_x_down<Ar>(pm[RPL - 1], px[RPL - 1], dn_B);
+            };
+            // after a group's last step: read row R's yb holds every m but the last column's
+            auto sum_m_of_row = [&]() { sumM = cell::five_sum_m<Ar>(py[RPL - 1], pm[RPL - 1]); };
+
             T e[RPL];
             int d = 0;
             int h1 = hp_lane[1];
@@ -585,19 +606,27 @@ __device__ __forceinline__ void pairhmm_body(const KernelArgs& a, uint8_t* smem,
                 T e1[RPL];
                 load_e(h1, e1);
                 const int h2 = hp_lane[d + 2], h3 = hp_lane[d + 3];
-                column(e, uaM, uaX, uaY, ubM, ubX, true, d);
+                if constexpr (FIV) column5(e, ta, true); else column(e, uaM, uaX, uaY, ubM, ubX, true, d);
                 load_e(h2, e);
-                column(e1, ubM, ubX, ubY, uaM, uaX, true, d + 1);
+                if constexpr (FIV) column5(e1, tb, true); else column(e1, ubM, ubX, ubY, uaM, uaX, true, d + 1);
                 h1 = h3;
             }
+            // (a group's last step is the main loop's last one or a step of the tail, as its wavefront neighbours' H have it)
+            if constexpr (FIV) { if (d == nsteps_g) sum_m_of_row(); }
             // tail: at most a few guarded columns (groups of one wavefront differ slightly in H)
             for (; d < nmax; ++d) {
                 const int hn = hp_lane[d + 1];
-                column(e, uaM, uaX, uaY, ubM, ubX, d < nsteps_g, d);
                 T t;
-                t = uaM; uaM = ubM; ubM = t;
-                t = uaX; uaX = ubX; ubX = t;
-                t = uaY; uaY = ubY; ubY = t;
+                if constexpr (FIV) {
+                    column5(e, ta, d < nsteps_g);
+                    t = ta; ta = tb; tb = t;
+                } else {
+                    column(e, uaM, uaX, uaY, ubM, ubX, d < nsteps_g, d);
+                    t = uaM; uaM = ubM; ubM = t;
+                    t = uaX; uaX = ubX; ubX = t;
+                    t = uaY; uaY = ubY; ubY = t;
+                }
+                if constexpr (FIV) { if (d == nsteps_g - 1) sum_m_of_row(); }      // the columns after it run on pad codes
                 load_e(hn, e);
             }
         };

@@ -89,13 +89,18 @@ float sweep(const Rows& r) {
             } else if constexpr (F == kSixA) {
                 Mc[c] = cell::emit<Ftz>(cell::six_M_paths<Ftz>(M2, X2, Y2, cA, my_above), e); Xc[c] = cell::plain_X<Ftz>(M1, X1, pMX, pXX); Yc[c] = cell::six_y<Ftz>(Ml, Yl, pXX);
             } else {
-                Mc[c] = cell::emit<Ftz>(cell::five_m_paths<Ftz>(M2, X2, Y2, cA, cC), e); Xc[c] = cell::five_x<Ftz>(M1, X1, cB); Yc[c] = cell::six_y<Ftz>(Ml, Yl, pXX);
+                // as the kernel hands them down: the paths value and x from the row above (the boundary row above read row 0); read row R
+                // sums its m in its yb
+                const float paths = i ? cell::five_paths_down<Ftz>(M2, X2, Y2, cA, cC) : cell::five_boundary_paths<Ftz>(Y2, cA, cC);
+                Mc[c] = cell::emit<Ftz>(paths, e); Xc[c] = cell::five_x_down<Ftz>(M1, X1, cB);
+                Yc[c] = cell::six_y<Ftz>(Ml, Yl, last ? Edge::pYY_sum_row() : pXX);
             }
         }
         std::swap(Mu, Mc); std::swap(Xu, Xc); std::swap(Yu, Yc);
     }
     float sumM = 0.0f, sumX = 0.0f;
     for (int c = 1; c <= H; ++c) { sumM = Ftz::add(sumM, Mu[c]); sumX = Ftz::add(sumX, Xu[c]); }
+    if (F == kFive && R > 0) sumM = cell::five_sum_m<Ftz>(Yu[H], Mu[H]);      // the row's yb after the last column, and the last m
     return F == kFive ? cell::five_result<Ftz>(sumM, Ap, sumX) : cell::result<Ftz>(sumM, sumX);
 }
 
