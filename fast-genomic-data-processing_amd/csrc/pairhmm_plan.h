@@ -400,7 +400,7 @@ inline int cross_tables(uint32_t n_regions, const mgx_pairhmm_input_t* regs, con
     return 0;
 }
 
-// Folds the small classes and makes the classes that hold any read, in job order: jobs are laid out in read-table order,
+// Folds the small classes and makes the classes that hold any test case, in job order: jobs are laid out in read-table order,
 // which is class order.
 inline int cross_bins(CrossPlan* p, uint64_t (&count)[kBins], int n_cu, uint32_t block, std::vector<Bin>* bins, uint64_t merge_below = kMergeBelow) {
     int remap[kBins];
@@ -418,7 +418,7 @@ inline int cross_bins(CrossPlan* p, uint64_t (&count)[kBins], int n_cu, uint32_t
     }
     for (int k = 0; k < kBins; ++k) {
         p->rstart[k + 1] = p->rstart[k] + reads_in[k];
-        if (!reads_in[k]) continue;
+        if (!jobs_in[k]) continue;      // no read, or only reads of regions without haplotypes: they stay in the read table, nothing is launched
         Bin bin;
         bin_shape(k, &bin);
         bin.job_begin = (uint32_t)job_begin;

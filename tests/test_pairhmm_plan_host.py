@@ -452,14 +452,17 @@ def test_cross_plan(driver, model):
     check_cross(driver.plan(reads, haps, regions=regions[:1], model=model), reads, haps, regions[:1], model)
 
 
-def test_class_of_reads_without_haplotypes_is_an_empty_launch(driver):
-    """A known defect, pinned as it is so that its fix shows: cross_bins keys a class on its reads, not on its jobs, so a class whose
-    only reads belong to a region without haplotypes is emitted with 0 jobs and a grid of 0 (hipLaunchKernelGGL refuses such a grid:
-    the batch fails instead of skipping the class).  Wanted: no such class in the plan."""
+def test_class_of_reads_without_haplotypes_is_not_in_the_plan(driver):
+    """cross_bins keys a class on its jobs, not on its reads: a class whose only reads belong to a region without haplotypes would be
+    a launch with a grid of 0, which hipLaunchKernelGGL refuses (the batch failed with "invalid configuration argument";
+    test_realign_seams_gpu.py has such a region on the device).  The reads stay in the read table, in their class's place, with no job."""
     p = driver.plan([100, 100, 10], [50], regions=[(0, 2, 0, 1), (2, 3, 0, 0)])
     assert p["rc"] == 0 and p["totals"][:3] == [3, 1, 2]
-    empty = [b for b in p["bins"] if b["job_count"] == 0]
-    assert [(b["G"], b["grid_f32"], b["grid_nhap"]) for b in empty] == [(4, 0, 0)]
+    assert [(b["job_begin"], b["job_count"]) for b in p["bins"]] == [(0, 2)] and all(b["grid_f32"] > 0 and b["grid_nhap"] > 0 for b in p["bins"])
+    assert [(t[2], t[5]) for t in p["rtab"]] == [(10, 0), (100, 0), (100, 1)] and p["rpre_end"] == [2]      # (length, first job)
+    # the same reads with a haplotype: their class is back
+    p = driver.plan([100, 100, 10], [50], regions=[(0, 2, 0, 1), (2, 3, 0, 1)])
+    assert sorted(b["job_count"] for b in p["bins"]) == [1, 2]
 
 
 def test_cross_plan_errors(driver):

@@ -153,12 +153,15 @@ def to_ref_part(regions, rng, hard=False):
     return out
 
 
-def check_to_ref_of_regions(regions, to_ref, res, ref_stride):
-    """start, ref_cigar and status against the restatement applied to the call's own best, offset and cigar"""
+def check_to_ref_of_regions(regions, to_ref, res, ref_stride, every=1):
+    """start, ref_cigar and status against the restatement applied to the call's own best, offset and cigar; `every`: of each
+    region's reads, those whose index is a multiple of it"""
     seen = {}
     for g, (d, t, o) in enumerate(zip(regions, to_ref, res)):
         haps, reads = RC.sequences(d)
         for r, read in enumerate(reads):
+            if r % every:
+                continue
             if not o["keep"][r]:
                 want = (C.DROPPED, 0, [])
             else:

@@ -17,11 +17,13 @@ ALTERNATES = (1, 2, 16, 17, 64, 65, 151, 4096, 4097, 32767)
 
 
 class LayoutDriver:
-    def __init__(self, workdir):
-        self.exe = os.path.join(str(workdir), "sw_layout_san")
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                               "-I", F.CSRC, os.path.join(F.ROOT, "tests", "cpp", "sw_layout_driver.cpp"), "-o", self.exe])
-        self.env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    def __init__(self, workdir, sanitize=True):
+        """sanitize=False: a plain build, for the GPU tests that only want the cuts (no sanitizer runs next to the device)"""
+        self.exe = os.path.join(str(workdir), "sw_layout_san" if sanitize else "sw_layout_plain")
+        how = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined"] if sanitize else ["-O2"]
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + how +
+                              ["-I", F.CSRC, os.path.join(F.ROOT, "tests", "cpp", "sw_layout_driver.cpp"), "-o", self.exe])
+        self.env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1") if sanitize else dict(os.environ)
         self.workdir, self.calls = str(workdir), 0
 
     def run(self, lens, strategies=None, params=F.STANDARD_NGS, paired=0, use16=1, limit=0, slices=0):
